@@ -2,8 +2,10 @@
 """bench.py -- BASELINE.json's metric: training images/sec of Faster R-CNN on synthetic frames, batch 1 per GPU, the
 proposal / RoI-head path on the hand-written HIP kernels.
 
-    python bench.py                          # configs[1]: VGG16, 600x1000, 1 GPU (the headline configuration) + an `also` block
-                                             #   with short driver-timed runs of configs[3] / configs[4] (ResNet-50-FPN fp32 / bf16)
+    python bench.py                          # configs[1]: VGG16, 600x1000, 1 GPU (the headline configuration): the timed steps and the line, nothing else
+    python bench.py --full                   # the same + roofline, hot-path kernel times, cpu_baseline and an `also` block with short
+                                             #   driver-timed runs of configs[3] / configs[4] (ResNet-50-FPN fp32 / bf16)
+    python bench.py --dump-outputs DIR       # + what the last timed step computed, as DIR/<name>.npy (dump_outputs)
     python bench.py --config fpn             # configs[3]: ResNet-50-FPN, 800x1344 (COCO shape padded to /32), fp32
     python bench.py --config fpn --amp bf16  # configs[4]: bf16 autocast on the torch layers + bf16 MFMA RPN head, fp32 box path
     python bench.py --config fpn --graph     # the same step captured once per resident frame in a HIP graph and replayed
@@ -11,7 +13,9 @@ proposal / RoI-head path on the hand-written HIP kernels.
         bench.py --gpus N --steps K --warmup W
 
 One step = forward (backbone -> RPN -> proposals -> targets -> RoIPool / RoIAlign -> head) + loss + backward + SGD on one
-frame per GPU.  Frames and boxes are resident in HBM before the timed region.  Rank 0 prints ONE JSON line.
+frame per GPU.  Frames and boxes are resident in HBM before the timed region.  Rank 0 prints ONE JSON line.  A plain run measures
+the headline figure alone (`value`, `ms_per_step`); roofline, cpu_baseline, also and hot_path's kernel times are measured under --full
+only (null / absent on a plain line).
   roofline     : the hand-written kernel with the largest average launch time in the timed region, timed live with HIP events
                  on its launch stream (libfrcnn_hip's frcnn_prof_* facility; kernels are reported under their own names, the
                  ones rocprofv3 prints); `bound` says what actually bounds it ("latency" for the single-workgroup sequential
@@ -20,7 +24,7 @@ frame per GPU.  Frames and boxes are resident in HBM before the timed region.  R
   cpu_baseline : the oracle's CPU restatement of the same training step (oracle/model_ref.py) on a bounded number of steps.
   hot_path     : per-kernel mean / median / p10 / p90 launch time, bytes, GB/s, PMC traffic; proposals/s from the
                  device-side proposal counts of the timed steps.
-  also         : (default VGG run on one GPU only) the same record for short runs of --config fpn and --config fpn --amp bf16, so
+  also         : (--full VGG run on one GPU only) the same record for short runs of --config fpn and --config fpn --amp bf16, so
                  that BASELINE's "RoIAlign + NMS us/img" and configs[3]/[4] are timed by whoever runs this command.
 """
 import argparse
@@ -28,6 +32,7 @@ import gc
 import glob
 import json
 import os
+import shutil
 import sys
 import time
 
@@ -38,17 +43,23 @@ sys.path.insert(0, ROOT)
 for _k in ("FWD", "BWD", "WRW"):
     os.environ.setdefault("MIOPEN_DEBUG_CONV_DIRECT_NAIVE_CONV_" + _k, "0")
 
-# PyTorch TunableOp: the first time a GEMM shape is seen (the initialisation pass below, outside the W / K accounting) every rocBLAS /
-# hipBLASLt solution for it is timed and the fastest is kept for the rest of the process (~8 s for the dozen shapes of a step).  The
-# default heuristic picks a 64x64 macro-tile for the classifier's 128 x 25088 x 4096 GEMMs that streams the 411 MB weight at 1.46 TB/s
-# (282 us, three of them per step); the tuned pick takes 190 us: 14.57 -> 14.29 ms per VGG step.  --no-tunableop (or
-# FRCNN_BENCH_TUNABLEOP=0) turns it off; the JSON line says which it was and whether the picks were tuned now or read from a file.
+# PyTorch TunableOp: the rocBLAS / hipBLASLt solution of every GEMM shape of a step.  The default heuristic picks a 64x64 macro-tile for
+# the classifier's 128 x 25088 x 4096 GEMMs that streams the 411 MB weight at 1.46 TB/s (282 us, three of them per step); the tuned pick
+# takes 190 us: 14.57 -> 14.29 ms per VGG step.  The picks are FIXED: tools/tunableop_picks.csv (TunableOp's own results file, made by
+# one tuning run of --full on an MI355X) is copied to the results file TunableOp reads at every start.  Timing the candidates in every
+# run instead picked different solutions for the near-tied small head GEMMs from run to run, and a different summation order in one GEMM
+# is enough to send the training steps -- and --dump-outputs -- elsewhere.  A plain run tunes nothing (a shape the file does not list
+# takes the library default); --full still tunes the shapes it lacks (the FPN configurations' own GEMMs).  TunableOp ignores the file
+# when its validator lines (PyTorch / ROCm / hipBLASLt / rocBLAS versions, architecture) do not match this software.  --no-tunableop (or
+# FRCNN_BENCH_TUNABLEOP=0) turns it off; the JSON line says which it was.
 TUNABLEOP = os.environ.get("FRCNN_BENCH_TUNABLEOP", "1") != "0" and "--no-tunableop" not in sys.argv
-TUNABLEOP_FILE = os.path.join(os.environ.get("TMPDIR", "/tmp"), "frcnn_bench_tunableop_%d.csv")
-TUNABLEOP_CACHED = bool(glob.glob(TUNABLEOP_FILE.replace("%d", "*")))
+TUNABLEOP_PICKS = os.path.join(ROOT, "tools", "tunableop_picks.csv")
+TUNABLEOP_FILE = os.path.join(os.environ.get("TMPDIR", "/tmp"), "frcnn_bench_tunableop_picks_%d.csv")
 if TUNABLEOP:
+    # the file of this rank's device (TunableOp inserts the device ordinal); ranks sharing a device (gloo rehearsal) copy the same bytes
+    shutil.copyfile(TUNABLEOP_PICKS, TUNABLEOP_FILE % int(os.environ.get("LOCAL_RANK", "0")))
     os.environ.setdefault("PYTORCH_TUNABLEOP_ENABLED", "1")
-    os.environ.setdefault("PYTORCH_TUNABLEOP_TUNING", "1")
+    os.environ.setdefault("PYTORCH_TUNABLEOP_TUNING", "1" if "--full" in sys.argv else "0")
     os.environ.setdefault("PYTORCH_TUNABLEOP_VERBOSE", "0")
     os.environ.setdefault("PYTORCH_TUNABLEOP_FILENAME", TUNABLEOP_FILE)
 
@@ -267,8 +278,56 @@ def timed_region(step, steps, warmup, device, armed=None, before_step=None):
     return {"dt": dt, "dt_local": dt_local, "per_rank_ms": per_rank_ms, "step_ms": step_ms, "last": last}
 
 
-def run_config(args, config, amp, steps, warmup, graph, rank, world, device, with_cpu):
-    """One bench record (the JSON object described in the module docstring) for one configuration."""
+DUMP_SAMPLE = 4096            # --dump-outputs: elements drawn from each parameter tensor larger than this (and from its gradient)
+DUMP_LIMIT = 64 << 20         # bytes, all files together
+
+
+def dump_outputs(path, pred, target, losses, count, params):
+    """--dump-outputs: what one training step computed, as path/<name>.npy -- float32, or float64 for integer tensors (exact):
+    pred_* / target_* = the four predictions and four targets the model's forward returned, loss_terms = (total, rpn_cls, rpn_reg,
+    fast_rcnn_cls, fast_rcnn_reg), proposal_count, and for the trainable parameters (`params` = [(name, parameter, gradient or None)],
+    in the model's order) after the step's update and their gradients: the L2 norm of every tensor (float64) and a fixed sample of
+    DUMP_SAMPLE elements of every larger one (indices drawn from a seeded generator: the same in every run).  Returns {name: bytes}."""
+    import numpy as np
+
+    def host(t):
+        t = t.detach().cpu()
+        return t.float().numpy() if t.is_floating_point() else t.double().numpy()
+    out = {}
+    for i, name in enumerate(("rpn_cls", "rpn_reg", "fast_rcnn_cls", "fast_rcnn_reg")):
+        out["pred_" + name] = host(pred[i])
+        out["target_" + name] = host(target[i])
+    out["loss_terms"] = np.array([float(v.detach()) for v in losses], np.float64)
+    out["proposal_count"] = host(count).reshape(-1)
+    rng = np.random.RandomState(0)
+    samples = {"params": [], "grads": []}
+    norms = {"params": [], "grads": []}
+    for _, p, g in params:
+        n = p.numel()
+        idx = None if n <= DUMP_SAMPLE else torch.from_numpy(np.sort(rng.randint(0, n, DUMP_SAMPLE))).to(p.device)
+        for key, t in (("params", p), ("grads", g)):
+            if t is None:                             # a parameter the step did not reach: NaN, not a silent zero
+                samples[key].append(np.full(min(n, DUMP_SAMPLE), np.nan, np.float32))
+                norms[key].append(np.nan)
+                continue
+            flat = t.detach().reshape(-1)
+            samples[key].append((flat if idx is None else flat[idx]).float().cpu().numpy())
+            norms[key].append(float(torch.linalg.vector_norm(flat, dtype=torch.float64)))
+    for key in ("params", "grads"):
+        out[key + "_sample"] = np.concatenate(samples[key]) if samples[key] else np.zeros(0, np.float32)
+        out[key + "_norm"] = np.array(norms[key], np.float64)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT))
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {name: a.nbytes for name, a in out.items()}
+
+
+def run_config(args, config, amp, steps, warmup, graph, rank, world, device, with_cpu, dump=None):
+    """One bench record (the JSON object described in the module docstring) for one configuration; `dump` = a directory: what the last
+    timed step computed is written there (dump_outputs)."""
     from faster_rcnn_pytorch_amd import _lib, ops, parallel
     from faster_rcnn_pytorch_amd.loss import FRCNNLoss
     cfg = CONFIGS[config]
@@ -301,8 +360,13 @@ def run_config(args, config, amp, steps, warmup, graph, rank, world, device, wit
         frames.append((x, b.to(device), l.to(device)))
     torch.cuda.synchronize()
     counts = []                                       # device-side proposal counts of the timed steps (read after the timed region)
+    trainable = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
+    # --dump-outputs: frame -> (predictions, targets, loss terms, gradients, proposal count) of its step, kept as references to the step's own
+    # tensors (no copy is added to the step): eager, the last timed step's; as graphs, every frame's captured outputs, which each replay rewrites
+    keep = {}
+    last = warmup + steps - 1
 
-    def body(fi):
+    def body(fi, stash=False):
         x, b, l = frames[fi]
         if amp == "bf16":
             with torch.autocast("cuda", dtype=torch.bfloat16):
@@ -310,14 +374,17 @@ def run_config(args, config, amp, steps, warmup, graph, rank, world, device, wit
             pred = tuple(p.float() for p in pred)
         else:
             pred, target = net(x, [b], [l])
-        loss = crit(pred, target)[0]
+        losses = crit(pred, target)
+        loss = losses[0]
         opt.zero_grad(set_to_none=True)
         loss.backward()
         opt.step()
+        if stash:
+            keep[fi] = (pred, target, losses, [p.grad for _, p in trainable], model.last_proposal_count)
         return loss
 
     def eager_step(i):
-        loss = body(i % len(frames))
+        loss = body(i % len(frames), stash=bool(dump) and i == last)
         counts.append(model.last_proposal_count)
         return loss
 
@@ -327,8 +394,9 @@ def run_config(args, config, amp, steps, warmup, graph, rank, world, device, wit
     for i in range(3):
         eager_step(i)
     torch.cuda.synchronize()
-    ops.CONV_TRACE = []                              # which calls the fp32 conv stage gets in one step (shapes only; for the roofline's flop / byte totals)
-    ops.AFFINE_TRACE = {}                            # likewise the norm / residual / ReLU passes: launches and the bytes each must move
+    if args.full:
+        ops.CONV_TRACE = []                          # which calls the fp32 conv stage gets in one step (shapes only; for the roofline's flop / byte totals)
+        ops.AFFINE_TRACE = {}                        # likewise the norm / residual / ReLU passes: launches and the bytes each must move
     eager_step(3)
     conv_calls, ops.CONV_TRACE = ops.CONV_TRACE, None
     affine_calls, ops.AFFINE_TRACE = ops.AFFINE_TRACE, None
@@ -351,7 +419,10 @@ def run_config(args, config, amp, steps, warmup, graph, rank, world, device, wit
                 pred = tuple(p.float() for p in pred)
             else:
                 pred, target = model(x, [b], [l])
-            return crit(pred, target), pred
+            losses = crit(pred, target)
+            if dump:
+                keep[fi] = (pred, target, losses, None, model.last_proposal_count)     # (the gradients: GraphStep's persistent buffers)
+            return losses, pred
 
         def record(fi, losses):
             keep_loss[fi:fi + 1].copy_(losses[0].detach().reshape(1))
@@ -384,7 +455,7 @@ def run_config(args, config, amp, steps, warmup, graph, rank, world, device, wit
             g = torch.cuda.CUDAGraph()
             opt.zero_grad(set_to_none=True)
             with torch.cuda.graph(g, pool=pool):
-                loss = body(fi)
+                loss = body(fi, stash=bool(dump))
                 keep_loss[fi:fi + 1].copy_(loss.detach().reshape(1))
                 keep_cnt[fi:fi + 1].copy_(model.last_proposal_count)
             pool = g.pool()
@@ -400,7 +471,8 @@ def run_config(args, config, amp, steps, warmup, graph, rank, world, device, wit
     # long-lived: freeze it and keep the collector off while steps are timed (reference counting still frees the step's tensors).
     if not args.gc_on:
         gc.collect(); gc.freeze(); gc.disable()
-    events = not args.no_kernel_events and not graph
+    kernel_events = args.full and not args.no_kernel_events       # live per-kernel times (roofline, hot_path): --full only
+    events = kernel_events and not graph
     ms0 = {}
 
     def armed():                                      # between the warm-up and the timed region
@@ -418,13 +490,18 @@ def run_config(args, config, amp, steps, warmup, graph, rank, world, device, wit
     _lib.prof_enable(False)
     dt, per_rank_ms, step_ms, loss = tr["dt"], tr["per_rank_ms"], tr["step_ms"], tr["last"]
     log("timed region: %d steps in %.3f s" % (steps, dt))
+    if dump and rank == 0:
+        pred, target, losses, grads, count = keep[last % len(frames)]
+        grads = grads or [p.grad for _, p in trainable]
+        dump_outputs(dump, pred, target, losses, count, [(n, p, g) for (n, p), g in zip(trainable, grads)])
+        log("outputs of the last timed step written to %s" % dump)
     gc.enable()
     ms1 = torch.cuda.memory_stats(device)
     allocator = {k: int(ms1.get(k, 0) - ms0.get(k, 0)) for k in ("num_device_alloc", "num_device_free", "num_alloc_retries", "num_ooms")}
     final_loss = float(loss.detach())
     model.check_device_status()                      # sticky device-side error word (aborted scan / short sample): raises if set
     n_sampled = len(range(0, steps, args.event_every))               # timed steps whose kernels were bracketed
-    if graph and not args.no_kernel_events:
+    if graph and kernel_events:
         # a captured graph cannot carry the per-kernel event brackets: the live kernel times of --graph come from a short EAGER pass
         # of the same steps right after the timed region (same process, same frames, warm)
         _lib.prof_reset()
@@ -436,7 +513,7 @@ def run_config(args, config, amp, steps, warmup, graph, rank, world, device, wit
         _lib.prof_enable(False)
     if graphs:
         counts[:] = [g[2] for g in graphs]                           # persistent copies written inside the captured steps
-    samples = {} if args.no_kernel_events else _lib.prof_samples()
+    samples = _lib.prof_samples() if kernel_events else {}
     n_props = [int(c.item()) for c in counts if c is not None]       # device counts, read after the timed region
     backend = torch.distributed.get_backend() if world > 1 else None
     world_seen = torch.distributed.get_world_size() if world > 1 else 1
@@ -444,7 +521,7 @@ def run_config(args, config, amp, steps, warmup, graph, rank, world, device, wit
 
     if rank != 0:
         return None
-    pmc, pmc_src = load_pmc(config, amp)
+    pmc, pmc_src = load_pmc(config, amp) if samples else ({}, None)
     cpu = cpu_baseline(config, cfg, args.cpu_steps, args.lr) if with_cpu else None
     return build_record(config, amp, world=world, steps=steps, warmup=warmup, dt=dt, per_rank_ms=per_rank_ms, step_ms=step_ms,
                         samples=samples, n_sampled=n_sampled, n_props=n_props, graph=graph, pmc=pmc, pmc_src=pmc_src, cpu=cpu,
@@ -581,6 +658,7 @@ def build_record(config, amp, *, world, steps, warmup, dt, per_rank_ms, step_ms,
             roofline["hbm_kernel"] = roofline_of(max(hbm, key=lambda k: per_kernel[k]["us_per_img"]))
         if graph:
             roofline["measured_in"] = "an eager pass of %d steps after the timed graph replays (a captured graph cannot carry the event brackets)" % n_sampled
+    sampled = (lambda x: x) if per_kernel else (lambda x: None)      # kernel totals of a run without kernel samples: null, not 0
     hot_us = sum(v["us_per_img"] for v in per_kernel.values())
     smed, sp10, sp90 = percentiles(step_ms)
     st = sum(v["us_per_img"] for k, v in per_kernel.items() if k.startswith(("proposal_prologue", "topk_", "nms_", "level_ids")))
@@ -600,23 +678,25 @@ def build_record(config, amp, *, world, steps, warmup, dt, per_rank_ms, step_ms,
                      "source": "HIP events at the step boundaries on the main stream (rank 0)"} if step_ms else None),
         "allocator_in_timed_region": allocator,
         "conditions": {
-            "gemm_selection": ("PyTorch TunableOp: rocBLAS / hipBLASLt solution timed and picked per GEMM shape during the initialisation pass"
+            "gemm_selection": ("PyTorch TunableOp: rocBLAS / hipBLASLt solution per GEMM shape, fixed by a committed results file"
                                if os.environ.get("PYTORCH_TUNABLEOP_ENABLED") == "1" else "library default heuristics"),
-            "tunableop_results": (("read from a results file of an earlier run + tuned now for new shapes" if TUNABLEOP_CACHED else "tuned in this process")
+            "tunableop_results": (("read from tools/tunableop_picks.csv (the same solutions in every run)"
+                                   + ("; shapes it does not list tuned in this process" if os.environ.get("PYTORCH_TUNABLEOP_TUNING") == "1" else
+                                      "; shapes it does not list: library default"))
                                   if os.environ.get("PYTORCH_TUNABLEOP_ENABLED") == "1" else None),
             "python_gc": "on" if gc_on else "frozen after initialisation, off while the timed steps run (--gc-on to leave it on)",
             "off_switches": "--no-tunableop --gc-on give the untuned, collector-on figure"},
         "distributed": {"backend": backend, "world_size_seen_by_rank0": world_seen, "per_rank_ms_per_step": per_rank_ms,
                         "min_ms": min(per_rank_ms), "max_ms": max(per_rank_ms), "ddp": ddp},
-        "hot_path": {"sum_kernel_us_per_img": round(hot_us, 1),
-                     "launches_per_img": round(sum(v["launches_per_img"] for v in per_kernel.values()), 1),
+        "hot_path": {"sum_kernel_us_per_img": sampled(round(hot_us, 1)),
+                     "launches_per_img": sampled(round(sum(v["launches_per_img"] for v in per_kernel.values()), 1)),
                      # proposals actually produced: mean of the device-side counts of the timed steps (capacity P is an upper bound)
                      "mean_proposals_per_img": round(mean_props, 1) if mean_props is not None else None,
                      "proposals_per_s": round(value * mean_props, 1) if mean_props is not None else None,
                      # BASELINE.json's second figure: NMS + RoI pooling forward/backward, HIP-event us per image
-                     "nms_plus_roi_us_per_img": round(sum(v["us_per_img"] for k, v in per_kernel.items() if k.startswith(("nms_", "roi_"))), 1),
+                     "nms_plus_roi_us_per_img": sampled(round(sum(v["us_per_img"] for k, v in per_kernel.items() if k.startswith(("nms_", "roi_"))), 1)),
                      # SURVEY 8(d) "proposals/s" unit: one image's proposal stage = prologue -> top-k -> NMS -> P rois
-                     "proposal_stage_us_per_img": round(st, 1),
+                     "proposal_stage_us_per_img": sampled(round(st, 1)),
                      "proposal_stage_proposals_per_s": round(mean_props / (st * 1e-6), 0) if (st and mean_props is not None) else None,
                      "kernels": per_kernel},
         "final_loss": round(final_loss, 4), "device_status": 0,
@@ -722,6 +802,11 @@ def main():
                          "fp32 operands cut exactly into three bf16 pieces, six bf16 matrix instructions per 16 k rows, fp32 accumulation (as close to float64)")
     ap.add_argument("--amp", default="none", choices=["none", "bf16"],
                     help="autocast the torch layers (backbone / RPN convs / FC head); NOT the default: the reference trains in fp32")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: live per-kernel times (roofline, hot_path), the CPU baseline and, for the default "
+                         "configuration on one GPU, the `also` runs; a plain run times the steps and prints the line, nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (dump_outputs; a few MB)")
     args = ap.parse_args()
 
     from faster_rcnn_pytorch_amd import parallel
@@ -747,10 +832,10 @@ def main():
                                          "(tests: as close to float64 as the fp32 matrix instruction)")
         return rec
     out = tag_products(run_config(args, args.config, args.amp, args.steps, args.warmup, args.graph, rank, world, device,
-                                  with_cpu=(not args.no_cpu_baseline and world == 1)))
+                                  with_cpu=(args.full and not args.no_cpu_baseline and world == 1), dump=args.dump_outputs))
     release()
     also = []
-    if rank == 0 and world == 1 and not args.no_also and args.config == "vgg" and args.amp == "none" and not args.graph:
+    if args.full and rank == 0 and world == 1 and not args.no_also and args.config == "vgg" and args.amp == "none" and not args.graph:
         # BASELINE.json configs[3] / configs[4] and its "RoIAlign + NMS us/img" figure, timed by the same command (short runs).
         # The FPN step enqueues ~2500 launches from Python and is host-bound when submitted launch by launch (its eager figure moves
         # +-8 % between boxes); both entries are therefore timed as HIP-graph replays (--graph), with the eager figure beside it.

@@ -3,8 +3,10 @@
 end to end before the first real 8-GPU launch (world-size-2 gloo, stub model)."""
 import json
 import os
+import subprocess
 import sys
 
+import pytest
 import torch
 import torch.multiprocessing as mp
 
@@ -251,3 +253,71 @@ def test_the_bench_mirror_of_the_stage_tiling_is_the_library_rule():
         assert (m, tp) == bench.wino_tiling(shapes), shapes
     assert bench.wino_tiling([(37, 62)]) == (4, 192) and bench.wino_tiling([(75, 125)]) == (4, 640) and bench.wino_tiling([(13, 21)]) == (2, 128)
 
+
+
+def _dump_step(bench, path):
+    torch.manual_seed(0)
+    lin = torch.nn.Linear(100, 50)                                            # 5000 weights: more than DUMP_SAMPLE, so sampled; 50 biases whole
+    lin(torch.randn(3, 100)).pow(2).sum().backward()
+    pred = (torch.randn(1, 10, 2), torch.randn(1, 10, 4), torch.randn(4, 3), torch.randn(4, 4))
+    target = (torch.tensor([-1, 0, 1, 1, 0, 0, -1, 1, 0, 1], dtype=torch.int8), torch.randn(10, 4), torch.tensor([0, 2, 1, 0]), torch.randn(4, 4))
+    losses = tuple(torch.tensor(v) for v in (1.5, 0.5, 0.25, 0.5, 0.25))
+    sizes = bench.dump_outputs(str(path), pred, target, losses, torch.tensor([7], dtype=torch.int32),
+                               [("weight", lin.weight, lin.weight.grad), ("bias", lin.bias, None)])
+    return sizes, lin, pred, target
+
+
+def test_dump_outputs_writes_the_step_as_float_arrays_with_a_fixed_sample(tmp_path):
+    """--dump-outputs: every file float32 / float64 (integer targets exactly, as float64), the parameter sample drawn at the same indices in
+    every run, a parameter without a gradient marked NaN rather than zero, everything under the 64 MB limit."""
+    import numpy as np
+    import bench
+    sizes, lin, pred, target = _dump_step(bench, tmp_path / "a")
+    _dump_step(bench, tmp_path / "b")
+    assert sum(sizes.values()) <= bench.DUMP_LIMIT == 64 << 20
+    names = sorted(f[:-4] for f in os.listdir(tmp_path / "a"))
+    assert names == sorted(sizes)
+    for n in names:
+        a, b = np.load(tmp_path / "a" / (n + ".npy")), np.load(tmp_path / "b" / (n + ".npy"))
+        assert a.dtype in (np.float32, np.float64), n
+        assert np.array_equal(a, b, equal_nan=True), n                     # same inputs, same files
+    d = lambda n: np.load(tmp_path / "a" / (n + ".npy"))                    # noqa: E731
+    assert np.array_equal(d("pred_rpn_reg"), pred[1].numpy()) and np.array_equal(d("target_rpn_cls"), target[0].double().numpy())
+    assert d("target_fast_rcnn_cls").dtype == np.float64 and np.array_equal(d("target_fast_rcnn_cls"), [0, 2, 1, 0])
+    assert list(d("loss_terms")) == [1.5, 0.5, 0.25, 0.5, 0.25] and list(d("proposal_count")) == [7]
+    ps, gs = d("params_sample"), d("grads_sample")
+    assert ps.shape == gs.shape == (bench.DUMP_SAMPLE + 50,)
+    assert np.isin(ps[:bench.DUMP_SAMPLE], lin.weight.detach().numpy().ravel()).all() and np.array_equal(ps[bench.DUMP_SAMPLE:], lin.bias.detach().numpy())
+    w, g = lin.weight.detach().numpy().ravel(), lin.weight.grad.numpy().ravel()
+    assert all(g[np.nonzero(w == v)[0][0]] == gv for v, gv in zip(ps[:64], gs[:64]))    # a gradient sample sits at its parameter's index
+    assert np.isnan(gs[bench.DUMP_SAMPLE:]).all() and np.isnan(d("grads_norm")[1])
+    assert abs(d("params_norm")[0] - np.linalg.norm(w.astype(np.float64))) < 1e-9 and abs(d("grads_norm")[0] - np.linalg.norm(g.astype(np.float64))) < 1e-9
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_times_the_given_steps_and_dumps_the_same_outputs_every_run(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: exactly K timed steps on the line, ms_per_step = 1000 / value on one GPU, none of
+    the --full extras, and the last timed step's outputs in DIR (finite loss terms, a proposal count within the post-NMS capacity) -- the SAME
+    files bit for bit from two runs, each with a temporary directory of its own (nothing carried over: the GEMM picks are the committed ones)."""
+    import numpy as np
+    runs = []
+    for name in ("a", "b"):
+        out, tmp = tmp_path / ("outputs_" + name), tmp_path / ("tmp_" + name)
+        tmp.mkdir()
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--dump-outputs", str(out)],
+                           cwd=str(tmp_path), capture_output=True, text=True, timeout=600, env=dict(os.environ, TMPDIR=str(tmp)))
+        assert r.returncode == 0, r.stderr[-4000:]
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        assert line["steps"] == 3 and line["warmup"] == 2 and line["unit"] == "images/s" and line["dtype"] == "f32" and line["higher_is_better"] is True
+        assert abs(line["ms_per_step"] - 1e3 / line["value"]) < 0.01 * line["ms_per_step"]
+        assert line["roofline"] is None and line["cpu_baseline"] is None and "also" not in line and line["hot_path"]["sum_kernel_us_per_img"] is None
+        assert line["conditions"]["tunableop"] == "cached"
+        runs.append({f[:-4]: np.load(out / f) for f in os.listdir(out)})
+    files = runs[0]
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values()) and sum(a.nbytes for a in files.values()) <= 64 << 20
+    assert np.isfinite(files["loss_terms"]).all() and files["loss_terms"].shape == (5,)
+    assert 0 < files["proposal_count"][0] <= 2000 and files["pred_rpn_cls"].shape == (1, 20646, 2)
+    assert np.isfinite(files["params_sample"]).all() and np.isfinite(files["grads_sample"]).all()
+    assert sorted(runs[1]) == sorted(files)
+    for k in files:
+        assert np.array_equal(files[k], runs[1][k], equal_nan=True), k
