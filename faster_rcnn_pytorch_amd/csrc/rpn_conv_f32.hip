@@ -943,7 +943,8 @@ extern "C" __attribute__((visibility("default"))) int frcnn_debug_wn_stamps(unsi
 // MT x NW = the workgroup's output tile (128 or 64 each way: the 64-channel layers of a backbone have a 64-wide side); its four waves sit
 // 2 x 2, a wave owns (MT / 2) x (NW / 2) = MI x NI MFMA tiles of 32 x 32.
 // SPLIT (round 5; opt-in, frcnn_conv3x3_f32_products): the SAME fp32 operands from the SAME LDS image, but the product on the bf16 matrix cores -- every
-// value is cut into three bf16 pieces in registers (v = h + m + l EXACTLY: h = v's upper 16 bits, the residuals are exact fp32 differences), and a tile's
+// value is cut into three bf16 pieces in registers (v = h + m + l EXACTLY: h = v's upper 16 bits, m = the residual rounded to bf16, l = what remains;
+// the residuals are exact fp32 differences -- for |v| >= 2^-110, below which l falls under fp32's normal range and the cut loses it), and a tile's
 // 16 k rows are six v_mfma_f32_32x32x16_bf16 (l h, h l, m m, m h, h m, h h; the three dropped products are each <= 2^-24 of the term) = 192 matrix-pipe
 // cycles where the fp32 instruction needs 8 x 64.  Against float64 the result is as close as the fp32 instruction's (tools/dev/micro/split_product_check.hip,
 // profiles/r05_split_product_check.txt: rms error / sum |a b| 1.9e-8 vs 2.4e-8 at K = 256 ... 4096 on mixed-sign data).
@@ -956,9 +957,14 @@ __device__ __forceinline__ void wn_cut8(const float *v, wn_u32x4 &h, wn_u32x4 &m
         const unsigned x0 = __builtin_bit_cast(unsigned, v[2 * p]), x1 = __builtin_bit_cast(unsigned, v[2 * p + 1]);
         h[p] = __builtin_amdgcn_perm(x1, x0, 0x07060302u);                // bf16 element 2 p = upper half of x0, 2 p + 1 = upper half of x1
         const float ra = v[2 * p] - __builtin_bit_cast(float, x0 & 0xFFFF0000u), rb = v[2 * p + 1] - __builtin_bit_cast(float, x1 & 0xFFFF0000u);
+        // m = the residual ROUNDED to the nearest bf16 (ties to even), not truncated: truncated, every piece carried v's sign, so the three dropped products
+        // (m l, l m, l l) all had the term's sign and a sum without cancellation came out -0.6 u low (tests/test_gpu_products_numerics.py, all-positive
+        // operands; tools/dev/micro/split_dc_check.hip (e)).  Rounded, l = r - m takes either sign and those products average out.  Still exact: r has at
+        // most 16 significant bits, m keeps the upper 8 (rounded), l the rest
         const unsigned r0 = __builtin_bit_cast(unsigned, ra), r1 = __builtin_bit_cast(unsigned, rb);
-        m[p] = __builtin_amdgcn_perm(r1, r0, 0x07060302u);
-        const float qa = ra - __builtin_bit_cast(float, r0 & 0xFFFF0000u), qb = rb - __builtin_bit_cast(float, r1 & 0xFFFF0000u);
+        const unsigned n0 = (r0 + 0x7FFFu + ((r0 >> 16) & 1u)) & 0xFFFF0000u, n1 = (r1 + 0x7FFFu + ((r1 >> 16) & 1u)) & 0xFFFF0000u;
+        m[p] = __builtin_amdgcn_perm(n1, n0, 0x07060302u);
+        const float qa = ra - __builtin_bit_cast(float, n0), qb = rb - __builtin_bit_cast(float, n1);
         l[p] = __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, qb), __builtin_bit_cast(unsigned, qa), 0x07060302u);
     }
 }

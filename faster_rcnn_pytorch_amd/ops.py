@@ -596,7 +596,8 @@ def conv3x3_bf16_c256_supported(x, weight):
 def conv3x3_f32_products(mode=None):
     """How the fp32 conv stage takes its products (process-wide; csrc/rpn_conv_f32.hip, frcnn_conv3x3_f32_products): "native" = the fp32 matrix instruction (default),
     "split" = the same fp32 operands cut exactly into three bf16 pieces each and six bf16 matrix instructions per 16 k rows with fp32 accumulation -- as
-    close to float64 as "native", 1.4-1.5 x the rate.  Returns the previous mode; None only asks."""
+    close to float64 as "native", 1.4-1.5 x the rate.  Also governs gemm_nt (same kernel); the fused 64 -> 64 product on 4 x 4 tiles stays native.  The
+    split cut is exact for operands with |v| >= 2^-110 (and 0); smaller ones lose their last piece (< 2^-126).  Returns the previous mode; None only asks."""
     names = ("native", "split")
     if mode is None:
         return names[lib.frcnn_conv3x3_f32_products(-1)]

@@ -255,6 +255,9 @@ int frcnn_conv3x3_f32_supported(const int *H_host, const int *W_host, int n_leve
  *   1  the same fp32 operands cut into three bf16 pieces each in registers (exactly) and six v_mfma_f32_32x32x16_bf16 per 16 k rows, fp32 accumulation:
  *      against float64 as close as mode 0 (tests/test_gpu_ops.py: test_conv3x3_f32_split_products_*), 1.4-1.5 x the rate.  Inputs, outputs, workspaces and
  *      every other kernel of the stage are the same.  Environment: FRCNN_CONV_F32_PRODUCTS=split sets the initial value.
+ * The switch also governs frcnn_gemm_nt_f32 (the 1 x 1 weight gradients: the same product kernel).  It does not reach the fused 64 -> 64 product on
+ * 4 x 4 tiles (rpn_wino_gemm_out64_kernel), which stays on the fp32 instruction in either mode.  Mode 1's cut is exact for |v| >= 2^-110 and 0; below,
+ * the smallest piece falls under fp32's normal range and is lost (error < 2^-126 per operand; tests/test_gpu_products_numerics.py).
  * Returns the previous mode; mode < 0 only asks. */
 int frcnn_conv3x3_f32_products(int mode);
 int frcnn_conv3x3_f32_fwd(const float *const *x_levels, float *const *y_levels, const int *H_host, const int *W_host, int n_levels, int Cin, int Cout,

@@ -1720,6 +1720,7 @@ def test_conv3x3_f32_stage_vs_float64(ops, name, Cin, Cout, shapes, use_bias, re
 
 
 SPLIT_CASES = [c for c in CONV3X3_CASES if c[0] in ("vgg_conv3_1", "vgg_conv4_1", "wide_in", "levels", "vgg_conv2_1", "narrow_both", "wide_out_64", "rpn_37x62")]
+SPLIT_CASES += [("vgg_conv5_1", 512, 512, [(37, 62)], True, True, True)]           # Cin = 512: five of VGG16's thirteen convolutions are 512 -> 512
 
 
 @pytest.mark.parametrize("name,Cin,Cout,shapes,use_bias,relu,grads", SPLIT_CASES, ids=[c[0] for c in SPLIT_CASES])
