@@ -36,6 +36,7 @@
 #include "frcnn_common.h"
 #include "frcnn_internal.h"
 #include "frcnn_layout.h"
+#include "nms_dev.h"
 FRCNN_LAYOUT_STAMP(nms);
 #include <cstdlib>
 #include <cstring>
@@ -59,19 +60,6 @@ extern "C" __attribute__((visibility("default"))) void frcnn_nms_sweep_read(void
 #define NMS_TV(idx, slot, v) do {} while (0)
 #define NMS_TSWEEP(idx, k) do {} while (0)
 #endif
-
-// v_max_f32 / v_min_f32 without LLVM's sNaN-canonicalising v_max(x,x) in front of every operand
-__device__ __forceinline__ float vmaxf(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ float vminf(float a, float b) { float r; asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-
-// exact form: torchvision's expression, IEEE division (symmetric in its two boxes: fp + and min/max commute)
-__device__ __forceinline__ bool nms_suppress_exact(float4 a, float area_a, float4 b, float area_b, float thr)
-{
-    const float w = vmaxf(vminf(a.z, b.z) - vmaxf(a.x, b.x), 0.0f);
-    const float h = vmaxf(vminf(a.w, b.w) - vmaxf(a.y, b.y), 0.0f);
-    const float inter = w * h;
-    return inter / (area_a + area_b - inter) > thr;
-}
 
 // 32 suppressor candidates [j0, j0+32) of one tile against my box.  Returns the per-lane result word; *unsure gets the lanes (as a
 // wave mask) for which at least one candidate fell inside the guard band (or had a non-positive union) and must be re-evaluated

@@ -1,0 +1,43 @@
+"""Graph-captured inference: FRCNN.detect (both mirrors) recorded once into a HIP graph and replayed per frame.
+
+The test loop of the reference (test.py:60) calls predict once per image; every call pays the Python launch cost of the whole
+network.  DetectGraph records detect -- which has no host sync -- for one input size and replays it."""
+import torch
+
+
+class DetectGraph(object):
+    """model.detect at a fixed [1, 3, H, W] input size, captured into one torch.cuda.graph.
+
+    __call__(x) copies x into the graph's static input buffer, replays, and returns the graph's static ops.Detections: its tensors are
+    overwritten by the next call (clone them, or call .to_host(), to keep a result).  The score threshold lives in a device tensor
+    that the kernels read at replay time, so set_threshold() takes effect on the next call without a new capture."""
+
+    def __init__(self, model, image_hw, threshold=0.05, device=None, warmup=2):
+        m = getattr(model, "module", model)                     # a DDP-wrapped model: capture the module itself
+        dev = torch.device(device) if device is not None else next(m.parameters()).device
+        H, W = (int(v) for v in image_hw)
+        self.model = m
+        self.image_hw = (H, W)
+        self.x = torch.zeros((1, 3, H, W), dtype=torch.float32, device=dev)
+        self.threshold = torch.full((1,), float(threshold), dtype=torch.float32, device=dev)
+        # eager warm-up on a side stream: lazy allocations, cached constants and anchor grids, workspaces
+        side = torch.cuda.Stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            for _ in range(max(int(warmup), 1)):
+                m.detect(self.x, float(threshold), threshold_dev=self.threshold)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            self.out = m.detect(self.x, float(threshold), threshold_dev=self.threshold)
+
+    def set_threshold(self, t):
+        """Writes the device threshold in place: the next replay uses it."""
+        self.threshold.fill_(float(t))
+
+    def __call__(self, x):
+        if tuple(x.shape) != tuple(self.x.shape):
+            raise ValueError("DetectGraph: captured for input %s, got %s" % (tuple(self.x.shape), tuple(x.shape)))
+        self.x.copy_(x)
+        self.graph.replay()
+        return self.out

@@ -332,6 +332,22 @@ class FRCNN(nn.Module):
         pred_bbox = pred_bbox.reshape(-1, self.num_classes * 4).clamp(min=0, max=1)
         return self._suppress(pred_bbox, pred_cls, threshold)
 
+    @torch.no_grad()
+    def detect(self, x, opts_or_threshold, threshold_dev=None, want_prob=False):
+        """predict without a host sync (graph-capturable): the test-mode path with the fixed-capacity proposals and their device count,
+        the head on all P rows, and the post-processing of models/model.py:368-402 in ops.detect_postprocess.  threshold_dev (a device
+        float32[1]) overrides the threshold when given.  Returns ops.Detections (its n_rois is the proposal count); .to_host() gives
+        what predict returns."""
+        threshold = float(getattr(opts_or_threshold, "thres", opts_or_threshold))
+        features = self.extractor(x)
+        hw = x.size()[2:]
+        pred_rpn_cls, pred_rpn_reg = self.rpn(features)
+        rois, n_rois, _ = self.rp.propose(pred_rpn_cls.squeeze(0), pred_rpn_reg.squeeze(0), None, "test",
+                                          grid=self.anchor_maker.grid_desc(hw))
+        pred_fast_rcnn_cls, pred_fast_rcnn_reg = self.fast_rcnn_head(features, rois)      # rows >= n_rois: zero boxes, ignored below
+        return ops.detect_postprocess(pred_fast_rcnn_cls, pred_fast_rcnn_reg, rois, n_rois, threshold, 0.3, threshold_dev=threshold_dev,
+                                      want_prob=want_prob)
+
     def _suppress(self, raw_cls_bbox, raw_prob, threshold):
         """models/model.py:382-402 (per-class score mask + nms(0.3), class 0 = background skipped, results concatenated
         class by class) as ONE class-aware NMS: 2 host syncs in total instead of 2 per class."""

@@ -466,6 +466,16 @@ class FRCNN(nn.Module):
         pred_bbox = pred_bbox.reshape(-1, self.num_classes * 4).clamp(min=0, max=1)
         return self._suppress(pred_bbox, pred_cls, threshold)
 
+    @torch.no_grad()
+    def detect(self, x, opts_or_threshold, threshold_dev=None, want_prob=False):
+        """predict without a host sync (see models.model.FRCNN.detect): models/new_model.py:420-470 on the fixed-capacity proposals."""
+        threshold = float(getattr(opts_or_threshold, "thres", opts_or_threshold))
+        features = self.backbone(x)
+        _, _, rois, n_rois, _ = self.rpn.propose(x, features, "test")
+        pred_fast_rcnn_cls, pred_fast_rcnn_reg = self.frcnn_head(features, rois, x.shape[2:])
+        return ops.detect_postprocess(pred_fast_rcnn_cls, pred_fast_rcnn_reg, rois, n_rois, threshold, 0.3, threshold_dev=threshold_dev,
+                                      want_prob=want_prob)
+
     def _suppress(self, raw_cls_bbox, raw_prob, threshold):
         """models/model.py:382-402 (per-class score mask + nms(0.3), class 0 = background skipped, results concatenated
         class by class) as ONE class-aware NMS: 2 host syncs in total instead of 2 per class."""

@@ -8,10 +8,12 @@ Mirrors (file:line under the reference):
   torchvision.ops.RoIPool        as called at models/model.py:97,113
   torchvision.ops.MultiScaleRoIAlign   as called at models/new_model.py:127,143
   torchvision AnchorGenerator    as called at models/new_model.py:23-25,46
+  FRCNN.predict post-processing  models/model.py:368-402, models/new_model.py:420-470 (detect_postprocess)
 
 PyTorch is plumbing here (device memory, streams, autograd glue).  Every op requires contiguous
 fp32 tensors on a HIP device and raises otherwise: there is no CPU path in the product.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -322,6 +324,56 @@ def batched_nms(boxes, scores, idxs, iou_threshold):
         check(lib.frcnn_nms_classed(_ptr(sboxes), _ptr(scls), None, n, float(iou_threshold), n, _ptr(keep), None, _ptr(cnt), _ptr(ws), nb,
                                     _stream()), "nms_classed")
     return order[keep[:host_count(cnt)]]
+
+
+class Detections(collections.namedtuple("Detections", "boxes labels scores count class_counts prob n_rois")):
+    """Fixed-capacity device results of detect_postprocess: boxes [(C-1)P,4] f32, labels [(C-1)P] i32, scores [(C-1)P] f32, the first
+    count[0] rows valid (class-major, score order inside a class); class_counts [C-1] i32; prob [P,C] f32 or None; n_rois = the device
+    count of live RoI rows the call read (-1 = an aborted proposal scan upstream)."""
+    __slots__ = ()
+
+    def to_host(self):
+        """The one host sync: (bbox f32 [M,4], label i32 [M], score f32 [M]) on the CPU, exactly what FRCNN.predict returns.
+        Raises FrcnnError when the proposal stage reported an aborted scan (count = -1)."""
+        n = host_count(self.count, "detect_postprocess")
+        return self.boxes[:n].cpu(), self.labels[:n].cpu(), self.scores[:n].cpu()
+
+
+def detect_postprocess(head_cls, head_reg, rois, n_rois, threshold, nms_threshold=0.3, threshold_dev=None, want_prob=False):
+    """The post-processing half of FRCNN.predict (models/model.py:368-402, models/new_model.py:420-470) in three launches and no host
+    sync: softmax, per-class decode + clamp of all P rows, then per class the score mask `prob > threshold` and nms(nms_threshold),
+    concatenated class by class.  head_cls [P,C] logits, head_reg [P,4C] deltas (bf16 / fp16 outputs of an autocast head are cast to
+    fp32), rois [P,4] normalised xyxy, n_rois device int32[1] (rows >= n_rois are ignored).  threshold_dev: a device float32[1] that
+    overrides `threshold` when given -- read when the kernels run, so a captured graph honours a new value.  Returns Detections."""
+    def f32(t):
+        return t.float() if isinstance(t, torch.Tensor) and t.dtype in (torch.bfloat16, torch.float16) else t
+    head_cls = _req(f32(head_cls), name="head_cls")
+    head_reg = _req(f32(head_reg), name="head_reg")
+    rois = _req(rois, name="rois").reshape(-1, 4)
+    n_rois = _req(n_rois, torch.int32, "n_rois").reshape(-1)
+    if head_cls.dim() != 2:
+        raise ValueError("detect_postprocess: head_cls must be [P, C], got %s" % (tuple(head_cls.shape),))
+    P, C_ = head_cls.shape
+    head_reg = head_reg.reshape(P, -1)
+    if head_reg.shape[1] != 4 * C_ or rois.shape[0] != P or n_rois.numel() < 1:
+        raise ValueError("detect_postprocess: shapes disagree: head_cls %s, head_reg %s, rois %s" % (tuple(head_cls.shape), tuple(head_reg.shape), tuple(rois.shape)))
+    if threshold_dev is not None:
+        threshold_dev = _req(threshold_dev, name="threshold_dev").reshape(-1)
+    dev = head_cls.device
+    cap = max((C_ - 1) * P, 1)
+    boxes = torch.empty((cap, 4), dtype=torch.float32, device=dev)
+    labels = torch.empty((cap,), dtype=torch.int32, device=dev)
+    scores = torch.empty((cap,), dtype=torch.float32, device=dev)
+    count = torch.empty((1,), dtype=torch.int32, device=dev)
+    class_counts = torch.empty((max(C_ - 1, 1),), dtype=torch.int32, device=dev)
+    prob = torch.empty((P, C_), dtype=torch.float32, device=dev) if want_prob else None
+    nb = _lib.workspace_bytes(_lib.OP_DETECT, P, C_)
+    ws = _workspace(dev, nb)
+    with torch.cuda.device(dev):
+        check(lib.frcnn_detect_postprocess(_ptr(head_cls), _ptr(head_reg), _ptr(rois), _ptr(n_rois), P, C_, float(threshold), _ptr(threshold_dev),
+                                           float(nms_threshold), _ptr(boxes), _ptr(labels), _ptr(scores), _ptr(count), _ptr(class_counts),
+                                           _ptr(prob), _ptr(ws), nb, _stream()), "detect_postprocess")
+    return Detections(boxes, labels, scores, count, class_counts, prob, n_rois)
 
 
 def region_proposal(reg, cls, anchors, min_size_norm, pre_nms_top_k, iou_threshold, post_nms_top_k, grid=None, want_src=False,

@@ -57,7 +57,8 @@ typedef enum {
     FRCNN_OP_HEAD_BWD = 7,        /* n1 = C (frcnn_rpn_head_tail_ml_bwd) */
     FRCNN_OP_RPN_CONV = 8,        /* frcnn_rpn_conv_head_fwd / frcnn_rpn_conv_bwd_data (packed bf16 weights) */
     FRCNN_OP_RPN_CONV_WGRAD = 9,  /* frcnn_rpn_conv_wgrad (per-split partial gradients) */
-    FRCNN_OP_RPN_CONV_F32 = 10    /* n1 = C: frcnn_rpn_conv3x3_f32_fwd / _bwd_data / _wgrad (ticket words, transposed weights, slabs) */
+    FRCNN_OP_RPN_CONV_F32 = 10,   /* n1 = C: frcnn_rpn_conv3x3_f32_fwd / _bwd_data / _wgrad (ticket words, transposed weights, slabs) */
+    FRCNN_OP_DETECT = 11          /* n1 = P RoI rows, n2 = C classes: frcnn_detect_postprocess (0 outside its limits) */
 } frcnn_op;
 
 /* FRCNN_ABI_VERSION, or FRCNN_ERR_UNSUPPORTED (message in frcnn_last_error) when the objects the library was linked from were compiled
@@ -407,6 +408,26 @@ int frcnn_detection_loss(const float *rpn_cls /*[N,2]*/, const float *rpn_reg /*
                          const float *t_reg /*[R,4]*/, int64_t R, int NC,
                          float *out7, float *g_rpn_cls, float *g_rpn_reg, float *g_head_cls, float *g_head_reg,
                          void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- detection post-process (models/model.py:368-402, models/new_model.py:420-470) ------------------------------ */
+/* The post-processing half of FRCNN.predict in three launches and no host sync (graph-capturable): for every live row
+ * r < *n_rois_dev, prob[r] = softmax(head_cls[r]) (fp32) and, for every class c in 1 .. C-1,
+ *   box = clamp01(cxcy_to_xy(decode(head_reg[r,c] * (0.1, 0.1, 0.2, 0.2), xy_to_cxcy(rois[r]))))   (bit-identical to frcnn_box_codec);
+ * then _suppress: per class the candidates prob[r,c] > thr (strict, fp32; thr = *threshold_dev when given, else threshold),
+ * greedy NMS in descending score (ties: ascending r) with frcnn_nms_classed's IoU decision (> nms_threshold, strict), and the
+ * CLASS-MAJOR concatenation: class 1 first, score order inside a class, labels c - 1.  *out_count = the total (<= (C-1)*P);
+ * out_class_counts[c-1] (optional) the per-class counts.  Rows >= *n_rois_dev are never detections (they may hold NaN).
+ * *n_rois_dev < 0 (an aborted proposal scan upstream) gives *out_count = -1.  out_prob (optional) receives the softmax.
+ * Limits: 1 <= P <= 2048, 2 <= C <= 256 (FRCNN_ERR_UNSUPPORTED otherwise).  out_boxes 16-byte aligned.
+ * workspace: frcnn_workspace_bytes(FRCNN_OP_DETECT, P, C) bytes, any content.                                        */
+int frcnn_detect_postprocess(const float *head_cls /*[P,C] logits*/, const float *head_reg /*[P,4C] raw deltas*/,
+                             const float *rois /*[P,4] normalised xyxy*/, const int32_t *n_rois_dev /*live rows, <= P*/,
+                             int64_t P, int C, float threshold, const float *threshold_dev /*device float or NULL*/,
+                             float nms_threshold,
+                             float *out_boxes /*[(C-1)*P,4]*/, int32_t *out_labels /*[(C-1)*P]*/, float *out_scores /*[(C-1)*P]*/,
+                             int32_t *out_count /*[1]*/, int32_t *out_class_counts /*[C-1] or NULL*/,
+                             float *out_prob /*[P,C] or NULL*/,
+                             void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- input stage in front of the path ------------------------------------------------------
  * One uint8 HWC RGB frame in HBM -> [hflip] -> PIL-bilinear resize to (oh, ow) -> /255 -> (x - mean) / std -> float CHW

@@ -1,0 +1,126 @@
+"""Inference throughput of one frame at a time (the reference's test.py:60 loop): FRCNN.predict eager, FRCNN.detect eager and
+inference.DetectGraph replays, every result brought to the host; and the GPU time of the post-process alone, the op chain behind
+predict (softmax ... decode ... batched_nms, with its host syncs) against ops.detect_postprocess, from HIP events.
+
+    python tools/infer_bench.py --config vgg|fpn [--amp bf16] [--steps N] [--warmup W] [--only detect]
+
+Synthetic frames (600x1000 for VGG16, 800x1344 for ResNet-50-FPN), head weights spread as tests/test_gpu_detect.py spreads them (a
+random-init head gives near-constant scores).  Prints one JSON line.  --only detect runs the eager detect loop alone (for a
+kernel trace)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+from faster_rcnn_pytorch_amd import ops  # noqa: E402
+from faster_rcnn_pytorch_amd.inference import DetectGraph  # noqa: E402
+
+THRESHOLD = 0.05
+
+
+def build(config, dev):
+    torch.manual_seed(0)
+    if config == "vgg":
+        from faster_rcnn_pytorch_amd.model import FRCNN
+        m = FRCNN(num_classes=21, sampling="host").to(dev)
+        rpn_cls, rpn_reg, head, seed, hw = m.rpn.cls_layer, m.rpn.reg_layer, m.fast_rcnn_head, 5, (600, 1000)
+        rpn_scale = (30, 10)
+    else:
+        from faster_rcnn_pytorch_amd.new_model import FRCNN
+        m = FRCNN(num_classes=91, sampling="host").to(dev)
+        rpn_cls, rpn_reg, head, seed, hw = m.rpn.rpn_head.cls_layer, m.rpn.rpn_head.reg_layer, m.frcnn_head, 6, (800, 1344)
+        rpn_scale = (30, 2)
+    g = torch.Generator().manual_seed(seed)
+    with torch.no_grad():
+        rpn_cls.weight.mul_(rpn_scale[0])
+        rpn_reg.weight.mul_(rpn_scale[1])
+        head.cls_head.weight.copy_(torch.randn(head.cls_head.weight.shape, generator=g) * 0.8)
+        head.reg_head.weight.copy_(torch.randn(head.reg_head.weight.shape, generator=g) * 0.5)
+    return m.eval(), head, hw
+
+
+def old_chain(m, rois, n, hc, hr, thr):
+    """The post-processing lines of FRCNN.predict (model.py / new_model.py), on the head outputs of n live rows."""
+    rois = rois[:n]
+    pred_cls = torch.softmax(hc, dim=-1)
+    reg = hr.reshape(-1, m.num_classes, 4) * ops.const_tensor((0.1, 0.1, 0.2, 0.2), hc.device)
+    r = rois.reshape(-1, 1, 4).expand_as(reg)
+    box = ops.cxcy_to_xy(ops.decode(reg.reshape(-1, 4).contiguous(), ops.xy_to_cxcy(r.reshape(-1, 4).contiguous())))
+    box = box.reshape(-1, m.num_classes * 4).clamp(min=0, max=1)
+    return m._suppress(box, pred_cls, thr)
+
+
+def rate(fn, steps, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        fn()
+    torch.cuda.synchronize()
+    return steps / (time.perf_counter() - t0)
+
+
+def event_ms(fn, reps):
+    out = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        out.append(a.elapsed_time(b))
+    return float(np.median(out))
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--config", choices=("vgg", "fpn"), default="vgg")
+    ap.add_argument("--amp", choices=("none", "bf16"), default="none")
+    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--only", choices=("all", "detect"), default="all")
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    m, head, (H, W) = build(a.config, dev)
+    x = torch.randn(1, 3, H, W, generator=torch.Generator().manual_seed(21)).to(dev)
+    amp = torch.autocast("cuda", dtype=torch.bfloat16, cache_enabled=False) if a.amp == "bf16" else torch.autocast("cuda", enabled=False)
+    res = {"config": a.config, "amp": a.amp, "image_hw": [H, W], "threshold": THRESHOLD, "steps": a.steps,
+           "device": torch.cuda.get_device_name(0)}
+    with amp:
+        if a.only == "detect":
+            res["images_per_s"] = {"detect_eager": rate(lambda: m.detect(x, THRESHOLD).to_host(), a.steps, a.warmup)}
+            print(json.dumps(res))
+            return
+        ips = {"predict_eager": rate(lambda: m.predict(x, THRESHOLD), a.steps, a.warmup),
+               "detect_eager": rate(lambda: m.detect(x, THRESHOLD).to_host(), a.steps, a.warmup)}
+        dg = DetectGraph(m, (H, W), threshold=THRESHOLD)
+        ips["detect_graph"] = rate(lambda: dg(x).to_host(), a.steps, a.warmup)
+        res["images_per_s"] = ips
+        # the post-process alone, on the head outputs of one detect call
+        cap = {}
+        h = head.register_forward_hook(lambda mod, i, o: cap.__setitem__("head", (i[1], o[0].detach(), o[1].detach())))
+        det = m.detect(x, THRESHOLD, want_prob=True)
+        h.remove()
+        rois, hc, hr = cap["head"]
+        n = int(det.n_rois.item())
+        hcn, hrn = hc[:n].float().contiguous(), hr[:n].float().contiguous()
+        res["postprocess_ms"] = {"old_chain_softmax_to_nms_classed": event_ms(lambda: old_chain(m, rois, n, hcn, hrn, THRESHOLD), a.steps),
+                                 "fused_detect_postprocess": event_ms(lambda: ops.detect_postprocess(hc, hr, rois, det.n_rois, THRESHOLD), a.steps)}
+        prob = det.prob[:n, 1:]
+        res["rois_per_image"] = n
+        res["candidates_per_image"] = int((prob > THRESHOLD).sum().item())
+        res["detections_per_image"] = int(det.count.item())
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
