@@ -16,7 +16,7 @@
 //   One workgroup barrier per (chunk, kernel row) step = 48 MFMAs per wave; both LDS buffers are double-buffered and filled from
 //   registers that were loaded one step (weights) / one chunk (pixels) ahead.
 // Epilogue on the accumulators (C/D layout: lane = position, registers = 16 channels): round to bf16 = raw (stored as 64-byte row
-//   segments), add b3, ReLU, round to bf16 -- and those registers ARE the B operand of the second product (D2[j][n] += Wh[j][c] h[c][n]):
+//   segments), add b3 to that ROUNDED value (fp32), ReLU (a NaN stays a NaN), round to bf16 -- and those registers ARE the B operand of the second product (D2[j][n] += Wh[j][c] h[c][n]):
 //   for a 32-channel tile the lane's registers 8 s .. 8 s + 7 hold channels 16 s + {0..3, 8..11} (+4 for the upper half-wave), which
 //   is a permutation of a K = 16 slice; the head weights are pre-packed with the same permutation.  The two channel halves are
 //   added through LDS, the biases are added and cls / reg are written.
@@ -468,7 +468,7 @@ __device__ __forceinline__ void rpn_conv3x3_head_tile(int lvl, int tile, int ysu
                 }
                 const float2 bias = *(const float2 *)(s_b3 + c);
                 const float z0 = __uint_as_float(own << 16) + bias.x, z1 = __uint_as_float(own & 0xFFFF0000u) + bias.y;
-                hb.u[k] = cvt_pk_bf16(z0 > 0.0f ? z0 : 0.0f, z1 > 0.0f ? z1 : 0.0f);
+                hb.u[k] = cvt_pk_bf16(z0 <= 0.0f ? 0.0f : z0, z1 <= 0.0f ? 0.0f : z1);     // (not z > 0 ? z : 0: a NaN must stay a NaN, as through torch.relu)
             }
 #pragma unroll
             for (int s = 0; s < 2; ++s) {

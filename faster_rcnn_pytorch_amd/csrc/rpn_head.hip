@@ -91,7 +91,7 @@ __global__ __launch_bounds__(64 * WAVES) void rpn_head_tail_kernel(HeadLevels L,
             }
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
-                const float h = a[u] > 0.0f ? a[u] : 0.0f;    // ReLU of the 3x3 output (bias already added)
+                const float h = a[u] <= 0.0f ? 0.0f : a[u];   // ReLU of the 3x3 output (bias already added); a NaN stays a NaN, as through torch.relu
 #pragma unroll
                 for (int t = 0; t < NT; ++t) {
                     const float4 q = bw[t][u >> 2];
@@ -117,7 +117,7 @@ __global__ __launch_bounds__(64 * WAVES) void rpn_head_tail_kernel(HeadLevels L,
                 bv[t][4] = to_bf16_rne(q1.x); bv[t][5] = to_bf16_rne(q1.y); bv[t][6] = to_bf16_rne(q1.z); bv[t][7] = to_bf16_rne(q1.w);
             }
 #pragma unroll
-            for (int u = 0; u < 8; ++u) av[u] = to_bf16_rne(a[u] > 0.0f ? a[u] : 0.0f);
+            for (int u = 0; u < 8; ++u) av[u] = to_bf16_rne(a[u] <= 0.0f ? 0.0f : a[u]);      // (NaN-keeping ReLU)
 #pragma unroll
             for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv[t], acc[t], 0, 0, 0);
         }

@@ -378,3 +378,142 @@ def test_resnet50_fpn_800x1344_same_weights_features_rpn_outputs_and_gradients_v
     assert rec["grad_rel_device_decisions_dev_vs_cpu_max"] < TOL, sorted(rec["grad_rel_device_decisions_dev_vs_cpu"].items(), key=lambda kv: -kv[1])[:5]
     assert n_flip < 1e-4 * n_dec and pop.worst < 1e-4
     assert rec["grad_rel_own_decisions_dev_vs_cpu_max"] < 5e-2
+
+
+# ------------------------------------------------------------------------------------------ the bf16 mixed-precision configuration (BASELINE configs[4])
+LIB_ROUTES = ("conv3x3", "conv3x3_fwd", "conv3x3_bf16_c256", "conv3x3_c3", "conv1x1", "gemm_nt", "affine_act", "affine_act_mixed", "rpn_conv3x3",
+              "rpn_conv_head_levels", "rpn_head_tail_levels", "rpn_head_tail", "rpn_conv_bwd_data", "rpn_conv_wgrad")
+
+
+def _fpn_group(name):
+    for prefix, grp in (("backbone.body.", "backbone"), ("backbone.fpn.inner_blocks.", "fpn_inner"), ("backbone.fpn.layer_blocks.", "fpn_layer"), ("rpn_head.", "rpn_head")):
+        if name.startswith(prefix):
+            return grp
+    raise KeyError(name)
+
+
+def test_resnet50_fpn_800x1344_bf16_same_weights_library_vs_torch_autocast_vs_float64(monkeypatch):
+    """ONE state_dict, one 800 x 1344 frame, backbone + FPN + RPN head three times:
+      L  the library path under bf16 autocast (spies assert the routes: conv3x3_bf16_c256 twice -- P2, P3 --, rpn_conv_head_levels once, all 16
+         bottlenecks through _forward_mixed = 53 affine_act_mixed calls with the stem and the four downsample norms);
+      T  the SAME module object under the same autocast with every library route off (all ops.*_supported -> False, fused_bf16_conv = False, the
+         head as conv2d / relu per level, and F.interpolate fed fp32 as autocast itself would feed it, so that the top-down sum is autocast's fp32
+         one): the plain torch modules under autocast.  Spies assert that no ops. convolution / norm / head call runs;
+      F  float64 on the CPU, own decisions.
+    Every bound is a multiple of T's OWN distance to F, never of L's: dist(L, F) <= 2 x dist(T, F) for the five maps, the RPN softmax scores
+    (absolute) and regressions (rel()).  L and T are the same chain of ~55 bf16-rounded layers; L adds three roundings in the top-down sum, the
+    output convolutions' bias after the rounding, and does NOT round the frozen norms' scale / shift: each at most one bf16 ulp where T has
+    accumulated many, while a wrong kernel moves a tensor by O(1) of its scale.  Backward of the probe loss sum(cls G1) + sum(reg G2) (fixed
+    seeded G, no proposals or targets) in all three: per parameter group (backbone, FPN inner, FPN layer, RPN head), on the groups' maxima,
+    rel(gL, gF) <= 2 x rel(gT, gF) + 1e-4 -- ReLU decisions differ between any two bf16 runs, hence per group and against T's own distance.
+    All maxima are written through _report as same_weights_fpn_bf16.json (profiles/same_weights_fpn_bf16.json is a run's copy, quoted in docs/PARITY.md)."""
+    import time
+    from faster_rcnn_pytorch_amd import new_model, ops
+    from faster_rcnn_pytorch_amd.new_model import BackboneWithFPN, Bottleneck, FRCNN
+    H, W = 800, 1344
+    torch.manual_seed(0)
+    m = FRCNN(num_classes=91, sampling="host").to(DEV)
+    with torch.no_grad():
+        m.rpn.rpn_head.cls_layer.weight.mul_(30)
+    bb, head = m.backbone, m.rpn.rpn_head
+    x = synth(5, H, W, 3, 1, 91)[0]
+    gg = torch.Generator().manual_seed(77)
+    P = sum(h * w for h, w in [(200, 336), (100, 168), (50, 84), (25, 42), (13, 21)])
+    G1, G2 = torch.randn(1, P * 3, 2, generator=gg), torch.randn(1, P * 3, 4, generator=gg)
+    m.train()
+    t0 = time.time()
+
+    def run(fused):
+        m.zero_grad(set_to_none=True)
+        with torch.autocast("cuda", dtype=torch.bfloat16):
+            feats = list(bb(x.to(DEV)).values())
+            if fused:
+                cls, reg = head.forward_levels(feats)
+            else:
+                cr = [head(f) for f in feats]
+                cls, reg = torch.cat([c for c, _ in cr], 1), torch.cat([r for _, r in cr], 1)
+        ((cls.float() * G1.to(DEV)).sum() + (reg.float() * G2.to(DEV)).sum()).backward()
+        named = [("backbone." + n, p) for n, p in bb.named_parameters()] + [("rpn_head." + n, p) for n, p in head.named_parameters()]
+        return [f.detach().float().cpu() for f in feats], cls.detach().float().cpu(), reg.detach().float().cpu(), {n: g.cpu() for n, g in _grads(named).items()}, (cls.dtype, reg.dtype)
+
+    # ---- L: the library path, routes counted
+    calls = {k: 0 for k in LIB_ROUTES + ("_forward_mixed",)}
+
+    def counted(name, fn):
+        def w(*a, **k):
+            calls[name] += 1
+            return fn(*a, **k)
+        return w
+    for name in LIB_ROUTES:
+        monkeypatch.setattr(ops, name, counted(name, getattr(ops, name)))
+    monkeypatch.setattr(Bottleneck, "_forward_mixed", counted("_forward_mixed", Bottleneck._forward_mixed))
+    fL, cL, rL, gL, dtL = run(True)
+    monkeypatch.undo()
+    assert calls["conv3x3_bf16_c256"] == 2 and calls["rpn_conv_head_levels"] == 1 and calls["_forward_mixed"] == 16 and calls["affine_act_mixed"] == 1 + 16 * 3 + 4, calls
+    assert calls["conv3x3"] == 0 and calls["affine_act"] == 0 and calls["rpn_head_tail_levels"] == 0 and dtL == (torch.float32, torch.float32), calls
+    print("\n[same-weights fpn_bf16] L done %.0f s" % (time.time() - t0), flush=True)
+
+    # ---- T: the plain torch modules under autocast, same object, same weights
+    calls_t = {k: 0 for k in LIB_ROUTES}
+    for name in LIB_ROUTES:
+        fn = getattr(ops, name)
+        monkeypatch.setattr(ops, name, (lambda n, f: (lambda *a, **k: (calls_t.__setitem__(n, calls_t[n] + 1), f(*a, **k))[1]))(name, fn))
+    for name in dir(ops):
+        if name.endswith("_supported"):
+            monkeypatch.setattr(ops, name, lambda *a, **k: False)
+    monkeypatch.setattr(head, "fused_bf16_conv", False)
+    interp = new_model.F.interpolate
+    monkeypatch.setattr(new_model.F, "interpolate", lambda t, *a, **k: interp(t.float(), *a, **k))     # autocast's own treatment of interpolate: fp32
+    fT, cT, rT, gT, _ = run(False)
+    monkeypatch.undo()
+    assert sum(calls_t.values()) == 0, calls_t
+    print("[same-weights fpn_bf16] T done %.0f s" % (time.time() - t0), flush=True)
+
+    # ---- F: float64 on the CPU, forward and backward
+    _threads()
+    ref = model_ref.RefFRCNNFPN(BackboneWithFPN(trainable_layers=3), 91)
+    cpu = lambda sd: {k: v.detach().cpu() for k, v in sd.items()}                  # noqa: E731
+    ref.backbone.load_state_dict(cpu(bb.state_dict()))
+    ref.rpn_head.load_state_dict(cpu(head.state_dict()))
+    ref64 = copy.deepcopy(ref).double()
+    del ref
+    f64 = list(ref64.backbone(x.double()).values())
+    c64, r64 = [], []
+    for f in f64:
+        h = torch.relu(ref64.rpn_head.inter_layer(f))
+        c64.append(ref64.rpn_head.cls_layer(h).permute(0, 2, 3, 1).reshape(1, -1, 2))
+        r64.append(ref64.rpn_head.reg_layer(h).permute(0, 2, 3, 1).reshape(1, -1, 4))
+    cls64, reg64 = torch.cat(c64, 1), torch.cat(r64, 1)
+    print("[same-weights fpn_bf16] F forward done %.0f s" % (time.time() - t0), flush=True)
+    ((cls64 * G1.double()).sum() + (reg64 * G2.double()).sum()).backward()
+    gF = _grads([("backbone." + n, p) for n, p in ref64.backbone.named_parameters()] + [("rpn_head." + n, p) for n, p in ref64.rpn_head.named_parameters()])
+    f64 = [f.detach() for f in f64]
+    print("[same-weights fpn_bf16] F backward done %.0f s" % (time.time() - t0), flush=True)
+
+    sm = lambda t: torch.softmax(t.detach().double().cpu(), dim=-1)          # noqa: E731
+    levels = ["P2", "P3", "P4", "P5", "P6"]
+    rec = {"frame": "%dx%d seed 5, probe loss sum(cls G1) + sum(reg G2), G seed 77" % (H, W), "float64_backward": True, "routes_L": calls,
+           "features_rel_L_vs_F": {n: rel(a, b) for n, a, b in zip(levels, fL, f64)}, "features_rel_T_vs_F": {n: rel(a, b) for n, a, b in zip(levels, fT, f64)},
+           "features_rel_L_vs_T": {n: rel(a, b) for n, a, b in zip(levels, fL, fT)},
+           "rpn_score_abs_L_vs_F": float((sm(cL) - sm(cls64)).abs().max()), "rpn_score_abs_T_vs_F": float((sm(cT) - sm(cls64)).abs().max()),
+           "rpn_score_abs_L_vs_T": float((sm(cL) - sm(cT)).abs().max()),
+           "rpn_reg_rel_L_vs_F": rel(rL, reg64), "rpn_reg_rel_T_vs_F": rel(rT, reg64), "rpn_reg_rel_L_vs_T": rel(rL, rT),
+           "grad_rel_L_vs_F": {n: rel(gL[n], gF[n]) for n in gF}, "grad_rel_T_vs_F": {n: rel(gT[n], gF[n]) for n in gF}, "grad_rel_L_vs_T": {n: rel(gL[n], gT[n]) for n in gF}}
+    for k in ("grad_rel_L_vs_F", "grad_rel_T_vs_F", "grad_rel_L_vs_T"):
+        grp = {}
+        for n, v in rec[k].items():
+            grp[_fpn_group(n)] = max(grp.get(_fpn_group(n), 0.0), v)
+        rec[k + "_group_max"] = grp
+    rec["seconds"] = time.time() - t0
+    _report("fpn_bf16", rec)
+    print("[same-weights fpn_bf16] " + json.dumps({k: v for k, v in rec.items() if k.startswith(("features", "rpn_")) or k.endswith("group_max")}), flush=True)
+    assert set(gL) == set(gT) == set(gF) and len(gF) > 60
+    for n in gF:
+        for g in (gL[n], gT[n]):
+            assert g.dtype == torch.float32 and bool(torch.isfinite(g).all()) and float(g.abs().sum()) > 0, n
+    for n in levels:
+        assert rec["features_rel_L_vs_F"][n] <= 2 * rec["features_rel_T_vs_F"][n], (n, rec["features_rel_L_vs_F"][n], rec["features_rel_T_vs_F"][n])
+    assert rec["rpn_score_abs_L_vs_F"] <= 2 * rec["rpn_score_abs_T_vs_F"], (rec["rpn_score_abs_L_vs_F"], rec["rpn_score_abs_T_vs_F"])
+    assert rec["rpn_reg_rel_L_vs_F"] <= 2 * rec["rpn_reg_rel_T_vs_F"], (rec["rpn_reg_rel_L_vs_F"], rec["rpn_reg_rel_T_vs_F"])
+    for grp, v in rec["grad_rel_L_vs_F_group_max"].items():
+        assert v <= 2 * rec["grad_rel_T_vs_F_group_max"][grp] + 1e-4, (grp, v, rec["grad_rel_T_vs_F_group_max"][grp])
