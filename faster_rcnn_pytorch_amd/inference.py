@@ -10,13 +10,21 @@ class DetectGraph(object):
 
     __call__(x) copies x into the graph's static input buffer, replays, and returns the graph's static ops.Detections: its tensors are
     overwritten by the next call (clone them, or call .to_host(), to keep a result).  The score threshold lives in a device tensor
-    that the kernels read at replay time, so set_threshold() takes effect on the next call without a new capture."""
+    that the kernels read at replay time, so set_threshold() takes effect on the next call without a new capture.
 
-    def __init__(self, model, image_hw, threshold=0.05, device=None, warmup=2):
+    evaluator= (an evaluation.DetectionEvaluator) and gt= (an evaluation.GroundTruth) add the evaluator's per-frame update to the same
+    graph: the reference's test loop (test.py:60: predict, then the evaluator) as one replay per frame with no host sync.  Write the
+    frame's ground truth with gt.set(...) before the call (the warm-up and the capture score nothing).  Without them the captured
+    graph is detect alone."""
+
+    def __init__(self, model, image_hw, threshold=0.05, device=None, warmup=2, evaluator=None, gt=None):
         m = getattr(model, "module", model)                     # a DDP-wrapped model: capture the module itself
         dev = torch.device(device) if device is not None else next(m.parameters()).device
         H, W = (int(v) for v in image_hw)
+        if (evaluator is None) != (gt is None):
+            raise ValueError("DetectGraph: evaluator= and gt= go together")
         self.model = m
+        self.evaluator, self.gt = evaluator, gt
         self.image_hw = (H, W)
         self.x = torch.zeros((1, 3, H, W), dtype=torch.float32, device=dev)
         self.threshold = torch.full((1,), float(threshold), dtype=torch.float32, device=dev)
@@ -25,11 +33,15 @@ class DetectGraph(object):
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
             for _ in range(max(int(warmup), 1)):
-                m.detect(self.x, float(threshold), threshold_dev=self.threshold)
+                out = m.detect(self.x, float(threshold), threshold_dev=self.threshold)
+            if evaluator is not None:
+                evaluator._workspace(out.labels.numel(), gt.capacity)         # the update's zeroed workspace: allocated outside the capture
         torch.cuda.current_stream(dev).wait_stream(side)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             self.out = m.detect(self.x, float(threshold), threshold_dev=self.threshold)
+            if evaluator is not None:
+                evaluator.update(self.out, gt)
 
     def set_threshold(self, t):
         """Writes the device threshold in place: the next replay uses it."""

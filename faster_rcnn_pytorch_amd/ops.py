@@ -9,6 +9,7 @@ Mirrors (file:line under the reference):
   torchvision.ops.MultiScaleRoIAlign   as called at models/new_model.py:127,143
   torchvision AnchorGenerator    as called at models/new_model.py:23-25,46
   FRCNN.predict post-processing  models/model.py:368-402, models/new_model.py:420-470 (detect_postprocess)
+  VOC AP evaluator               evaluation/voc_eval.py:67-225 (eval_update, eval_average_precision)
 
 PyTorch is plumbing here (device memory, streams, autograd glue).  Every op requires contiguous
 fp32 tensors on a HIP device and raises otherwise: there is no CPU path in the product.
@@ -374,6 +375,71 @@ def detect_postprocess(head_cls, head_reg, rois, n_rois, threshold, nms_threshol
                                            float(nms_threshold), _ptr(boxes), _ptr(labels), _ptr(scores), _ptr(count), _ptr(class_counts),
                                            _ptr(prob), _ptr(ws), nb, _stream()), "detect_postprocess")
     return Detections(boxes, labels, scores, count, class_counts, prob, n_rois)
+
+
+def eval_update(dets, gt_boxes, gt_labels, gt_difficult, n_gt, frame, thresholds, num_classes, npos, rec_score, rec_label, rec_image,
+                rec_position, rec_flags, cursor, error_word, workspace=None):
+    """One frame of the VOC AP protocol (evaluation/voc_eval.py:84-91, 46-56, 156-197) in one launch and no host sync: matches the live
+    rows of `dets` (an ops.Detections) against the frame's ground truth, adds the non-difficult ground truths to npos, reserves
+    dets.count slots of the record store with one atomic add on `cursor` and writes the records.  gt_boxes [G,4] f32 pixel xyxy,
+    gt_labels [G] i32 (the detections' 0-based label space), gt_difficult [G] u8, n_gt i32[1], frame i32[3] = (w, h, image_id),
+    thresholds f64[T]: all on the device and read when the kernel runs, so a captured graph sees new values at replay.  The record
+    store: rec_score f32, rec_label / rec_image / rec_position i32, rec_flags i32 (bit pattern: 2 bits per threshold, _lib.EVAL_TP /
+    EVAL_FP / EVAL_IGNORED), all [record_capacity]; cursor i64[1]; error_word i32[1] (_lib.EVAL_ERR_*); npos i64[C-1].  See
+    include/frcnn_hip.h.  faster_rcnn_pytorch_amd.evaluation.DetectionEvaluator owns these buffers."""
+    boxes = _req(dets.boxes, name="dets.boxes")
+    labels = _req(dets.labels, torch.int32, "dets.labels")
+    scores = _req(dets.scores, name="dets.scores")
+    count = _req(dets.count, torch.int32, "dets.count")
+    gt_boxes = _req(gt_boxes, name="gt_boxes")
+    gt_labels = _req(gt_labels, torch.int32, "gt_labels")
+    gt_difficult = _req(gt_difficult, torch.uint8, "gt_difficult")
+    n_gt = _req(n_gt, torch.int32, "n_gt")
+    frame = _req(frame, torch.int32, "frame")
+    thresholds = _req(thresholds, torch.float64, "thresholds")
+    npos = _req(npos, torch.int64, "npos")
+    cursor = _req(cursor, torch.int64, "cursor")
+    error_word = _req(error_word, torch.int32, "error_word")
+    recs = (_req(rec_score, name="rec_score"), _req(rec_label, torch.int32, "rec_label"), _req(rec_image, torch.int32, "rec_image"),
+            _req(rec_position, torch.int32, "rec_position"), _req(rec_flags, torch.int32, "rec_flags"))
+    D, G, T, cap = labels.numel(), gt_labels.numel(), thresholds.numel(), rec_score.numel()
+    if boxes.numel() != 4 * D or scores.numel() != D or gt_boxes.numel() != 4 * G or gt_difficult.numel() != G or frame.numel() != 3 \
+            or npos.numel() != num_classes - 1 or any(r.numel() != cap for r in recs) or count.numel() < 1 or n_gt.numel() < 1:
+        raise ValueError("eval_update: shapes disagree")
+    for t in (dets.boxes, dets.labels, dets.scores, dets.count, npos, cursor, error_word, rec_score, rec_label, rec_image, rec_position, rec_flags):
+        if not t.is_contiguous():
+            raise ValueError("eval_update: the detections and the evaluator's buffers must be contiguous (they are written or read in place)")
+    dev = boxes.device
+    nb = _lib.workspace_bytes(_lib.OP_EVAL, D, G)
+    ws = workspace if workspace is not None else _ctrl_workspace(dev, "eval", max(nb, 1))
+    with torch.cuda.device(dev):
+        check(lib.frcnn_eval_update(_ptr(boxes), _ptr(labels), _ptr(scores), _ptr(count), D, _ptr(gt_boxes), _ptr(gt_labels), _ptr(gt_difficult),
+                                    _ptr(n_gt), G, _ptr(frame), _ptr(thresholds), T, int(num_classes), _ptr(npos), _ptr(recs[0]), _ptr(recs[1]),
+                                    _ptr(recs[2]), _ptr(recs[3]), _ptr(recs[4]), cap, _ptr(cursor), _ptr(error_word), _ptr(ws), ws.numel(),
+                                    _stream()), "eval_update")
+
+
+def eval_average_precision(labels_sorted, flags_sorted, n_records, npos, n_thresholds, num_classes):
+    """voc_ap of every class at every threshold (evaluation/voc_eval.py:199-219, 115-135) over records in the order (label ascending,
+    score descending, image_id ascending, position ascending), the first min(n_records, capacity) live (n_records: device i64[1]).
+    Returns (ap f64 [T, C-1] -- NaN where npos == 0 --, tp_total i64 [T, C-1], fp_total i64 [T, C-1]) on the device."""
+    labels_sorted = _req(labels_sorted, torch.int32, "labels_sorted")
+    flags_sorted = _req(flags_sorted, torch.int32, "flags_sorted")
+    n_records = _req(n_records, torch.int64, "n_records")
+    npos = _req(npos, torch.int64, "npos")
+    cap, T, nc = labels_sorted.numel(), int(n_thresholds), int(num_classes) - 1
+    if flags_sorted.numel() != cap or npos.numel() != nc or n_records.numel() < 1:
+        raise ValueError("eval_average_precision: shapes disagree")
+    dev = labels_sorted.device
+    ap = torch.empty((max(T, 1), max(nc, 1)), dtype=torch.float64, device=dev)
+    tp = torch.empty((max(T, 1), max(nc, 1)), dtype=torch.int64, device=dev)
+    fp = torch.empty((max(T, 1), max(nc, 1)), dtype=torch.int64, device=dev)
+    nb = 256 + 8 * cap
+    ws = _workspace(dev, nb)
+    with torch.cuda.device(dev):
+        check(lib.frcnn_eval_average_precision(_ptr(labels_sorted), _ptr(flags_sorted), _ptr(n_records), cap, _ptr(npos), T, int(num_classes),
+                                               _ptr(ap), _ptr(tp), _ptr(fp), _ptr(ws), nb, _stream()), "eval_average_precision")
+    return ap, tp, fp
 
 
 def region_proposal(reg, cls, anchors, min_size_norm, pre_nms_top_k, iou_threshold, post_nms_top_k, grid=None, want_src=False,

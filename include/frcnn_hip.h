@@ -58,7 +58,8 @@ typedef enum {
     FRCNN_OP_RPN_CONV = 8,        /* frcnn_rpn_conv_head_fwd / frcnn_rpn_conv_bwd_data (packed bf16 weights) */
     FRCNN_OP_RPN_CONV_WGRAD = 9,  /* frcnn_rpn_conv_wgrad (per-split partial gradients) */
     FRCNN_OP_RPN_CONV_F32 = 10,   /* n1 = C: frcnn_rpn_conv3x3_f32_fwd / _bwd_data / _wgrad (ticket words, transposed weights, slabs) */
-    FRCNN_OP_DETECT = 11          /* n1 = P RoI rows, n2 = C classes: frcnn_detect_postprocess (0 outside its limits) */
+    FRCNN_OP_DETECT = 11,         /* n1 = P RoI rows, n2 = C classes: frcnn_detect_postprocess (0 outside its limits) */
+    FRCNN_OP_EVAL = 12            /* n1 = detection capacity, n2 = ground-truth capacity: frcnn_eval_update (0 outside its limits) */
 } frcnn_op;
 
 /* FRCNN_ABI_VERSION, or FRCNN_ERR_UNSUPPORTED (message in frcnn_last_error) when the objects the library was linked from were compiled
@@ -428,6 +429,45 @@ int frcnn_detect_postprocess(const float *head_cls /*[P,C] logits*/, const float
                              int32_t *out_count /*[1]*/, int32_t *out_class_counts /*[C-1] or NULL*/,
                              float *out_prob /*[P,C] or NULL*/,
                              void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- detection evaluator: the VOC AP protocol (evaluation/voc_eval.py:67-112,115-135,138-225) ------------------------ */
+/* Flags of a record: 2 bits per threshold t (bits 2t, 2t+1). */
+#define FRCNN_EVAL_TP 1u
+#define FRCNN_EVAL_FP 2u
+#define FRCNN_EVAL_IGNORED 3u      /* the best match is a difficult ground truth at >= t: neither (voc_eval.py:185) */
+/* One frame in one launch and no host sync (graph-capturable): replaces save_pred's pixel boxes (voc_eval.py:84-91), save_gt's
+ * gt_counter_per_class (:46-56) and cal_mAP's match and decision (:156-197) for the detections of one image.
+ *   boxes / labels / scores / count_dev: the tensors of frcnn_detect_postprocess (normalised fp32 xyxy, 0-based labels, *count_dev live
+ *   rows of det_capacity); gt_boxes fp32 pixel xyxy, gt_labels in the same label space, gt_difficult 0 / 1, *n_gt_dev live rows of
+ *   gt_capacity; frame_dev = (original width, original height, image_id); thresholds_dev = T IoU thresholds (float64).  Everything
+ *   that varies per frame is read on the device when the kernel runs.
+ * Pixel box = double(box) * double(w or h); the match is the same-class ground truth of the largest float64 overlap with the
+ * devkit's +1 convention, first wins ties, used and difficult ones included; at threshold t a detection whose overlap is >= t is
+ * IGNORED when the match is difficult, TP when it is the first of the frame's detections (score descending, position ascending) that
+ * share the match and reach t, FP otherwise; a detection below t or without a same-class ground truth is FP.
+ * Effects: npos[l] += 1 for every non-difficult ground truth; *cursor += count (ONE atomic add; slots past record_capacity are counted,
+ * not written); records (score, label, image_id, position, flags) in the reserved slots, in any order -- the defined order of the set
+ * is (score descending, image_id ascending, position ascending).  *error_word |= 1 when *count_dev < 0 (an aborted proposal scan
+ * upstream), 2 when *n_gt_dev > gt_capacity, 4 when *count_dev > det_capacity, 8 for a label outside 0 .. C-2; a frame with bit 1, 2
+ * or 4 is not recorded.
+ * Limits (FRCNN_ERR_UNSUPPORTED otherwise): 2 <= C <= 256, 1 <= det_capacity <= (C-1) * 2048, 1 <= gt_capacity <= 1024, 1 <= T <= 16.
+ * boxes and gt_boxes 16-byte aligned.  workspace: frcnn_workspace_bytes(FRCNN_OP_EVAL, det_capacity, gt_capacity) bytes, DEDICATED to
+ * this entry point and ZERO before the first call (a ticket and the per-ground-truth winner words; the kernel leaves them zero). */
+int frcnn_eval_update(const float *boxes /*[D,4]*/, const int32_t *labels /*[D]*/, const float *scores /*[D]*/, const int32_t *count_dev,
+                      int64_t det_capacity, const float *gt_boxes /*[G,4] pixels*/, const int32_t *gt_labels /*[G]*/,
+                      const uint8_t *gt_difficult /*[G]*/, const int32_t *n_gt_dev, int64_t gt_capacity,
+                      const int32_t *frame_dev /*[3]: w, h, image_id*/, const double *thresholds_dev /*[T]*/, int T, int C,
+                      int64_t *npos /*[C-1]*/, float *rec_score, int32_t *rec_label, int32_t *rec_image, int32_t *rec_position,
+                      uint32_t *rec_flags, int64_t record_capacity, int64_t *cursor /*[1]*/, int32_t *error_word /*[1]*/,
+                      void *workspace, size_t workspace_bytes, void *stream);
+/* Precision / recall and voc_ap (voc_eval.py:199-219, 115-135) of every class at every threshold, once per test set.  labels_sorted /
+ * flags_sorted: the records ordered by (label ascending, score descending, image_id ascending, position ascending), the first
+ * min(*n_dev, capacity) rows live.  ap[t, c] (float64) = NaN when npos[c] == 0 (a class the reference does not know), else the sum of
+ * (rec[i] - rec[i-1]) * mpre[i] over the points where recall changes, added in ascending order like the reference; tp_total /
+ * fp_total [T, C-1] the counts.  Limits: 2 <= C <= 256, 1 <= T <= 16.  workspace >= 256 + 8 * capacity bytes, any content. */
+int frcnn_eval_average_precision(const int32_t *labels_sorted, const uint32_t *flags_sorted, const int64_t *n_dev, int64_t capacity,
+                                 const int64_t *npos /*[C-1]*/, int T, int C, double *ap /*[T,C-1]*/, int64_t *tp_total /*[T,C-1]*/,
+                                 int64_t *fp_total /*[T,C-1]*/, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- input stage in front of the path ------------------------------------------------------
  * One uint8 HWC RGB frame in HBM -> [hflip] -> PIL-bilinear resize to (oh, ow) -> /255 -> (x - mean) / std -> float CHW

@@ -2,11 +2,13 @@
 inference.DetectGraph replays, every result brought to the host; and the GPU time of the post-process alone, the op chain behind
 predict (softmax ... decode ... batched_nms, with its host syncs) against ops.detect_postprocess, from HIP events.
 
-    python tools/infer_bench.py --config vgg|fpn [--amp bf16] [--steps N] [--warmup W] [--only detect]
+    python tools/infer_bench.py --config vgg|fpn [--amp bf16] [--steps N] [--warmup W] [--only detect] [--eval] [--out FILE]
 
 Synthetic frames (600x1000 for VGG16, 800x1344 for ResNet-50-FPN), head weights spread as tests/test_gpu_detect.py spreads them (a
 random-init head gives near-constant scores).  Prints one JSON line.  --only detect runs the eager detect loop alone (for a
-kernel trace)."""
+kernel trace).  --eval measures the detection evaluator instead (faster_rcnn_pytorch_amd/evaluation.py): images/s of DetectGraph
+replays with and without the evaluator's update in the graph, the update kernel's GPU time from the in-library profiler, and the
+host alternative -- to_host() per frame plus the reference-form matching in numpy -- in the same run.  --out writes the JSON too."""
 import argparse
 import json
 import os
@@ -81,6 +83,76 @@ def event_ms(fn, reps):
     return float(np.median(out))
 
 
+def host_match(b, l, s, gtb, gtl, gtd, w, h, thr=0.5):
+    """The reference-form matching of one frame on the host (evaluation/voc_eval.py:90-91, 162-197 without its JSON files): float64
+    pixel boxes, the +1 overlap against the same-class ground truths, first maximum, TP / FP / ignored in score order."""
+    px = b.astype(np.float32) * np.array([w, h, w, h])
+    gt = gtb.astype(np.float64)
+    ga = (gt[:, 2] - gt[:, 0] + 1) * (gt[:, 3] - gt[:, 1] + 1)
+    used, flags = set(), np.zeros(len(l), np.int8)
+    for i in np.argsort(-s, kind="stable"):
+        bb = px[i]
+        iw = np.minimum(bb[2], gt[:, 2]) - np.maximum(bb[0], gt[:, 0]) + 1
+        ih = np.minimum(bb[3], gt[:, 3]) - np.maximum(bb[1], gt[:, 1]) + 1
+        ok = (gtl == l[i]) & (iw > 0) & (ih > 0)
+        flags[i] = 2
+        if ok.any():
+            ov = np.where(ok, iw * ih / ((bb[2] - bb[0] + 1) * (bb[3] - bb[1] + 1) + ga - iw * ih), -np.inf)
+            m = int(np.argmax(ov))
+            if ov[m] >= thr:
+                if gtd[m]:
+                    flags[i] = 3
+                elif m not in used:
+                    used.add(m)
+                    flags[i] = 1
+    return flags
+
+
+def eval_bench(a, m, x, H, W, res):
+    """DetectGraph with and without the evaluator's update, and the host alternative, on one synthetic frame whose ground truth is cut
+    from its own detections."""
+    from faster_rcnn_pytorch_amd import _lib
+    from faster_rcnn_pytorch_amd.evaluation import DetectionEvaluator, GroundTruth
+    b, l, s = (t.numpy() for t in m.detect(x, THRESHOLD).to_host())
+    w, h = 500, 375
+    pick = np.arange(0, max(len(l), 1), max(len(l) // 8, 1))[:8] if len(l) else np.zeros(0, np.int64)
+    gtb = np.round(b[pick].astype(np.float64) * np.array([w, h, w, h])).astype(np.float32).reshape(-1, 4)
+    gtl, gtd = l[pick].astype(np.int32), (np.arange(len(pick)) % 4 == 1).astype(np.uint8)
+    ev = DetectionEvaluator(m.num_classes, (0.5,), record_capacity=1 << 22, gt_capacity=64, device=x.device)
+    gt = GroundTruth(64, x.device)
+    plain = DetectGraph(m, (H, W), threshold=THRESHOLD)
+    fused = DetectGraph(m, (H, W), threshold=THRESHOLD, evaluator=ev, gt=gt)
+    frame = [0]
+
+    def with_update():
+        gt.set(gtb, gtl, gtd, (w, h), frame[0])
+        frame[0] += 1
+        fused(x)
+
+    def host_path():
+        hb, hl, hs = (t.numpy() for t in plain(x).to_host())
+        host_match(hb, hl, hs, gtb, gtl, gtd, w, h)
+    ips = {"detect_graph_no_sync": rate(lambda: plain(x), a.steps, a.warmup),
+           "detect_graph_with_eval_update": rate(with_update, a.steps, a.warmup),
+           "detect_graph_to_host_plus_numpy_matching": rate(host_path, a.steps, a.warmup)}
+    res["images_per_s"] = ips
+    ev.reset()
+    _lib.prof_reset()
+    _lib.prof_enable(True)
+    for k in range(a.steps):                                   # eager updates: the profiler's events bracket each launch
+        gt.set(gtb, gtl, gtd, (w, h), k)
+        ev.update(plain.out, gt)
+    torch.cuda.synchronize()
+    _lib.prof_enable(False)
+    us = sorted(1e3 * v for v in _lib.prof_samples().get("eval_update_kernel", []))
+    res["eval_update_kernel_us"] = {"median": us[len(us) // 2], "min": us[0], "launches": len(us)} if us else None
+    t0 = time.perf_counter()
+    out = ev.summarize()
+    res["summarize_ms"] = 1e3 * (time.perf_counter() - t0)
+    res["detections_per_image"], res["gt_per_image"], res["records"] = int(len(l)), int(len(pick)), out["n_records"]
+    res["map_at_0.5"] = float(out["map"][0])
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--config", choices=("vgg", "fpn"), default="vgg")
@@ -88,6 +160,8 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--only", choices=("all", "detect"), default="all")
+    ap.add_argument("--eval", action="store_true", help="measure the detection evaluator (DetectGraph with / without its update, and the host path)")
+    ap.add_argument("--out", default=None, help="also write the JSON record to this file")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     m, head, (H, W) = build(a.config, dev)
@@ -96,6 +170,13 @@ def main():
     res = {"config": a.config, "amp": a.amp, "image_hw": [H, W], "threshold": THRESHOLD, "steps": a.steps,
            "device": torch.cuda.get_device_name(0)}
     with amp:
+        if a.eval:
+            eval_bench(a, m, x, H, W, res)
+            print(json.dumps(res))
+            if a.out:
+                with open(a.out, "w") as f:
+                    json.dump(res, f, indent=1)
+            return
         if a.only == "detect":
             res["images_per_s"] = {"detect_eager": rate(lambda: m.detect(x, THRESHOLD).to_host(), a.steps, a.warmup)}
             print(json.dumps(res))
@@ -120,6 +201,9 @@ def main():
         res["candidates_per_image"] = int((prob > THRESHOLD).sum().item())
         res["detections_per_image"] = int(det.count.item())
     print(json.dumps(res))
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
 
 
 if __name__ == "__main__":
