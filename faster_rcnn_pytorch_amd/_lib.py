@@ -16,6 +16,7 @@ HT_ERR_PERM_LENGTH, HT_ERR_PERM_RANGE, HT_ERR_UPSTREAM_ABORT, HT_ERR_SHORT = 1, 
 OP_TOPK, OP_NMS, OP_REGION_PROPOSAL, OP_RPN_TARGETS, OP_HEAD_TARGETS, OP_PREPROCESS, OP_HEAD_BWD, OP_RPN_CONV, OP_RPN_CONV_WGRAD, OP_RPN_CONV_F32 = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
 OP_DETECT = 11
 OP_EVAL = 12
+OP_COCO_EVAL = 13
 EVAL_TP, EVAL_FP, EVAL_IGNORED = 1, 2, 3                     # a record's flags: 2 bits per threshold
 EVAL_ERR_UPSTREAM_ABORT, EVAL_ERR_GT_OVERFLOW, EVAL_ERR_COUNT_RANGE, EVAL_ERR_LABEL_RANGE = 1, 2, 4, 8
 
@@ -85,6 +86,9 @@ SIGNATURES = {
     "frcnn_eval_update": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
                                 _vp, _sz, _vp]),
     "frcnn_eval_average_precision": (_i, [_vp, _vp, _vp, _i64, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "frcnn_coco_eval_update": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
+                                     _vp, _vp, _vp, _sz, _vp]),
+    "frcnn_coco_eval_accumulate": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "frcnn_preprocess_image": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "frcnn_preprocess_boxes": (_i, [_vp, _i64, _i, _i, _i, _i, _i, _vp, _vp]),
     "frcnn_diag_occupy": (_i, [_i, _i, _vp]),

@@ -23,6 +23,7 @@
 // labels detect produces.
 #include "frcnn_common.h"
 #include "frcnn_layout.h"
+#include "eval_dev.h"
 FRCNN_LAYOUT_STAMP(eval);
 
 #define EVAL_MAX_P 2048
@@ -32,13 +33,6 @@ FRCNN_LAYOUT_STAMP(eval);
 #define EVAL_THREADS 256
 #define EVAL_MAX_WG 64
 
-// device error word (evaluation.py reports them)
-#define EVAL_ERR_UPSTREAM_ABORT 1      // count < 0: an aborted proposal scan upstream
-#define EVAL_ERR_GT_OVERFLOW 2         // n_gt > the ground-truth capacity
-#define EVAL_ERR_COUNT_RANGE 4         // count > the detection capacity
-#define EVAL_ERR_LABEL_RANGE 8         // a label outside 0 .. C-2
-
-typedef unsigned long long u64;
 
 static bool eval_supported(int64_t D, int64_t G) { return D >= 1 && D <= (int64_t)(EVAL_MAX_C - 1) * EVAL_MAX_P && G >= 1 && G <= EVAL_MAX_G; }
 
@@ -64,13 +58,6 @@ size_t frcnn_ws_eval(int64_t D, int64_t G)
 {
     if (!eval_supported(D, G)) return 0;
     return 256 + eval_ws_layout(D, G, nullptr, nullptr);        // + the slack that aligns the caller's pointer
-}
-
-// monotone in the float's value; -0 folded onto +0 (Python's sort sees them as equal)
-__device__ __forceinline__ uint32_t eval_orderable(float score)
-{
-    const uint32_t u = __float_as_uint(score == 0.0f ? 0.0f : score);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
 // Python's max(a, b) / min(a, b): the first argument unless the second is strictly beyond it (a NaN first argument stays)

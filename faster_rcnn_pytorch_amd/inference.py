@@ -12,7 +12,8 @@ class DetectGraph(object):
     overwritten by the next call (clone them, or call .to_host(), to keep a result).  The score threshold lives in a device tensor
     that the kernels read at replay time, so set_threshold() takes effect on the next call without a new capture.
 
-    evaluator= (an evaluation.DetectionEvaluator) and gt= (an evaluation.GroundTruth) add the evaluator's per-frame update to the same
+    evaluator= (an evaluation.DetectionEvaluator with gt= an evaluation.GroundTruth for the VOC protocol, or an
+    evaluation.CocoDetectionEvaluator with gt= an evaluation.CocoGroundTruth for the COCO one) adds the evaluator's per-frame update to the same
     graph: the reference's test loop (test.py:60: predict, then the evaluator) as one replay per frame with no host sync.  Write the
     frame's ground truth with gt.set(...) before the call (the warm-up and the capture score nothing).  Without them the captured
     graph is detect alone."""

@@ -10,6 +10,7 @@ Mirrors (file:line under the reference):
   torchvision AnchorGenerator    as called at models/new_model.py:23-25,46
   FRCNN.predict post-processing  models/model.py:368-402, models/new_model.py:420-470 (detect_postprocess)
   VOC AP evaluator               evaluation/voc_eval.py:67-225 (eval_update, eval_average_precision)
+  COCO evaluator (bbox)          evaluation/coco_eval.py, test.py:60-88,124-128 (coco_eval_update, coco_eval_accumulate)
 
 PyTorch is plumbing here (device memory, streams, autograd glue).  Every op requires contiguous
 fp32 tensors on a HIP device and raises otherwise: there is no CPU path in the product.
@@ -440,6 +441,77 @@ def eval_average_precision(labels_sorted, flags_sorted, n_records, npos, n_thres
         check(lib.frcnn_eval_average_precision(_ptr(labels_sorted), _ptr(flags_sorted), _ptr(n_records), cap, _ptr(npos), T, int(num_classes),
                                                _ptr(ap), _ptr(tp), _ptr(fp), _ptr(ws), nb, _stream()), "eval_average_precision")
     return ap, tp, fp
+
+
+def coco_eval_update(dets, gt_boxes, gt_area, gt_labels, gt_iscrowd, n_gt, frame, thresholds, num_classes, max_det, npig, rec_score,
+                     rec_label, rec_image, rec_rank, rec_flags, cursor, error_word, workspace=None):
+    """One frame of the COCO bbox protocol (evaluation/coco_eval.py CocoEvaluator.update, test.py:60-88: pycocotools' computeIoU and
+    evaluateImg) in one launch and no host sync: per category the live rows of `dets` (an ops.Detections, rows in any order) are ranked
+    by (score descending, position ascending), cut to max_det and matched at every (area range, threshold); the kept detections are
+    appended to the record store and the frame's non-ignored ground truths are added to npig.  gt_boxes [G,4] f64 pixel xywh, gt_area
+    [G] f64, gt_labels [G] i32, gt_iscrowd [G] u8, n_gt i32[1], frame i32[3] = (w, h, image_id), thresholds f64[T]: all on the device and
+    read when the kernel runs.  The record store: rec_score f32, rec_label / rec_image / rec_rank i32 [record_capacity], rec_flags i32
+    [record_capacity, 4] (per area range 2 bits per threshold: _lib.EVAL_TP / EVAL_FP / EVAL_IGNORED); cursor i64[1]; error_word i32[1]
+    (_lib.EVAL_ERR_*); npig i64[C-1, 4].  See include/frcnn_hip.h.  evaluation.CocoDetectionEvaluator owns these buffers."""
+    boxes = _req(dets.boxes, name="dets.boxes")
+    labels = _req(dets.labels, torch.int32, "dets.labels")
+    scores = _req(dets.scores, name="dets.scores")
+    count = _req(dets.count, torch.int32, "dets.count")
+    gt_boxes = _req(gt_boxes, torch.float64, "gt_boxes")
+    gt_area = _req(gt_area, torch.float64, "gt_area")
+    gt_labels = _req(gt_labels, torch.int32, "gt_labels")
+    gt_iscrowd = _req(gt_iscrowd, torch.uint8, "gt_iscrowd")
+    n_gt = _req(n_gt, torch.int32, "n_gt")
+    frame = _req(frame, torch.int32, "frame")
+    thresholds = _req(thresholds, torch.float64, "thresholds")
+    npig = _req(npig, torch.int64, "npig")
+    cursor = _req(cursor, torch.int64, "cursor")
+    error_word = _req(error_word, torch.int32, "error_word")
+    recs = (_req(rec_score, name="rec_score"), _req(rec_label, torch.int32, "rec_label"), _req(rec_image, torch.int32, "rec_image"),
+            _req(rec_rank, torch.int32, "rec_rank"), _req(rec_flags, torch.int32, "rec_flags"))
+    D, G, T, cap = labels.numel(), gt_labels.numel(), thresholds.numel(), rec_score.numel()
+    if boxes.numel() != 4 * D or scores.numel() != D or gt_boxes.numel() != 4 * G or gt_area.numel() != G or gt_iscrowd.numel() != G \
+            or frame.numel() != 3 or npig.numel() != 4 * (num_classes - 1) or any(r.numel() != cap for r in recs[:4]) \
+            or rec_flags.numel() != 4 * cap or count.numel() < 1 or n_gt.numel() < 1:
+        raise ValueError("coco_eval_update: shapes disagree")
+    for t in (dets.boxes, dets.labels, dets.scores, dets.count, npig, cursor, error_word, rec_score, rec_label, rec_image, rec_rank, rec_flags):
+        if not t.is_contiguous():
+            raise ValueError("coco_eval_update: the detections and the evaluator's buffers must be contiguous (they are written or read in place)")
+    dev = boxes.device
+    nb = _lib.workspace_bytes(_lib.OP_COCO_EVAL, D, G)
+    ws = workspace if workspace is not None else _workspace(dev, nb)
+    with torch.cuda.device(dev):
+        check(lib.frcnn_coco_eval_update(_ptr(boxes), _ptr(labels), _ptr(scores), _ptr(count), D, _ptr(gt_boxes), _ptr(gt_area), _ptr(gt_labels),
+                                         _ptr(gt_iscrowd), _ptr(n_gt), G, _ptr(frame), _ptr(thresholds), T, int(num_classes), int(max_det),
+                                         _ptr(npig), _ptr(recs[0]), _ptr(recs[1]), _ptr(recs[2]), _ptr(recs[3]), _ptr(recs[4]), cap, _ptr(cursor),
+                                         _ptr(error_word), _ptr(ws), ws.numel(), _stream()), "coco_eval_update")
+
+
+def coco_eval_accumulate(labels_sorted, ranks_sorted, flags_sorted, n_records, npig, rec_thresholds, n_thresholds, num_classes, max_dets):
+    """COCOeval.accumulate (evaluation/coco_eval.py CocoEvaluator.accumulate, test.py:124-128) over records in the order (label ascending,
+    score descending, image_id ascending, rank ascending), the first min(n_records, capacity) live (n_records: device i64[1]).
+    rec_thresholds f64[R] on the device, max_dets three ints.  Returns (precision f64 [T, R, C-1, 4, 3], recall f64 [T, C-1, 4, 3]) on the
+    device, -1 where npig == 0."""
+    labels_sorted = _req(labels_sorted, torch.int32, "labels_sorted")
+    ranks_sorted = _req(ranks_sorted, torch.int32, "ranks_sorted")
+    flags_sorted = _req(flags_sorted, torch.int32, "flags_sorted")
+    n_records = _req(n_records, torch.int64, "n_records")
+    npig = _req(npig, torch.int64, "npig")
+    rec_thresholds = _req(rec_thresholds, torch.float64, "rec_thresholds")
+    cap, T, nc, R = labels_sorted.numel(), int(n_thresholds), int(num_classes) - 1, rec_thresholds.numel()
+    md = [int(v) for v in max_dets]
+    if ranks_sorted.numel() != cap or flags_sorted.numel() != 4 * cap or npig.numel() != 4 * nc or n_records.numel() < 1 or len(md) != 3:
+        raise ValueError("coco_eval_accumulate: shapes disagree")
+    dev = labels_sorted.device
+    precision = torch.empty((max(T, 1), max(R, 1), max(nc, 1), 4, 3), dtype=torch.float64, device=dev)
+    recall = torch.empty((max(T, 1), max(nc, 1), 4, 3), dtype=torch.float64, device=dev)
+    nb = 256 + 32 * cap
+    ws = _workspace(dev, nb)
+    with torch.cuda.device(dev):
+        check(lib.frcnn_coco_eval_accumulate(_ptr(labels_sorted), _ptr(ranks_sorted), _ptr(flags_sorted), _ptr(n_records), cap, _ptr(npig),
+                                             _ptr(rec_thresholds), R, T, int(num_classes), md[0], md[1], md[2], _ptr(precision), _ptr(recall),
+                                             _ptr(ws), nb, _stream()), "coco_eval_accumulate")
+    return precision, recall
 
 
 def region_proposal(reg, cls, anchors, min_size_norm, pre_nms_top_k, iou_threshold, post_nms_top_k, grid=None, want_src=False,

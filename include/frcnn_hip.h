@@ -59,7 +59,8 @@ typedef enum {
     FRCNN_OP_RPN_CONV_WGRAD = 9,  /* frcnn_rpn_conv_wgrad (per-split partial gradients) */
     FRCNN_OP_RPN_CONV_F32 = 10,   /* n1 = C: frcnn_rpn_conv3x3_f32_fwd / _bwd_data / _wgrad (ticket words, transposed weights, slabs) */
     FRCNN_OP_DETECT = 11,         /* n1 = P RoI rows, n2 = C classes: frcnn_detect_postprocess (0 outside its limits) */
-    FRCNN_OP_EVAL = 12            /* n1 = detection capacity, n2 = ground-truth capacity: frcnn_eval_update (0 outside its limits) */
+    FRCNN_OP_EVAL = 12,           /* n1 = detection capacity, n2 = ground-truth capacity: frcnn_eval_update (0 outside its limits) */
+    FRCNN_OP_COCO_EVAL = 13       /* n1 = detection capacity, n2 = ground-truth capacity: frcnn_coco_eval_update (0 outside its limits) */
 } frcnn_op;
 
 /* FRCNN_ABI_VERSION, or FRCNN_ERR_UNSUPPORTED (message in frcnn_last_error) when the objects the library was linked from were compiled
@@ -468,6 +469,47 @@ int frcnn_eval_update(const float *boxes /*[D,4]*/, const int32_t *labels /*[D]*
 int frcnn_eval_average_precision(const int32_t *labels_sorted, const uint32_t *flags_sorted, const int64_t *n_dev, int64_t capacity,
                                  const int64_t *npos /*[C-1]*/, int T, int C, double *ap /*[T,C-1]*/, int64_t *tp_total /*[T,C-1]*/,
                                  int64_t *fp_total /*[T,C-1]*/, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- detection evaluator: the COCO protocol, bbox, useCats = 1 (evaluation/coco_eval.py, test.py:60-88,124-128) --------- */
+/* One frame in one launch and no host sync (graph-capturable): replaces CocoEvaluator.update (evaluation/coco_eval.py: prepare_for_coco_detection,
+ * convert_to_xywh, COCOeval.evaluate -> computeIoU / evaluateImg) and the pixel boxes of test.py:68-71 for the detections of one image.
+ *   boxes / labels / scores / count_dev: the tensors of frcnn_detect_postprocess (normalised fp32 xyxy, 0-based labels, *count_dev live
+ *   rows of det_capacity, in ANY order); gt_boxes float64 pixel xywh, gt_area float64 (the annotation's own area), gt_labels in the same
+ *   label space, gt_iscrowd 0 / 1, *n_gt_dev live rows of gt_capacity; frame_dev = (original width, original height, image_id);
+ *   thresholds_dev = T IoU thresholds (float64).  Everything that varies per frame is read on the device when the kernel runs.
+ * Pixel box in fp32: X1 = x1 * w, ..., W = X2 - X1, H = Y2 - Y1, widened to float64; area = W * H.  Per category the detections are
+ * ranked by (score descending, position ascending) and cut to max_det (<= 100).  IoU is maskUtils.iou on boxes in float64 (crowd: union
+ * = the detection's area).  Area ranges: all, small, medium, large = [0, 1e10], [0, 32^2], [32^2, 96^2], [96^2, 1e10]; a ground truth
+ * is ignored in a range when it is crowd or its area lies outside.  Matching is COCOeval.evaluateImg per (area range, threshold): the
+ * non-ignored ground truths first, the ignored ones only when none of the first matched, matched non-crowd ground truths skipped, the
+ * later of equal IoUs wins; an unmatched detection whose area lies outside the range is ignored.
+ * Effects: npig[l, a] += 1 for every ground truth not ignored in range a; *cursor += the kept detections (one atomic add per category
+ * present; slots past record_capacity are counted, not written); records (score, label, image_id, rank in its image and category,
+ * flags[4]: per area range 2 bits per threshold, FRCNN_EVAL_TP = matched and not ignored, FRCNN_EVAL_FP = unmatched and not ignored,
+ * FRCNN_EVAL_IGNORED otherwise) in the reserved slots, in any order -- the defined order of the set is (label ascending, score
+ * descending, image_id ascending, rank ascending).  *error_word |= 1 when *count_dev < 0, 2 when *n_gt_dev > gt_capacity, 4 when
+ * *count_dev > det_capacity, 8 for a detection or ground-truth label outside 0 .. C-2; a frame with any of them is not recorded.
+ * Limits (FRCNN_ERR_UNSUPPORTED otherwise): 2 <= C <= 256, 1 <= det_capacity <= (C-1) * 2048, 1 <= gt_capacity <= 1024, 1 <= T <= 16,
+ * 1 <= max_det <= 100.  boxes 16-byte aligned.  workspace: frcnn_workspace_bytes(FRCNN_OP_COCO_EVAL, det_capacity, gt_capacity) bytes,
+ * any content, not shared with a call that may run at the same time. */
+int frcnn_coco_eval_update(const float *boxes /*[D,4]*/, const int32_t *labels /*[D]*/, const float *scores /*[D]*/, const int32_t *count_dev,
+                           int64_t det_capacity, const double *gt_boxes /*[G,4] pixel xywh*/, const double *gt_area /*[G]*/,
+                           const int32_t *gt_labels /*[G]*/, const uint8_t *gt_iscrowd /*[G]*/, const int32_t *n_gt_dev, int64_t gt_capacity,
+                           const int32_t *frame_dev /*[3]: w, h, image_id*/, const double *thresholds_dev /*[T]*/, int T, int C, int max_det,
+                           int64_t *npig /*[C-1,4]*/, float *rec_score, int32_t *rec_label, int32_t *rec_image, int32_t *rec_rank,
+                           uint32_t *rec_flags /*[record_capacity,4]*/, int64_t record_capacity, int64_t *cursor /*[1]*/,
+                           int32_t *error_word /*[1]*/, void *workspace, size_t workspace_bytes, void *stream);
+/* COCOeval.accumulate (evaluation/coco_eval.py: CocoEvaluator.accumulate, test.py:124-128), once per test set.  labels_sorted /
+ * ranks_sorted / flags_sorted [capacity,4]: the records ordered by (label ascending, score descending, image_id ascending, rank
+ * ascending), the first min(*n_dev, capacity) rows live.  For every category k, area range a and M in (max_det_0, max_det_1, max_det_2)
+ * over the records of rank < M: tp / fp cumulative sums, rc = tp / npig, pr = tp / (fp + tp + 2^-52), pr made non-increasing from the
+ * right; recall[t,k,a,m] = rc[-1] (0 without detections); precision[t,r,k,a,m] = pr[searchsorted(rc, rec_thresholds[r], 'left')], 0
+ * past the end; both -1 where npig[k,a] == 0.  precision float64 [T,R,C-1,4,3], recall float64 [T,C-1,4,3].
+ * Limits: 2 <= C <= 256, 1 <= T <= 16, 1 <= R <= 256.  workspace >= 256 + 32 * capacity bytes, any content. */
+int frcnn_coco_eval_accumulate(const int32_t *labels_sorted, const int32_t *ranks_sorted, const uint32_t *flags_sorted, const int64_t *n_dev,
+                               int64_t capacity, const int64_t *npig /*[C-1,4]*/, const double *rec_thresholds_dev /*[R]*/, int R, int T, int C,
+                               int max_det_0, int max_det_1, int max_det_2, double *precision, double *recall, void *workspace,
+                               size_t workspace_bytes, void *stream);
 
 /* ---- input stage in front of the path ------------------------------------------------------
  * One uint8 HWC RGB frame in HBM -> [hflip] -> PIL-bilinear resize to (oh, ow) -> /255 -> (x - mean) / std -> float CHW

@@ -2,13 +2,16 @@
 inference.DetectGraph replays, every result brought to the host; and the GPU time of the post-process alone, the op chain behind
 predict (softmax ... decode ... batched_nms, with its host syncs) against ops.detect_postprocess, from HIP events.
 
-    python tools/infer_bench.py --config vgg|fpn [--amp bf16] [--steps N] [--warmup W] [--only detect] [--eval] [--out FILE]
+    python tools/infer_bench.py --config vgg|fpn [--amp bf16] [--steps N] [--warmup W] [--only detect] [--eval [--protocol voc|coco]] [--out FILE]
 
 Synthetic frames (600x1000 for VGG16, 800x1344 for ResNet-50-FPN), head weights spread as tests/test_gpu_detect.py spreads them (a
 random-init head gives near-constant scores).  Prints one JSON line.  --only detect runs the eager detect loop alone (for a
 kernel trace).  --eval measures the detection evaluator instead (faster_rcnn_pytorch_amd/evaluation.py): images/s of DetectGraph
 replays with and without the evaluator's update in the graph, the update kernel's GPU time from the in-library profiler, and the
-host alternative -- to_host() per frame plus the reference-form matching in numpy -- in the same run.  --out writes the JSON too."""
+host alternative -- to_host() per frame plus the reference-form matching in numpy -- in the same run.  --eval --protocol coco
+measures the COCO protocol (evaluation.CocoDetectionEvaluator): replays with and without its update, the update kernel's GPU time,
+the accumulate kernel's and summarize(); the VOC update's kernel time is taken in the same run for comparison.  --out writes the JSON
+too.  No time is asserted anywhere."""
 import argparse
 import json
 import os
@@ -153,6 +156,53 @@ def eval_bench(a, m, x, H, W, res):
     res["map_at_0.5"] = float(out["map"][0])
 
 
+def coco_eval_bench(a, m, x, H, W, res):
+    """DetectGraph with and without the COCO evaluator's update on one synthetic frame whose annotations are cut from its own
+    detections, the update and accumulate kernels' GPU times, and the VOC update's kernel time on the same detections."""
+    from faster_rcnn_pytorch_amd import _lib
+    from faster_rcnn_pytorch_amd.evaluation import CocoDetectionEvaluator, CocoGroundTruth, DetectionEvaluator, GroundTruth
+    b, l, s = (t.numpy() for t in m.detect(x, THRESHOLD).to_host())
+    w, h = 640, 480
+    pick = np.arange(0, max(len(l), 1), max(len(l) // 8, 1))[:8] if len(l) else np.zeros(0, np.int64)
+    px = np.round(b[pick].astype(np.float64) * np.array([w, h, w, h])).reshape(-1, 4)
+    gtb = np.stack([px[:, 0], px[:, 1], px[:, 2] - px[:, 0], px[:, 3] - px[:, 1]], 1)
+    gtl, crowd = l[pick].astype(np.int32), (np.arange(len(pick)) % 4 == 1).astype(np.uint8)
+    ev = CocoDetectionEvaluator(m.num_classes, record_capacity=1 << 20, gt_capacity=64, device=x.device)
+    gt = CocoGroundTruth(64, x.device)
+    plain = DetectGraph(m, (H, W), threshold=THRESHOLD)
+    fused = DetectGraph(m, (H, W), threshold=THRESHOLD, evaluator=ev, gt=gt)
+    frame = [0]
+
+    def with_update():
+        gt.set(gtb, gtl, crowd, None, orig_wh=(w, h), image_id=frame[0])
+        frame[0] += 1
+        fused(x)
+    res["protocol"] = "coco"
+    res["images_per_s"] = {"detect_graph_no_sync": rate(lambda: plain(x), a.steps, a.warmup),
+                           "detect_graph_with_coco_eval_update": rate(with_update, a.steps, a.warmup)}
+    ev.reset()
+    voc, vgt = DetectionEvaluator(m.num_classes, (0.5,), record_capacity=1 << 20, gt_capacity=64, device=x.device), GroundTruth(64, x.device)
+    vgt.set(px.astype(np.float32), gtl, crowd, (w, h), 0)
+    _lib.prof_reset()
+    _lib.prof_enable(True)
+    for k in range(a.steps):                                   # eager updates: the profiler's events bracket each launch
+        gt.set(gtb, gtl, crowd, None, orig_wh=(w, h), image_id=k)
+        ev.update(plain.out, gt)
+        voc.update(plain.out, vgt)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = ev.summarize()
+    res["summarize_ms"] = 1e3 * (time.perf_counter() - t0)
+    _lib.prof_enable(False)
+    samples = _lib.prof_samples()
+    for key, kernel in (("coco_update_kernel_us", "coco_update_kernel"), ("voc_eval_update_kernel_us", "eval_update_kernel"),
+                        ("coco_accumulate_kernel_us", "coco_accumulate_kernel")):
+        us = sorted(1e3 * v for v in samples.get(kernel, []))
+        res[key] = {"median": us[len(us) // 2], "min": us[0], "launches": len(us)} if us else None
+    res["detections_per_image"], res["gt_per_image"], res["records"] = int(len(l)), int(len(pick)), out["n_records"]
+    res["stats"] = [float(v) for v in out["stats"]]
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--config", choices=("vgg", "fpn"), default="vgg")
@@ -161,6 +211,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--only", choices=("all", "detect"), default="all")
     ap.add_argument("--eval", action="store_true", help="measure the detection evaluator (DetectGraph with / without its update, and the host path)")
+    ap.add_argument("--protocol", choices=("voc", "coco"), default="voc", help="with --eval: the VOC AP evaluator (default) or the COCO protocol")
     ap.add_argument("--out", default=None, help="also write the JSON record to this file")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -171,7 +222,7 @@ def main():
            "device": torch.cuda.get_device_name(0)}
     with amp:
         if a.eval:
-            eval_bench(a, m, x, H, W, res)
+            (coco_eval_bench if a.protocol == "coco" else eval_bench)(a, m, x, H, W, res)
             print(json.dumps(res))
             if a.out:
                 with open(a.out, "w") as f:
