@@ -91,6 +91,8 @@ SIGNATURES = {
     "frcnn_coco_eval_accumulate": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "frcnn_preprocess_image": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "frcnn_preprocess_boxes": (_i, [_vp, _i64, _i, _i, _i, _i, _i, _vp, _vp]),
+    "frcnn_mosaic_workspace": (_sz, [_vp, _i, _i]),
+    "frcnn_mosaic": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "frcnn_diag_occupy": (_i, [_i, _i, _vp]),
     "frcnn_prof_enable": (_i, [_i]),
     "frcnn_prof_collect": (_i, []),

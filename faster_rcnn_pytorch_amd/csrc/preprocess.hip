@@ -11,64 +11,22 @@
 //   resample_h_kernel      : lane = (row, out column): u8 x 3 gathers through the (optionally mirrored) window
 //   resample_v_norm_kernel : lane = (out row, out column) of the PADDED frame: vertical window, /255, -mean, /std in
 //                            binary32 in the reference's operation order, three coalesced plane stores; zeros in the pad
+// The window, the 3-channel window sum and the clip live in resample_dev.h (shared with mosaic.hip).
 // Bit-exact against Pillow through the oracle (tests/test_preprocess.py).  HBM-bound in principle (1.5 MB in, 10 MB out
 // for 480x640 -> 800x1066) but at these sizes the two passes are launch/latency bound (~10 us).
 #include "frcnn_common.h"
 #include "frcnn_internal.h"
 #include "frcnn_layout.h"
 FRCNN_LAYOUT_STAMP(preprocess);
-#include <cmath>
-
-#define RS_BITS 22
-
-static int rs_ksize_host(int in_size, int out_size)
-{
-    const double scale = (double)in_size / (double)out_size;
-    const double fs = scale < 1.0 ? 1.0 : scale;
-    return (int)std::ceil(fs) * 2 + 1;
-}
+#include "resample_dev.h"           // the resampler's device code, shared with mosaic.hip
 
 __global__ __launch_bounds__(256) void resample_coeffs_kernel(int in_x, int out_x, int ks_x, int32_t *__restrict__ bx, int32_t *__restrict__ kx,
                                                              int in_y, int out_y, int ks_y, int32_t *__restrict__ by, int32_t *__restrict__ ky)
 {
     int i = blockIdx.x * 256 + threadIdx.x;
-    int in_size, out_size, ks; int32_t *bounds, *kk;
-    if (i < out_x) { in_size = in_x; out_size = out_x; ks = ks_x; bounds = bx; kk = kx; }
-    else { i -= out_x; if (i >= out_y) return; in_size = in_y; out_size = out_y; ks = ks_y; bounds = by; kk = ky; }
-    const double scale = (double)in_size / (double)out_size;
-    const double fs = scale < 1.0 ? 1.0 : scale;
-    const double support = 1.0 * fs;
-    const double center = 0.0 + ((double)i + 0.5) * scale;
-    const double ss = 1.0 / fs;
-    int xmin = (int)(center - support + 0.5);
-    if (xmin < 0) xmin = 0;
-    int xmax = (int)(center + support + 0.5);
-    if (xmax > in_size) xmax = in_size;
-    xmax -= xmin;
-    double ww = 0.0;
-    for (int x = 0; x < xmax; ++x) {
-        double a = ((double)(x + xmin) - center + 0.5) * ss;
-        if (a < 0.0) a = -a;
-        ww += a < 1.0 ? 1.0 - a : 0.0;
-    }
-    for (int x = 0; x < ks; ++x) {
-        double v = 0.0;
-        if (x < xmax) {
-            double a = ((double)(x + xmin) - center + 0.5) * ss;
-            if (a < 0.0) a = -a;
-            v = a < 1.0 ? 1.0 - a : 0.0;
-            if (ww != 0.0) v = v / ww;
-        }
-        kk[(size_t)i * ks + x] = v < 0.0 ? (int32_t)(-0.5 + v * (double)(1 << RS_BITS)) : (int32_t)(0.5 + v * (double)(1 << RS_BITS));
-    }
-    bounds[2 * i] = xmin;
-    bounds[2 * i + 1] = xmax;
-}
-
-__device__ __forceinline__ uint8_t rs_clip8(int32_t v)
-{
-    v >>= RS_BITS;
-    return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
+    if (i < out_x) { rs_coeffs_row(i, in_x, out_x, ks_x, bx, kx); return; }
+    i -= out_x;
+    if (i < out_y) rs_coeffs_row(i, in_y, out_y, ks_y, by, ky);
 }
 
 __global__ __launch_bounds__(256) void resample_h_kernel(const uint8_t *__restrict__ src, int h, int w, int flip, int ow, int ks,
@@ -77,19 +35,11 @@ __global__ __launch_bounds__(256) void resample_h_kernel(const uint8_t *__restri
     const int xx = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
     if (xx >= ow) return;
     const int xmin = bx[2 * xx], n = bx[2 * xx + 1];
-    const int32_t *k = kx + (size_t)xx * ks;
     const uint8_t *row = src + (size_t)y * w * 3;
-    int32_t s0 = 1 << (RS_BITS - 1), s1 = s0, s2 = s0;
-    for (int x = 0; x < n; ++x) {
-        int sx = x + xmin;
-        if (flip) sx = w - 1 - sx;
-        const int32_t c = k[x];
-        s0 += (int32_t)row[sx * 3 + 0] * c;
-        s1 += (int32_t)row[sx * 3 + 1] * c;
-        s2 += (int32_t)row[sx * 3 + 2] * c;
-    }
+    uint8_t px[3];
+    rs_window_rgb(row + (flip ? w - 1 - xmin : xmin) * 3, flip ? -3 : 3, n, kx + (size_t)xx * ks, px);
     uint8_t *o = tmp + ((size_t)y * ow + xx) * 3;
-    o[0] = rs_clip8(s0); o[1] = rs_clip8(s1); o[2] = rs_clip8(s2);
+    o[0] = px[0]; o[1] = px[1]; o[2] = px[2];
 }
 
 struct NormConst { float mean[3], std[3]; };
@@ -103,14 +53,9 @@ __global__ __launch_bounds__(256) void resample_v_norm_kernel(const uint8_t *__r
     float v0 = 0.0f, v1 = 0.0f, v2 = 0.0f;
     if (yy < oh && xx < ow) {
         const int ymin = by[2 * yy], n = by[2 * yy + 1];
-        const int32_t *k = ky + (size_t)yy * ks;
-        int32_t s0 = 1 << (RS_BITS - 1), s1 = s0, s2 = s0;
-        for (int y = 0; y < n; ++y) {
-            const uint8_t *p = tmp + ((size_t)(y + ymin) * ow + xx) * 3;
-            const int32_t c = k[y];
-            s0 += (int32_t)p[0] * c; s1 += (int32_t)p[1] * c; s2 += (int32_t)p[2] * c;
-        }
-        const uint8_t u0 = rs_clip8(s0), u1 = rs_clip8(s1), u2 = rs_clip8(s2);
+        uint8_t px[3];
+        rs_window_rgb(tmp + ((size_t)ymin * ow + xx) * 3, (ptrdiff_t)ow * 3, n, ky + (size_t)yy * ks, px);
+        const uint8_t u0 = px[0], u1 = px[1], u2 = px[2];
         if (out_u8) { uint8_t *q = out_u8 + ((size_t)yy * ow + xx) * 3; q[0] = u0; q[1] = u1; q[2] = u2; }
         v0 = ((float)u0 / 255.0f - nc.mean[0]) / nc.std[0];          // F.to_tensor .div(255); F.normalize sub_(mean).div_(std)
         v1 = ((float)u1 / 255.0f - nc.mean[1]) / nc.std[1];

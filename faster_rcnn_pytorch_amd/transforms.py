@@ -8,9 +8,20 @@ Mirrors (file:line under the reference):
   new_datasets/build.py:20-33, datasets/build.py:10-24   Compose([RandomHorizontalFlip, Resize(800, 1333), ToTensor, Normalize])
   new_datasets/coco_dataset.py:49-66  batched_tensor_from_tensor_list (zero pad to a multiple of 32)
 JPEG decoding and the dataset classes stay out of scope; the flip coin is the caller's (random.random() < p).
+
+Mosaic augmentation (config.py:16 --mosaic_transform), on the kernels of csrc/mosaic.hip:
+  datasets/voc_dataset.py:145-156, datasets/coco_dataset.py:154-157   where the option is applied (the 0.5 coin is the caller's)
+  datasets/mosaic_transform.py:39-95   load_mosaic: three more frames (the caller's choice), the per-tile Compose, shift, concat
+  datasets/mosaic_transform.py:7-26    shift_mosaic_boxes, get_concat_h_cut_center, get_concat_v_cut_center
+  datasets/transforms_.py:61-127       resize_ (both resizes of a tile; its own order of float operations in the size logic)
+  datasets/transforms_.py:150-178      crop_ incl. the hand-back of the uncropped frame when no box survives
+  datasets/transforms_.py:278-288      RandomSizeCrop (DeviceMosaicStage.draw_regions: the same distribution, not the same stream)
+  datasets/build.py:15-19              the ordinary transform the canvas then enters (DeviceMosaicStage.__call__)
 """
+import collections
 import ctypes as C
 import math
+import random
 
 import numpy as np
 import torch
@@ -97,3 +108,115 @@ class DeviceInputStage:
         x = preprocess_image(img, (oh, ow), (ph, pw), flip, self.mean, self.std)
         b = preprocess_boxes(boxes, (w, h), (ow, oh), flip) if boxes is not None else None
         return x[None], b, {"size": (oh, ow), "padded": (ph, pw), "orig_size": (h, w)}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# mosaic augmentation
+# ---------------------------------------------------------------------------------------------------------------------------
+def mosaic_resize_hw(h, w, size, max_size=1333):
+    """The first resize of a mosaic tile: resize_'s size logic for a scalar size, in ITS order of float operations
+    (transforms_.py:93-114; get_size_with_aspect_ratio above mirrors the other transforms file) -> (H1, W1)."""
+    h, w = int(h), int(w)
+    if max_size is not None:
+        lo, hi = float(min(h, w)), float(max(h, w))
+        if size / lo * hi > max_size:
+            size = int(round(max_size / hi * lo))
+    if (w <= h and w == size) or (h <= w and h == size):
+        return h, w
+    if w < h:
+        return int(size * h / w), size
+    return size, int(size * w / h)
+
+
+class MosaicResult(collections.namedtuple("MosaicResult", "canvas_u8 boxes labels count fallback")):
+    """canvas_u8 uint8 [2 size, 2 size, 3]; boxes float32 [N, 4] and labels int64 [N] with the first `count` rows live (tile order,
+    each tile's own order) and zeros behind them; count int32 [1] and fallback uint8 [4] (1: the tile was not cropped) on the device."""
+    __slots__ = ()
+
+    def to_host(self):
+        """What load_mosaic returns: (uint8 array, boxes[:count], labels[:count]).  Synchronises."""
+        n = int(self.count.item())
+        return self.canvas_u8.cpu().numpy(), self.boxes[:n].cpu().numpy(), self.labels[:n].cpu().numpy()
+
+
+def mosaic(imgs, boxes, labels, regions, size, max_size=1333, counts=None):
+    """load_mosaic (mosaic_transform.py:39-95) for four frames already on the device, without a host read-back.
+
+    imgs: four uint8 HWC tensors.  boxes / labels: four float32 [n_k, 4] / int64 [n_k] tensors (pixel xyxy of their frame), or one
+    tile-major tensor each plus counts = (n_0, n_1, n_2, n_3).  regions: [4][4] host integers, (i, j, h, w) of each tile's crop in its
+    RESIZED frame (DeviceMosaicStage.draw_regions).  Whether a tile is cropped is decided on the device (crop_ hands back the uncropped
+    frame when no box survives); the result has fixed shapes and a device count, so the call can be captured into a graph."""
+    if len(imgs) != 4:
+        raise ValueError("mosaic takes four frames, got %d" % len(imgs))
+    imgs = [_req(im, torch.uint8, "imgs[%d]" % k) for k, im in enumerate(imgs)]
+    for im in imgs:
+        if im.dim() != 3 or im.shape[2] != 3:
+            raise ValueError("every frame must be [h, w, 3] uint8 (HWC RGB), got %s" % (tuple(im.shape),))
+    dev = imgs[0].device
+    if counts is None:
+        if len(boxes) != 4 or len(labels) != 4:
+            raise ValueError("mosaic takes four box and four label tensors (or one of each plus counts)")
+        counts = [int(b.shape[0]) for b in boxes]
+        if [int(l.shape[0]) for l in labels] != counts:
+            raise ValueError("boxes and labels disagree about the number of rows per tile")
+        boxes = torch.cat([_req(b, torch.float32, "boxes").reshape(-1, 4) for b in boxes])
+        labels = torch.cat([_req(l, torch.int64, "labels").reshape(-1) for l in labels])
+    boxes = _req(boxes, torch.float32, "boxes").reshape(-1, 4)
+    labels = _req(labels, torch.int64, "labels").reshape(-1)
+    counts = [int(c) for c in counts]
+    n = sum(counts)
+    if len(counts) != 4 or min(counts) < 0 or boxes.shape[0] != n or labels.shape[0] != n:
+        raise ValueError("counts %s do not describe %d boxes and %d labels" % (counts, boxes.shape[0], labels.shape[0]))
+    size = int(size)
+    src_hw = np.array([[im.shape[0], im.shape[1]] for im in imgs], np.int32)
+    reg = np.ascontiguousarray(regions, dtype=np.int32).reshape(4, 4)
+    offs = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+    ms = 0 if max_size is None else int(max_size)
+    canvas = torch.empty((2 * size, 2 * size, 3), dtype=torch.uint8, device=dev)
+    boxes_out, labels_out = torch.empty_like(boxes), torch.empty_like(labels)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    fallback = torch.empty(4, dtype=torch.uint8, device=dev)
+    nb = int(lib.frcnn_mosaic_workspace(_np_ptr(src_hw), size, ms))
+    if nb == 0:
+        raise ValueError("mosaic: unsupported shapes %s at size %d (sides of 1 .. 32767 before and after the first resize, 2 * size < 32768)"
+                         % (src_hw.tolist(), size))
+    ws = _workspace(dev, nb)
+    srcs = (C.c_void_p * 4)(*[im.data_ptr() for im in imgs])
+    with torch.cuda.device(dev):
+        check(lib.frcnn_mosaic(srcs, _np_ptr(src_hw), size, ms, _np_ptr(reg), _ptr(boxes), _ptr(labels), _np_ptr(offs), _ptr(canvas),
+                               _ptr(boxes_out), _ptr(labels_out), _ptr(count), _ptr(fallback), _ptr(ws), nb, _stream()), "mosaic")
+    return MosaicResult(canvas, boxes_out, labels_out, count, fallback)
+
+
+class DeviceMosaicStage:
+    """load_mosaic followed by the ordinary transform (datasets/build.py:15-19: flip, RandomResize([out_size], out_max_size), ToTensor,
+    Normalize), on the device.  The random draws stay with the caller: which three other frames, the dataset's `random.random() > 0.5`
+    (voc_dataset.py:145), the flip coin, and the crop regions -- draw_regions() draws those with the reference's distribution.
+
+    stage(imgs, boxes, labels, regions, flip=False) -> (x [1, 3, PH, PW] float32, normalised boxes [N, 4], labels [N], count int32 [1]
+    on the device, meta).  The final stage is applied to all N rows (it is elementwise): rows at and above count are padding."""
+
+    def __init__(self, size=600, max_size=1333, min_crop=384, out_size=800, out_max_size=1333, mean=IMAGENET_MEAN, std=IMAGENET_STD,
+                 size_divisible=None):
+        self.size, self.max_size, self.min_crop = int(size), max_size, int(min_crop)        # the reference fixes max_size = 1333, min_crop = 384
+        self.final = DeviceInputStage(out_size, out_max_size, mean, std, size_divisible)
+
+    def draw_regions(self, shapes, rng=random):
+        """RandomSizeCrop(min_crop, size) (transforms_.py:284-286) for four source shapes (h, w): w in [min_crop, min(W1, size)], h in
+        [min_crop, min(H1, size)], the corner uniform over the positions that fit.  The reference's DISTRIBUTION, not its random stream
+        (torchvision's get_params draws the corner from torch's generator).  rng: anything with randint(a, b), both ends included."""
+        out = []
+        for h, w in shapes:
+            H1, W1 = mosaic_resize_hw(h, w, self.size, self.max_size)
+            if min(H1, W1, self.size) < self.min_crop:
+                raise ValueError("a %d x %d frame resizes to %d x %d: smaller than min_crop %d" % (h, w, H1, W1, self.min_crop))
+            cw = rng.randint(self.min_crop, min(W1, self.size))
+            ch = rng.randint(self.min_crop, min(H1, self.size))
+            out.append((rng.randint(0, H1 - ch), rng.randint(0, W1 - cw), ch, cw))
+        return out
+
+    def __call__(self, imgs, boxes, labels, regions, flip=False, counts=None):
+        r = mosaic(imgs, boxes, labels, regions, self.size, self.max_size, counts)
+        x, b, meta = self.final(r.canvas_u8, r.boxes, flip)
+        meta["fallback"] = r.fallback
+        return x, b, r.labels, r.count, meta

@@ -524,6 +524,32 @@ int frcnn_preprocess_image(const uint8_t *src_hwc, int h, int w, int flip, int o
  * i.e. the normalised boxes the model takes.  binary32 throughout, like the reference's tensors.                   */
 int frcnn_preprocess_boxes(const float *boxes, int64_t n, int w, int h, int flip, int ow, int oh, float *out, void *stream);
 
+/* ---- mosaic augmentation (--mosaic_transform, config.py:16) -------------------------------------------------------
+ * Four uint8 HWC RGB frames in HBM -> one [2*size, 2*size, 3] uint8 canvas and one compacted box / label list.  Replaces load_mosaic
+ * (datasets/mosaic_transform.py:39-95; called from datasets/voc_dataset.py:145-156 and datasets/coco_dataset.py:154-157) without its
+ * choice of frames: per tile k = 0..3
+ *   Resize(size, max_size)     resize_, datasets/transforms_.py:61-127: Pillow's 8-bit bilinear resize to H1 x W1, boxes * (W1/w, H1/h)
+ *   RandomSizeCrop's crop_     transforms_.py:150-178 with the CALLER's region (i, j, h, w) (the draw of :284-286 is the caller's): boxes
+ *                              - (j, i), min (w, h), clamp at 0; kept when both sides > 0 and (cw*ch) / (bw*bh) > 0.3; when NO box is
+ *                              kept (a tile without boxes included) the tile is the uncropped H1 x W1 frame with ALL its boxes (:174-176)
+ *   Resize((size, size))       a second Pillow resize of the cropped image as an image of its own, boxes * (size/w, size/h)
+ *   shift_mosaic_boxes         mosaic_transform.py:7-12,82-85: + (0,0), (size,0), (0,size), (size,size)
+ *   get_concat_h/v_cut_center  mosaic_transform.py:15-26,88-93: the four size x size tiles side by side; boxes, labels in tile order
+ * Bit-identical to Pillow and to the reference's binary32 box arithmetic.  The crop decision is taken on the device and never read
+ * back: a fixed six launches, no allocation, capturable.
+ *   src_hw [4][2] (h, w) and regions [4][4] are HOST arrays, read during the call.  max_size <= 0: no cap.  tile_offsets [5] HOST:
+ *   tile k owns rows [tile_offsets[k], tile_offsets[k+1]) of boxes / labels; N = tile_offsets[4] (0 is legal: every tile falls back).
+ *   boxes [N,4] pixel xyxy of the source frames, labels [N]; boxes_out [N,4], labels_out [N]: the first *count_dev rows live, in tile
+ *   order and each tile's own order, zeros behind them.  boxes and boxes_out 16-byte aligned, not overlapping.  fallback_dev [4]: 1
+ *   where the tile was not cropped.  workspace: frcnn_mosaic_workspace(src_hw, size, max_size) bytes (0 for shapes it refuses).
+ * FRCNN_ERR_INVALID_ARG, before anything is launched: a NULL pointer; a side of a source or resized frame, or 2 * size, of 2^15 or
+ * more; a region outside its resized frame or with h < 1 or w < 1; offsets that do not start at 0 or decrease.  FRCNN_ERR_WORKSPACE: a
+ * short workspace.  */
+size_t frcnn_mosaic_workspace(const int32_t *src_hw, int size, int max_size);
+int frcnn_mosaic(const uint8_t *const src_hwc[4], const int32_t *src_hw, int size, int max_size, const int32_t *regions,
+                 const float *boxes, const int64_t *labels, const int32_t *tile_offsets, uint8_t *canvas, float *boxes_out,
+                 int64_t *labels_out, int32_t *count_dev, uint8_t *fallback_dev, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- in-library kernel timing (HIP events on the launch stream) -------------------------------------- */
 /* When enabled, every kernel launch made by this library is bracketed by two hipEventRecord on the
  * caller's stream.  frcnn_prof_collect() synchronises those events (call it after the stream is idle)
