@@ -15,35 +15,31 @@
 //      per area range with 2 bits per threshold: TP = matched and not ignored, FP = unmatched and not ignored, IGNORED = the rest).
 //      npig[k][a] += the frame's non-ignored ground truths.  No scratch has to be zero between calls.
 //  coco_accumulate_kernel : one workgroup per (category, area range) over the records in the order (label ascending, score descending,
-//      image_id ascending, rank ascending), for each of the 3 maxDets and each threshold: the scan of eval_ap_kernel for the cumulative
+//      image_id ascending, rank ascending), for each of the 3 maxDets and each threshold: the scan of eval_dev.h for the cumulative
 //      (tp, fp) over the records of rank < M, pr = tp / (fp + tp + 2^-52) stored at the true positives (between them pr only falls
 //      and recall does not move, so the envelope and searchsorted(rc, recThr, 'left') need nothing else; position 0 without a true
 //      positive holds 0), a right-to-left running maximum as a second scan, and one lane per recall threshold that bisects for the
 //      first true positive k with k / npig >= recThr.  The float64 operations of accumulate and no others.
 //
 // Not built: the segm and keypoints IoU types, useCats = 0.
+//
+// The limits (EVAL_MAX_*, EVAL_THREADS, eval_supported), the error bits of a frame, eval_lower_bound and the (tp, fp) scan are those of
+// eval_dev.h, shared with eval.hip.
 #include "frcnn_common.h"
 #include "frcnn_layout.h"
 #include "eval_dev.h"
 FRCNN_LAYOUT_STAMP(coco_eval);
 
-#define COCO_MAX_P 2048
-#define COCO_MAX_C 256
-#define COCO_MAX_G 1024
-#define COCO_MAX_T 16
 #define COCO_MAX_R 256
 #define COCO_A 4                       // area ranges: all, small, medium, large
 #define COCO_MAX_DET 100               // the per-image cut (maxDets[-1])
-#define COCO_THREADS 256
-#define COCO_TILE 4096                 // IoUs (float64) held in LDS at a time: >= 4 detections x COCO_MAX_G ground truths
+#define COCO_TILE 4096                 // IoUs (float64) held in LDS at a time: >= 4 detections x EVAL_MAX_G ground truths
 #define COCO_CROWD_BIT 4               // s_gflag: bits 0 .. 3 = ignored in area range a, bit 4 = crowd
-
-static bool coco_supported(int64_t D, int64_t G) { return D >= 1 && D <= (int64_t)(COCO_MAX_C - 1) * COCO_MAX_P && G >= 1 && G <= COCO_MAX_G; }
 
 // workspace: the packed keys of the frame's detections, one segment per category (any content; nothing must be zero)
 size_t frcnn_ws_coco_eval(int64_t D, int64_t G)
 {
-    if (!coco_supported(D, G)) return 0;
+    if (!eval_supported(D, G)) return 0;
     return 256 + align_up((size_t)D * sizeof(u64), 256);        // + the slack that aligns the caller's pointer
 }
 
@@ -54,7 +50,7 @@ __device__ __forceinline__ bool coco_outside(double area, int a)
     return area < lo || area > hi;
 }
 
-__global__ __launch_bounds__(COCO_THREADS) void coco_update_kernel(
+__global__ __launch_bounds__(EVAL_THREADS) void coco_update_kernel(
     const float4 *__restrict__ boxes, const int32_t *__restrict__ labels, const float *__restrict__ scores, const int32_t *__restrict__ count_dev,
     int D, const double *__restrict__ gt_boxes, const double *__restrict__ gt_area, const int32_t *__restrict__ gt_labels,
     const uint8_t *__restrict__ gt_crowd, const int32_t *__restrict__ n_gt_dev, int G, const int32_t *__restrict__ frame,
@@ -63,25 +59,22 @@ __global__ __launch_bounds__(COCO_THREADS) void coco_update_kernel(
     int32_t *__restrict__ err, u64 *__restrict__ ws_keys)
 {
     __shared__ double s_iou[COCO_TILE];
-    __shared__ uint32_t s_gtm[COCO_MAX_G / 32][64];             // [word][chain]: a lane's words lie in its own bank
-    __shared__ int32_t s_gidx[COCO_MAX_G];
-    __shared__ uint8_t s_gflag[COCO_MAX_G];
+    __shared__ uint32_t s_gtm[EVAL_MAX_G / 32][64];             // [word][chain]: a lane's words lie in its own bank
+    __shared__ int32_t s_gidx[EVAL_MAX_G];
+    __shared__ uint8_t s_gflag[EVAL_MAX_G];
     __shared__ u64 s_key[COCO_MAX_DET], s_sorted[COCO_MAX_DET];
     __shared__ double s_dx[COCO_MAX_DET], s_dy[COCO_MAX_DET], s_dxe[COCO_MAX_DET], s_dye[COCO_MAX_DET], s_dwh[COCO_MAX_DET];
     __shared__ uint32_t s_flags[COCO_MAX_DET][COCO_A];
     __shared__ uint8_t s_dout[COCO_MAX_DET];                    // bit a: the detection's area lies outside range a
-    __shared__ double s_thr[COCO_MAX_T];
+    __shared__ double s_thr[EVAL_MAX_T];
     __shared__ int s_hist[256];
     __shared__ int s_m, s_off, s_bad, s_fill, s_sel, s_rem;
-    __shared__ int s_wcnt[COCO_THREADS / 64];
+    __shared__ int s_wcnt[EVAL_THREADS / 64];
     __shared__ u64 s_base;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int k = blockIdx.x, nc = (int)gridDim.x;
     const int cnt_raw = *count_dev, ng_raw = *n_gt_dev;
-    int e = 0;
-    if (cnt_raw < 0) e |= EVAL_ERR_UPSTREAM_ABORT;
-    if (cnt_raw > D) e |= EVAL_ERR_COUNT_RANGE;
-    if (ng_raw > G) e |= EVAL_ERR_GT_OVERFLOW;
+    int e = eval_frame_error(cnt_raw, D, ng_raw, G);
     const int n = e ? 0 : cnt_raw;
     const int ng = e ? 0 : (ng_raw < 0 ? 0 : ng_raw);
     if (tid == 0) { s_m = 0; s_off = 0; s_bad = 0; s_fill = 0; }
@@ -90,12 +83,12 @@ __global__ __launch_bounds__(COCO_THREADS) void coco_update_kernel(
     // ---- the category's detections: how many, and where its segment of the workspace begins
     {
         int m_loc = 0, off_loc = 0, bad = 0;
-        for (int i = tid; i < n; i += COCO_THREADS) {
+        for (int i = tid; i < n; i += EVAL_THREADS) {
             const int l = labels[i];
             if (l < 0 || l >= nc) bad = 1;
             else { m_loc += l == k; off_loc += l < k; }
         }
-        for (int g = tid; g < ng; g += COCO_THREADS) {
+        for (int g = tid; g < ng; g += EVAL_THREADS) {
             const int l = gt_labels[g];
             if (l < 0 || l >= nc) bad = 1;
         }
@@ -105,7 +98,7 @@ __global__ __launch_bounds__(COCO_THREADS) void coco_update_kernel(
     }
     __syncthreads();
     if (s_bad) e |= EVAL_ERR_LABEL_RANGE;
-    // a frame that reports an error is not recorded at all: summarize() raises, a partial frame would only hide what was lost
+    // a frame that reports an error is not recorded at all (eval_dev.h)
     if (e) {
         if (k == 0 && tid == 0) atomicOr(err, e);
         return;
@@ -113,14 +106,14 @@ __global__ __launch_bounds__(COCO_THREADS) void coco_update_kernel(
     const int m = s_m, off = s_off;
     // ---- the category's ground truths, in their original order
     int mk = 0;
-    for (int c0 = 0; c0 < ng; c0 += COCO_THREADS) {
+    for (int c0 = 0; c0 < ng; c0 += EVAL_THREADS) {
         const int g = c0 + tid;
         const bool mine = g < ng && gt_labels[g] == k;
         const u64 mask = __ballot(mine);
         if (lane == 0) s_wcnt[wv] = __popcll(mask);
         __syncthreads();
         int base = mk, tot = 0;
-        for (int w = 0; w < COCO_THREADS / 64; ++w) {
+        for (int w = 0; w < EVAL_THREADS / 64; ++w) {
             if (w < wv) base += s_wcnt[w];
             tot += s_wcnt[w];
         }
@@ -147,7 +140,7 @@ __global__ __launch_bounds__(COCO_THREADS) void coco_update_kernel(
     // ---- the max_det first detections of the category in (score descending, position ascending)
     const int nd = m < max_det ? m : max_det;
     u64 *seg = ws_keys + off;                                                               // off + m <= n <= D
-    for (int i = tid; i < n; i += COCO_THREADS)
+    for (int i = tid; i < n; i += EVAL_THREADS)
         if (labels[i] == k) {
             const int slot = atomicAdd(&s_fill, 1);
             if (slot < m) seg[slot] = ((u64)eval_orderable(scores[i]) << 32) | (uint32_t)~(uint32_t)i;     // unique per detection
@@ -162,7 +155,7 @@ __global__ __launch_bounds__(COCO_THREADS) void coco_update_kernel(
         for (int shift = 56; shift >= 0; shift -= 8) {
             s_hist[tid] = 0;
             __syncthreads();
-            for (int i = tid; i < m; i += COCO_THREADS) {
+            for (int i = tid; i < m; i += EVAL_THREADS) {
                 const u64 key = seg[i];
                 if (shift == 56 || (key >> (shift + 8)) == prefix) atomicAdd(&s_hist[(int)((key >> shift) & 255ull)], 1);
             }
@@ -182,7 +175,7 @@ __global__ __launch_bounds__(COCO_THREADS) void coco_update_kernel(
         }
         if (tid == 0) s_fill = 0;
         __syncthreads();
-        for (int i = tid; i < m; i += COCO_THREADS) {
+        for (int i = tid; i < m; i += EVAL_THREADS) {
             const u64 key = seg[i];
             if (key >= prefix) {
                 const int slot = atomicAdd(&s_fill, 1);
@@ -197,7 +190,7 @@ __global__ __launch_bounds__(COCO_THREADS) void coco_update_kernel(
         for (int j = 0; j < nd; ++j) r += s_key[j] > key;
         s_sorted[r] = key;
     }
-    for (int i = tid; i < (COCO_MAX_G / 32) * 64; i += COCO_THREADS) (&s_gtm[0][0])[i] = 0u;
+    for (int i = tid; i < (EVAL_MAX_G / 32) * 64; i += EVAL_THREADS) (&s_gtm[0][0])[i] = 0u;
     __syncthreads();
     if (tid < nd) {
         const float4 b = boxes[(uint32_t)~(uint32_t)s_sorted[tid]];
@@ -219,7 +212,7 @@ __global__ __launch_bounds__(COCO_THREADS) void coco_update_kernel(
     const int dc = mk > 0 ? (COCO_TILE / mk < nd ? COCO_TILE / mk : nd) : nd;
     for (int d0 = 0; d0 < nd; d0 += dc) {
         const int cn = nd - d0 < dc ? nd - d0 : dc;
-        for (int p = tid; p < cn * mk; p += COCO_THREADS) {
+        for (int p = tid; p < cn * mk; p += EVAL_THREADS) {
             const int d = d0 + p / mk, j = p % mk, g = s_gidx[j];
             const double gx = gt_boxes[4 * g], gy = gt_boxes[4 * g + 1], gw = gt_boxes[4 * g + 2], gh = gt_boxes[4 * g + 3];
             double iou = 0.0;
@@ -285,39 +278,29 @@ __global__ __launch_bounds__(COCO_THREADS) void coco_update_kernel(
 // ---------------------------------------------------------------------------------------------------------------------------------
 // accumulate
 // ---------------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ long long coco_lower_bound(const int32_t *__restrict__ a, long long n, int v)
-{
-    long long lo = 0, hi = n;
-    while (lo < hi) {
-        const long long mid = (lo + hi) >> 1;
-        if (a[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-__global__ __launch_bounds__(COCO_THREADS) void coco_accumulate_kernel(
+__global__ __launch_bounds__(EVAL_THREADS) void coco_accumulate_kernel(
     const int32_t *__restrict__ labels, const int32_t *__restrict__ ranks, const uint32_t *__restrict__ flags, const u64 *__restrict__ n_dev,
     long long cap, const u64 *__restrict__ npig, const double *__restrict__ rec_thr, int R, int T, int K, int md0, int md1, int md2,
     double *__restrict__ precision, double *__restrict__ recall, double *__restrict__ prec_ws)
 {
-    __shared__ u64 s_wave[COCO_THREADS / 64];
+    __shared__ u64 s_wave[EVAL_THREADS / 64];
     __shared__ u64 s_carry;
-    __shared__ double s_wmax[COCO_THREADS / 64];
+    __shared__ double s_wmax[EVAL_THREADS / 64];
     __shared__ double s_cmax;
     const int k = blockIdx.x / COCO_A, a = blockIdx.x % COCO_A;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const u64 np = npig[(size_t)k * COCO_A + a];
     if (np == 0) {                                                                          // the cells stay at -1
-        for (int i = tid; i < 3 * T * R; i += COCO_THREADS) {
+        for (int i = tid; i < 3 * T * R; i += EVAL_THREADS) {
             const int mi = i % 3, r = (i / 3) % R, t = i / (3 * R);
             precision[((((size_t)t * R + r) * K + k) * COCO_A + a) * 3 + mi] = -1.0;
         }
-        for (int i = tid; i < 3 * T; i += COCO_THREADS) recall[(((size_t)(i / 3) * K + k) * COCO_A + a) * 3 + i % 3] = -1.0;
+        for (int i = tid; i < 3 * T; i += EVAL_THREADS) recall[(((size_t)(i / 3) * K + k) * COCO_A + a) * 3 + i % 3] = -1.0;
         return;
     }
     const u64 n_raw = *n_dev;
     const long long n = n_raw < (u64)cap ? (long long)n_raw : cap;
-    const long long lo = coco_lower_bound(labels, n, k), hi = coco_lower_bound(labels, n, k + 1);
+    const long long lo = eval_lower_bound(labels, n, k), hi = eval_lower_bound(labels, n, k + 1);
     const double dn = (double)np;
     double *pk = prec_ws + (size_t)a * (size_t)cap + lo;          // this (category, area range)'s own segment: at most hi - lo true positives
     for (int mi = 0; mi < 3; ++mi) {
@@ -325,31 +308,19 @@ __global__ __launch_bounds__(COCO_THREADS) void coco_accumulate_kernel(
         for (int t = 0; t < T; ++t) {
             if (tid == 0) { s_carry = 0ull; s_cmax = 0.0; }
             __syncthreads();
-            // cumulative (tp, fp) as one 64-bit scan: tp in the low word, fp in the high word (both < 2^32)
-            for (long long c0 = lo; c0 < hi; c0 += COCO_THREADS) {
+            for (long long c0 = lo; c0 < hi; c0 += EVAL_THREADS) {
                 const long long i = c0 + tid;
                 const uint32_t f = (i < hi && ranks[i] < M) ? (flags[i * COCO_A + a] >> (2 * t)) & 3u : 0u;
-                u64 v = f == FRCNN_EVAL_TP ? 1ull : (f == FRCNN_EVAL_FP ? 1ull << 32 : 0ull);
-                for (int o = 1; o < 64; o <<= 1) {
-                    const u64 u = __shfl_up(v, o);
-                    if (lane >= o) v += u;
-                }
-                if (lane == 63) s_wave[wv] = v;
-                __syncthreads();
-                u64 pre = s_carry;
-                for (int w = 0; w < wv; ++w) pre += s_wave[w];
-                v += pre;
+                const u64 v = eval_scan_step(f, s_wave, &s_carry);                          // the cumulative (tp, fp) over the records of rank < M
                 if (f == FRCNN_EVAL_TP) {
                     const long long tpc = (long long)(v & 0xffffffffull), fpc = (long long)(v >> 32);
                     pk[tpc - 1] = (double)tpc / (((double)fpc + (double)tpc) + 0x1p-52);    // tp / (fp + tp + np.spacing(1))
                 }
-                __syncthreads();
-                if (tid == COCO_THREADS - 1) s_carry = v;
-                __syncthreads();
+                eval_scan_carry(v, &s_carry);
             }
             const long long Kt = (long long)(s_carry & 0xffffffffull);
             // pr made non-increasing from the right: a running maximum over the true positives, last to first
-            for (long long c0 = 0; c0 < Kt; c0 += COCO_THREADS) {
+            for (long long c0 = 0; c0 < Kt; c0 += EVAL_THREADS) {
                 const long long i = Kt - 1 - (c0 + tid);
                 double v = i >= 0 ? pk[i] : 0.0;
                 for (int o = 1; o < 64; o <<= 1) {
@@ -363,12 +334,12 @@ __global__ __launch_bounds__(COCO_THREADS) void coco_accumulate_kernel(
                 if (pre > v) v = pre;
                 if (i >= 0) pk[i] = v;
                 __syncthreads();
-                if (tid == COCO_THREADS - 1) s_cmax = v;
+                if (tid == EVAL_THREADS - 1) s_cmax = v;
                 __syncthreads();
             }
             __syncthreads();
             // precision at searchsorted(rc, recThr, 'left'): the first true positive kk with kk / npig >= recThr; 0 past the end
-            for (int r = tid; r < R; r += COCO_THREADS) {
+            for (int r = tid; r < R; r += EVAL_THREADS) {
                 const double thr = rec_thr[r];
                 long long a0 = 1, b0 = Kt + 1;
                 while (a0 < b0) {
@@ -390,12 +361,12 @@ FRCNN_EXPORT int frcnn_coco_eval_update(const float *boxes, const int32_t *label
                                         int32_t *rec_label, int32_t *rec_image, int32_t *rec_rank, uint32_t *rec_flags, int64_t record_capacity,
                                         int64_t *cursor, int32_t *error_word, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (C < 2 || C > COCO_MAX_C || T < 1 || T > COCO_MAX_T || max_det < 1 || max_det > COCO_MAX_DET || !coco_supported(det_capacity, gt_capacity) ||
-        det_capacity > (int64_t)(C - 1) * COCO_MAX_P)
+    if (C < 2 || C > EVAL_MAX_C || T < 1 || T > EVAL_MAX_T || max_det < 1 || max_det > COCO_MAX_DET || !eval_supported(det_capacity, gt_capacity) ||
+        det_capacity > (int64_t)(C - 1) * EVAL_MAX_P)
         return frcnn_set_error(FRCNN_ERR_UNSUPPORTED,
                                "coco_eval_update: C = %d, T = %d, max_det = %d, detection capacity %lld, ground-truth capacity %lld outside "
                                "2 <= C <= %d, 1 <= T <= %d, 1 <= max_det <= %d, 1 <= D <= (C-1) * %d, 1 <= G <= %d", C, T, max_det,
-                               (long long)det_capacity, (long long)gt_capacity, COCO_MAX_C, COCO_MAX_T, COCO_MAX_DET, COCO_MAX_P, COCO_MAX_G);
+                               (long long)det_capacity, (long long)gt_capacity, EVAL_MAX_C, EVAL_MAX_T, COCO_MAX_DET, EVAL_MAX_P, EVAL_MAX_G);
     FRCNN_REQUIRE(boxes && labels && scores && count_dev && gt_boxes && gt_area && gt_labels && gt_iscrowd && n_gt_dev && frame_dev && thresholds_dev &&
                   npig && rec_score && rec_label && rec_image && rec_rank && rec_flags && cursor && error_word && workspace,
                   "coco_eval_update: NULL pointer");
@@ -404,9 +375,9 @@ FRCNN_EXPORT int frcnn_coco_eval_update(const float *boxes, const int32_t *label
                   "coco_eval_update: boxes must be 16-byte aligned, gt_boxes and gt_area 8-byte aligned");
     const size_t need = frcnn_ws_coco_eval(det_capacity, gt_capacity);
     if (workspace_bytes < need) return frcnn_set_error(FRCNN_ERR_WORKSPACE, "coco_eval_update: workspace %zu < %zu bytes", workspace_bytes, need);
-    u64 *keys = (u64 *)((char *)workspace + (align_up((uintptr_t)workspace, 256) - (uintptr_t)workspace));
+    u64 *keys = (u64 *)eval_ws_base(workspace);
     hipStream_t s = (hipStream_t)stream;
-    FRCNN_LAUNCH(coco_update_kernel, dim3((unsigned)(C - 1)), dim3(COCO_THREADS), 0, s, (const float4 *)boxes, labels, scores, count_dev,
+    FRCNN_LAUNCH(coco_update_kernel, dim3((unsigned)(C - 1)), dim3(EVAL_THREADS), 0, s, (const float4 *)boxes, labels, scores, count_dev,
                  (int)det_capacity, gt_boxes, gt_area, gt_labels, gt_iscrowd, n_gt_dev, (int)gt_capacity, frame_dev, thresholds_dev, T, max_det,
                  (u64 *)npig, rec_score, rec_label, rec_image, rec_rank, rec_flags, (long long)record_capacity, (u64 *)cursor, error_word, keys);
     FRCNN_CHECK_LAUNCH("coco_update_kernel");
@@ -418,9 +389,9 @@ FRCNN_EXPORT int frcnn_coco_eval_accumulate(const int32_t *labels_sorted, const 
                                             int T, int C, int max_det_0, int max_det_1, int max_det_2, double *precision, double *recall,
                                             void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (C < 2 || C > COCO_MAX_C || T < 1 || T > COCO_MAX_T || R < 1 || R > COCO_MAX_R)
+    if (C < 2 || C > EVAL_MAX_C || T < 1 || T > EVAL_MAX_T || R < 1 || R > COCO_MAX_R)
         return frcnn_set_error(FRCNN_ERR_UNSUPPORTED, "coco_eval_accumulate: C = %d, T = %d, R = %d outside 2 <= C <= %d, 1 <= T <= %d, 1 <= R <= %d",
-                               C, T, R, COCO_MAX_C, COCO_MAX_T, COCO_MAX_R);
+                               C, T, R, EVAL_MAX_C, EVAL_MAX_T, COCO_MAX_R);
     FRCNN_REQUIRE(labels_sorted && ranks_sorted && flags_sorted && n_dev && npig && rec_thresholds_dev && precision && recall && workspace,
                   "coco_eval_accumulate: NULL pointer");
     FRCNN_REQUIRE(capacity >= 1, "coco_eval_accumulate: capacity must be >= 1");
@@ -428,9 +399,9 @@ FRCNN_EXPORT int frcnn_coco_eval_accumulate(const int32_t *labels_sorted, const 
     const size_t need = 256 + (size_t)COCO_A * (size_t)capacity * sizeof(double);
     if (workspace_bytes < need)
         return frcnn_set_error(FRCNN_ERR_WORKSPACE, "coco_eval_accumulate: workspace %zu < %zu bytes", workspace_bytes, need);
-    double *pw = (double *)((char *)workspace + (align_up((uintptr_t)workspace, 256) - (uintptr_t)workspace));
+    double *pw = (double *)eval_ws_base(workspace);
     hipStream_t s = (hipStream_t)stream;
-    FRCNN_LAUNCH(coco_accumulate_kernel, dim3((unsigned)((C - 1) * COCO_A)), dim3(COCO_THREADS), 0, s, labels_sorted, ranks_sorted, flags_sorted,
+    FRCNN_LAUNCH(coco_accumulate_kernel, dim3((unsigned)((C - 1) * COCO_A)), dim3(EVAL_THREADS), 0, s, labels_sorted, ranks_sorted, flags_sorted,
                  (const u64 *)n_dev, (long long)capacity, (const u64 *)npig, rec_thresholds_dev, R, T, C - 1, max_det_0, max_det_1, max_det_2,
                  precision, recall, pw);
     FRCNN_CHECK_LAUNCH("coco_accumulate_kernel");

@@ -15,26 +15,21 @@
 //      ascending, position ascending) is restored when the set is summarised.
 //  eval_ap_kernel     : one workgroup per class over the records in the defined order.  Recall changes exactly at the true positives
 //      and the precision envelope's running maximum is taken at them only (precision falls at every false positive), so the
-//      workgroup scans the class's segment for the cumulative (tp, fp), stores precision k / max(k + fp, eps) of the k-th true positive,
+//      workgroup scans the class's segment for the cumulative (tp, fp) (the scan of eval_dev.h), stores precision k / max(k + fp, eps) of the k-th true positive,
 //      and one lane takes the right-to-left maximum and adds (k / npos - (k - 1) / npos) * mpre in ascending k: the same float64
 //      operations in the same order as voc_ap.  A class without a countable ground truth reports NaN (the reference does not know it).
 //
 // Not reproduced: save_pred's `class_num == 20: continue` (:100-103), a FIXME for a background id that never occurs with the 0-based
 // labels detect produces.
+//
+// The limits (EVAL_MAX_*, EVAL_THREADS, eval_supported), the error bits of a frame, eval_lower_bound and the (tp, fp) scan are those of
+// eval_dev.h, shared with coco_eval.hip.
 #include "frcnn_common.h"
 #include "frcnn_layout.h"
 #include "eval_dev.h"
 FRCNN_LAYOUT_STAMP(eval);
 
-#define EVAL_MAX_P 2048
-#define EVAL_MAX_C 256
-#define EVAL_MAX_G 1024
-#define EVAL_MAX_T 16
-#define EVAL_THREADS 256
 #define EVAL_MAX_WG 64
-
-
-static bool eval_supported(int64_t D, int64_t G) { return D >= 1 && D <= (int64_t)(EVAL_MAX_C - 1) * EVAL_MAX_P && G >= 1 && G <= EVAL_MAX_G; }
 
 // workspace: ticket (64 bytes) | winner words [EVAL_MAX_T][G] u64 | match [D] i32 | reach [D] u32, each 256-byte aligned.  The ticket
 // and the winner words must be ZERO before the first call; the kernel leaves them zero.
@@ -80,11 +75,7 @@ __global__ __launch_bounds__(EVAL_THREADS) void eval_update_kernel(
     const int tid = threadIdx.x;
     const int nc = C - 1;
     const int cnt_raw = *count_dev, ng_raw = *n_gt_dev;
-    int e = 0;
-    if (cnt_raw < 0) e |= EVAL_ERR_UPSTREAM_ABORT;
-    if (cnt_raw > D) e |= EVAL_ERR_COUNT_RANGE;
-    if (ng_raw > G) e |= EVAL_ERR_GT_OVERFLOW;
-    // a frame that reports an error is not recorded at all: summarize() raises, a partial frame would only hide what was lost
+    int e = eval_frame_error(cnt_raw, D, ng_raw, G);                                      // a frame with an error records nothing
     const int n = e ? 0 : cnt_raw;
     const int ng = e ? 0 : (ng_raw < 0 ? 0 : ng_raw);
     const double fw = (double)frame[0], fh = (double)frame[1];
@@ -180,16 +171,6 @@ __global__ __launch_bounds__(EVAL_THREADS) void eval_update_kernel(
 // ---------------------------------------------------------------------------------------------------------------------------------
 // average precision (:199-219, voc_ap :115-135)
 // ---------------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ long long eval_lower_bound(const int32_t *__restrict__ a, long long n, int v)
-{
-    long long lo = 0, hi = n;
-    while (lo < hi) {
-        const long long mid = (lo + hi) >> 1;
-        if (a[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(EVAL_THREADS) void eval_ap_kernel(const int32_t *__restrict__ labels, const uint32_t *__restrict__ flags,
                                                                const u64 *__restrict__ n_dev, long long cap, const u64 *__restrict__ npos, int T,
                                                                double *__restrict__ ap, long long *__restrict__ tp_total,
@@ -198,7 +179,7 @@ __global__ __launch_bounds__(EVAL_THREADS) void eval_ap_kernel(const int32_t *__
     __shared__ u64 s_wave[EVAL_THREADS / 64];
     __shared__ u64 s_carry;
     const int cls = blockIdx.x, nc = (int)gridDim.x;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x;
     const u64 n_raw = *n_dev;
     const long long n = n_raw < (u64)cap ? (long long)n_raw : cap;
     const long long lo = eval_lower_bound(labels, n, cls), hi = eval_lower_bound(labels, n, cls + 1);
@@ -207,28 +188,16 @@ __global__ __launch_bounds__(EVAL_THREADS) void eval_ap_kernel(const int32_t *__
     for (int t = 0; t < T; ++t) {
         if (tid == 0) s_carry = 0ull;
         __syncthreads();
-        // cumulative (tp, fp) as one 64-bit scan: tp in the low word, fp in the high word (both < 2^32)
         for (long long c0 = lo; c0 < hi; c0 += EVAL_THREADS) {
             const long long i = c0 + tid;
             const uint32_t f = i < hi ? (flags[i] >> (2 * t)) & 3u : 0u;
-            u64 v = f == FRCNN_EVAL_TP ? 1ull : (f == FRCNN_EVAL_FP ? 1ull << 32 : 0ull);
-            for (int o = 1; o < 64; o <<= 1) {
-                const u64 u = __shfl_up(v, o);
-                if (lane >= o) v += u;
-            }
-            if (lane == 63) s_wave[wv] = v;
-            __syncthreads();
-            u64 pre = s_carry;
-            for (int w = 0; w < wv; ++w) pre += s_wave[w];
-            v += pre;
+            const u64 v = eval_scan_step(f, s_wave, &s_carry);    // the cumulative (tp, fp) up to this record
             if (f == FRCNN_EVAL_TP) {
                 const long long k = (long long)(v & 0xffffffffull), fpc = (long long)(v >> 32);
                 const double den = (double)(k + fpc);             // >= 1 here; the reference's max(., eps) (:217) never binds at a true positive
                 pk[k - 1] = (double)k / den;
             }
-            __syncthreads();
-            if (tid == EVAL_THREADS - 1) s_carry = v;
-            __syncthreads();
+            eval_scan_carry(v, &s_carry);
         }
         const u64 tot = s_carry;
         const long long K = (long long)(tot & 0xffffffffull);
@@ -282,8 +251,7 @@ FRCNN_EXPORT int frcnn_eval_update(const float *boxes, const int32_t *labels, co
     const size_t need = frcnn_ws_eval(det_capacity, gt_capacity);
     if (workspace_bytes < need) return frcnn_set_error(FRCNN_ERR_WORKSPACE, "eval_update: workspace %zu < %zu bytes", workspace_bytes, need);
     EvalWs w;
-    char *base = (char *)workspace + (align_up((uintptr_t)workspace, 256) - (uintptr_t)workspace);
-    eval_ws_layout(det_capacity, gt_capacity, base, &w);
+    eval_ws_layout(det_capacity, gt_capacity, eval_ws_base(workspace), &w);
     int64_t nwg = (det_capacity + EVAL_THREADS - 1) / EVAL_THREADS;
     if (nwg > EVAL_MAX_WG) nwg = EVAL_MAX_WG;
     hipStream_t s = (hipStream_t)stream;
@@ -307,7 +275,7 @@ FRCNN_EXPORT int frcnn_eval_average_precision(const int32_t *labels_sorted, cons
     const size_t need = 256 + (size_t)capacity * sizeof(double);
     if (workspace_bytes < need)
         return frcnn_set_error(FRCNN_ERR_WORKSPACE, "eval_average_precision: workspace %zu < %zu bytes", workspace_bytes, need);
-    double *pw = (double *)((char *)workspace + (align_up((uintptr_t)workspace, 256) - (uintptr_t)workspace));
+    double *pw = (double *)eval_ws_base(workspace);
     hipStream_t s = (hipStream_t)stream;
     FRCNN_LAUNCH(eval_ap_kernel, dim3((unsigned)(C - 1)), dim3(EVAL_THREADS), 0, s, labels_sorted, flags_sorted, (const u64 *)n_dev,
                  (long long)capacity, (const u64 *)npos, T, ap, (long long *)tp_total, (long long *)fp_total, pw);

@@ -38,28 +38,32 @@ from ._lib import FrcnnError
 MAX_THRESHOLDS, MAX_GT, MAX_CLASSES = 16, 1024, 256
 
 
-class GroundTruth(object):
-    """Fixed-capacity device buffers of one frame's ground truth: boxes [capacity,4] f32 pixel xyxy, labels i32, difficult u8, n i32[1],
-    frame i32[3] = (original width, original height, image_id).  set() copies in place and never reallocates, so a captured graph that
-    read these buffers sees the new frame at its next replay."""
+class _FrameBuffer(object):
+    """Fixed-capacity device buffers of one frame's ground truth in ONE allocation, so that a frame from the host is one copy: a 16-byte
+    head (original width, original height, image_id, n) as int32 -- frame i32[3] and n i32[1] are views of it -- and then the fields of
+    _FIELDS, one after the other, each [capacity, width] and each an attribute of its name.  The evaluators' kernels read exactly this
+    layout.  _set() copies in place and never reallocates, so a captured graph that read these buffers sees the new frame at its next
+    replay."""
+    _FIELDS = ()                        # (name, numpy dtype, width) in buffer order
 
     def __init__(self, capacity, device):
         capacity = int(capacity)
         if not 1 <= capacity <= MAX_GT:
-            raise ValueError("GroundTruth: capacity %d outside 1 .. %d" % (capacity, MAX_GT))
+            raise ValueError("%s: capacity %d outside 1 .. %d" % (type(self).__name__, capacity, MAX_GT))
         self.capacity = capacity
         self.device = torch.device(device)
-        # one allocation, so that a frame from the host is ONE copy: (w, h, image_id, n) | boxes | labels | difficult
-        self._o_lab, self._o_dif = 16 + 16 * capacity, 16 + 20 * capacity
-        self._buf = torch.zeros(16 + 21 * capacity, dtype=torch.uint8, device=self.device)
+        sizes = [np.dtype(dt).itemsize * w * capacity for _, dt, w in self._FIELDS]
+        self._offsets = [16 + sum(sizes[:i]) for i in range(len(sizes) + 1)]
+        nbytes = self._offsets[-1]
+        self._buf = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
         self.frame = self._buf[0:12].view(torch.int32)
         self.n = self._buf[12:16].view(torch.int32)
-        self.boxes = self._buf[16:self._o_lab].view(torch.float32).view(capacity, 4)
-        self.labels = self._buf[self._o_lab:self._o_dif].view(torch.int32)
-        self.difficult = self._buf[self._o_dif:]
+        for i, (name, dt, w) in enumerate(self._FIELDS):
+            v = self._buf[self._offsets[i]:self._offsets[i + 1]].view(getattr(torch, np.dtype(dt).name))
+            setattr(self, name, v.view(capacity, w) if w > 1 else v)
         # pinned staging buffers in a ring: the copy of frame k is asynchronous, so frame k + 1 must not be written over it.  A slot is
         # reused only after the event behind its last copy has completed (it has, unless the host runs 8 frames ahead).
-        self._ring = [torch.zeros(16 + 21 * capacity, dtype=torch.uint8) for _ in range(8)]
+        self._ring = [torch.zeros(nbytes, dtype=torch.uint8) for _ in range(8)]
         if self.device.type == "cuda":
             self._ring = [h.pin_memory() for h in self._ring]
         self._events = [None] * len(self._ring)
@@ -77,34 +81,44 @@ class GroundTruth(object):
             self._events[k] = torch.cuda.Event()
             self._events[k].record(torch.cuda.current_stream(self.device))
 
+    def _set(self, columns, n, orig_wh, image_id):
+        """columns: one array of n rows per field of _FIELDS (None = zeros), all device tensors or all host arrays.  Host arrays go over
+        in one copy; device tensors are copied in place (no sync).  More rows than the capacity are NOT silently cut: n keeps the true
+        number and the evaluator's update reports the overflow."""
+        m = min(n, self.capacity)
+        head = torch.from_numpy(np.array([int(orig_wh[0]), int(orig_wh[1]), int(image_id), n], np.int32).view(np.uint8))
+        if isinstance(columns[0], torch.Tensor) and columns[0].is_cuda:
+            for (name, _, _), col in zip(self._FIELDS, columns):
+                dst = getattr(self, name)
+                if col is None:
+                    dst[:m].zero_()
+                else:
+                    dst[:m].copy_(col.reshape((-1,) + dst.shape[1:])[:m].to(dst.dtype))
+            k, host = self._stage()
+            host[:16].copy_(head)
+            self._buf[:16].copy_(host[:16], non_blocking=True)
+        else:
+            k, host = self._stage()
+            host[:16].copy_(head)
+            h = host.numpy()
+            for off, (_, dt, w), col in zip(self._offsets, self._FIELDS, columns):
+                rows = h[off:off + np.dtype(dt).itemsize * w * m]
+                rows[:] = 0 if col is None else np.ascontiguousarray(np.asarray(col).reshape(-1, w)[:m].astype(dt)).view(np.uint8).reshape(-1)
+            self._buf.copy_(host, non_blocking=True)
+        self._sent(k)
+        return self
+
+
+class GroundTruth(_FrameBuffer):
+    """One frame's VOC ground truth on the device: boxes [capacity,4] f32 pixel xyxy, labels i32, difficult u8, n i32[1], frame i32[3] =
+    (original width, original height, image_id)."""
+    _FIELDS = (("boxes", np.float32, 4), ("labels", np.int32, 1), ("difficult", np.uint8, 1))
+
     def set(self, boxes_px, labels, difficult, orig_wh, image_id):
         """boxes_px [n,4] pixel xyxy, labels [n] (0-based), difficult [n] (0 / 1 or None), orig_wh = (w, h) of the original image,
         image_id = the image's sequence number.  Host arrays go over in one copy; device tensors are copied in place (no sync).  More
         rows than the capacity are NOT silently cut: n keeps the true number and the evaluator's update reports the overflow."""
-        n = int(len(labels))
-        m = min(n, self.capacity)
-        head = np.array([int(orig_wh[0]), int(orig_wh[1]), int(image_id), n], np.int32)
-        if isinstance(boxes_px, torch.Tensor) and boxes_px.is_cuda:
-            self.boxes[:m].copy_(boxes_px.reshape(-1, 4)[:m].to(torch.float32))
-            self.labels[:m].copy_(labels[:m].to(torch.int32))
-            if difficult is None:
-                self.difficult[:m].zero_()
-            else:
-                self.difficult[:m].copy_(difficult[:m].to(torch.uint8))
-            k, host = self._stage()
-            host[:16].copy_(torch.from_numpy(head.view(np.uint8)))
-            self._buf[:16].copy_(host[:16], non_blocking=True)
-            self._sent(k)
-            return self
-        k, host = self._stage()
-        h = host.numpy()
-        h[:16] = head.view(np.uint8)
-        h[16:16 + 16 * m] = np.ascontiguousarray(np.asarray(boxes_px, np.float32).reshape(-1, 4)[:m]).view(np.uint8).reshape(-1)
-        h[self._o_lab:self._o_lab + 4 * m] = np.ascontiguousarray(np.asarray(labels, np.int32)[:m]).view(np.uint8)
-        h[self._o_dif:self._o_dif + m] = 0 if difficult is None else np.asarray(difficult)[:m].astype(np.uint8)
-        self._buf.copy_(host, non_blocking=True)
-        self._sent(k)
-        return self
+        return self._set((boxes_px, labels, difficult), int(len(labels)), orig_wh, image_id)
 
 
 def _score_key(score):
@@ -114,100 +128,115 @@ def _score_key(score):
     return 0xFFFFFFFF - o
 
 
-class DetectionEvaluator(object):
-    """VOC AP at T IoU thresholds in one pass.  update() is one HIP launch on the current stream and has no host sync; summarize() does
-    the only device -> host copy."""
+class _RecordStore(object):
+    """What the two evaluators share: the configuration, the record store in HBM -- rec_score f32, rec_label / rec_image / rec_<_COLUMN>
+    i32 [record_capacity], rec_flags i32 [record_capacity] or [record_capacity, _FLAGS_WIDTH] --, a counter tensor i64 [C-1, ...] named
+    by _COUNTER, the device cursor and error word, the update kernel's workspace, and everything that reads the store back.  A subclass
+    names its protocol's parts and adds update() and summarize()."""
+    _COLUMN = None                      # the fourth record column: the order of a frame's records ("position" / "rank")
+    _FLAGS_WIDTH = 1                    # flag words per record
+    _COUNTER = None                     # (attribute name, trailing shape) of the per-class ground-truth counter
+    _OP = None                          # (name of the update op in messages, its _lib.OP_* code)
+    _GT = None                          # the frame-buffer class update() takes
+    _CONFIG_WORDS = None                # what merge() says two evaluators may differ in
 
-    def __init__(self, num_classes, iou_thresholds=(0.5,), record_capacity=1 << 20, gt_capacity=128, device=None):
-        thr = [float(t) for t in iou_thresholds]
+    def __init__(self, num_classes, thr, record_capacity, gt_capacity):
+        """Validates and keeps the configuration; _allocate(device) follows once the subclass has checked its own extras."""
+        name = type(self).__name__
         if not 2 <= int(num_classes) <= MAX_CLASSES:
-            raise ValueError("DetectionEvaluator: num_classes %d outside 2 .. %d" % (num_classes, MAX_CLASSES))
+            raise ValueError("%s: num_classes %d outside 2 .. %d" % (name, num_classes, MAX_CLASSES))
         if not 1 <= len(thr) <= MAX_THRESHOLDS:
-            raise ValueError("DetectionEvaluator: %d IoU thresholds, 1 .. %d supported" % (len(thr), MAX_THRESHOLDS))
+            raise ValueError("%s: %d IoU thresholds, 1 .. %d supported" % (name, len(thr), MAX_THRESHOLDS))
         if not 1 <= int(gt_capacity) <= MAX_GT:
-            raise ValueError("DetectionEvaluator: gt_capacity %d outside 1 .. %d" % (gt_capacity, MAX_GT))
+            raise ValueError("%s: gt_capacity %d outside 1 .. %d" % (name, gt_capacity, MAX_GT))
         if int(record_capacity) < 1:
-            raise ValueError("DetectionEvaluator: record_capacity must be >= 1")
-        dev = torch.device(device if device is not None else "cuda")
-        if dev.type != "cuda":
-            raise RuntimeError("DetectionEvaluator runs only on a HIP device (no CPU fallback)")
-        self.device = dev
+            raise ValueError("%s: record_capacity must be >= 1" % name)
         self.num_classes = int(num_classes)
-        self.iou_thresholds = tuple(thr)
+        self.iou_thresholds = tuple(float(t) for t in thr)
         self.record_capacity = int(record_capacity)
         self.gt_capacity = int(gt_capacity)
-        self.thresholds = torch.tensor(thr, dtype=torch.float64, device=dev)
+
+    def _allocate(self, device):
+        dev = torch.device(device if device is not None else "cuda")
+        if dev.type != "cuda":
+            raise RuntimeError("%s runs only on a HIP device (no CPU fallback)" % type(self).__name__)
+        self.device = dev
+        self.thresholds = torch.tensor(self.iou_thresholds, dtype=torch.float64, device=dev)
         cap = self.record_capacity
         self.rec_score = torch.zeros(cap, dtype=torch.float32, device=dev)
         self.rec_label = torch.zeros(cap, dtype=torch.int32, device=dev)
         self.rec_image = torch.zeros(cap, dtype=torch.int32, device=dev)
-        self.rec_position = torch.zeros(cap, dtype=torch.int32, device=dev)
-        self.rec_flags = torch.zeros(cap, dtype=torch.int32, device=dev)          # bit pattern: 2 bits per threshold
-        self.npos = torch.zeros(self.num_classes - 1, dtype=torch.int64, device=dev)
+        self._rec_order = torch.zeros(cap, dtype=torch.int32, device=dev)
+        setattr(self, "rec_" + self._COLUMN, self._rec_order)
+        # bit pattern: 2 bits per threshold, one word per area range where the protocol has them
+        self.rec_flags = torch.zeros(cap if self._FLAGS_WIDTH == 1 else (cap, self._FLAGS_WIDTH), dtype=torch.int32, device=dev)
+        self._counter = torch.zeros((self.num_classes - 1,) + self._COUNTER[1], dtype=torch.int64, device=dev)
+        setattr(self, self._COUNTER[0], self._counter)
         self.cursor = torch.zeros(1, dtype=torch.int64, device=dev)
         self.error = torch.zeros(1, dtype=torch.int32, device=dev)
         self._ws = {}
 
     # ---- per frame ----------------------------------------------------------------------------------------------------------
     def _workspace(self, D, G):
-        """The update kernel's ticket and winner words: zero before the first call, left zero by the kernel, owned by this evaluator."""
+        """The update kernel's workspace (VOC: the ticket and winner words, zero before the first call and left zero by the kernel;
+        COCO: the key segments): owned by this evaluator, so that a captured graph keeps a valid address."""
         ws = self._ws.get((D, G))
         if ws is None:
-            nb = _lib.workspace_bytes(_lib.OP_EVAL, D, G)
+            nb = _lib.workspace_bytes(self._OP[1], D, G)
             if nb == 0:
-                raise FrcnnError("eval_update: detection capacity %d / ground-truth capacity %d outside the kernel's limits" % (D, G))
+                raise FrcnnError("%s: detection capacity %d / ground-truth capacity %d outside the kernel's limits" % (self._OP[0], D, G))
             ws = torch.zeros(nb, dtype=torch.uint8, device=self.device)
             self._ws[(D, G)] = ws
         return ws
 
-    def update(self, dets, gt):
-        """Scores one frame: dets = ops.Detections of the frame, gt = its GroundTruth.  No sync; capturable into a graph with detect."""
+    def _check_gt(self, gt):
         if gt.capacity > self.gt_capacity:
-            raise ValueError("DetectionEvaluator: GroundTruth capacity %d > gt_capacity %d" % (gt.capacity, self.gt_capacity))
-        ops.eval_update(dets, gt.boxes, gt.labels, gt.difficult, gt.n, gt.frame, self.thresholds, self.num_classes, self.npos, self.rec_score,
-                        self.rec_label, self.rec_image, self.rec_position, self.rec_flags, self.cursor, self.error,
-                        workspace=self._workspace(dets.labels.numel(), gt.capacity))
+            raise ValueError("%s: %s capacity %d > gt_capacity %d" % (type(self).__name__, self._GT.__name__, gt.capacity, self.gt_capacity))
 
     def reset(self):
         self.cursor.zero_()
-        self.npos.zero_()
+        self._counter.zero_()
         self.error.zero_()
 
     # ---- per test set -------------------------------------------------------------------------------------------------------
+    def _keys(self):
+        return ("score", "label", "image_id", self._COLUMN, "flags")
+
     def _records(self):
-        return (self.rec_score, self.rec_label, self.rec_image, self.rec_position, self.rec_flags)
+        return (self.rec_score, self.rec_label, self.rec_image, self._rec_order, self.rec_flags)
 
     def state(self):
-        """The evaluator's state as device tensors (one sync for the record count): the live records in slot order, npos, n_records
-        (what update counted: more than len(score) when the store overflowed) and the error word."""
+        """The evaluator's state as device tensors (one sync for the record count): the live records in slot order, the counter,
+        n_records (what update counted: more than len(score) when the store overflowed), the error word and the configuration."""
         n_all = int(self.cursor.item())
         n = min(n_all, self.record_capacity)
-        s = dict(zip(("score", "label", "image_id", "position", "flags"), (r[:n].clone() for r in self._records())))
-        s.update(npos=self.npos.clone(), n_records=n_all, error=self.error.clone(), iou_thresholds=self.iou_thresholds, num_classes=self.num_classes)
+        s = dict(zip(self._keys(), (r[:n].clone() for r in self._records())))
+        s.update(n_records=n_all, error=self.error.clone(), **self._config())
+        s[self._COUNTER[0]] = self._counter.clone()
         return s
 
     def merge(self, other):
-        """Appends the records of `other` (a DetectionEvaluator, or a state() of one, of the same classes and thresholds) and adds its
+        """Appends the records of `other` (an evaluator of this class, or a state() of one, of the same configuration) and adds its
         counters: evaluating shards separately and merging equals one evaluator over all of them."""
-        s = other.state() if isinstance(other, DetectionEvaluator) else other
-        if tuple(s["iou_thresholds"]) != self.iou_thresholds or s["num_classes"] != self.num_classes:
-            raise ValueError("DetectionEvaluator.merge: the evaluators differ in classes or thresholds")
+        s = other.state() if isinstance(other, type(self)) else other
+        if any((tuple(s[k]) if isinstance(v, tuple) else s[k]) != v for k, v in self._config().items()):
+            raise ValueError("%s.merge: the evaluators differ in %s" % (type(self).__name__, self._CONFIG_WORDS))
         n_all = int(self.cursor.item())
         n = min(n_all, self.record_capacity)
         m = min(int(s["score"].numel()), self.record_capacity - n)
-        for dst, key in zip(self._records(), ("score", "label", "image_id", "position", "flags")):
+        for dst, key in zip(self._records(), self._keys()):
             dst[n:n + m].copy_(s[key][:m].to(self.device))
         self.cursor += int(s["n_records"])                     # keeps counting past the capacity: summarize() reports the loss
-        self.npos += s["npos"].to(self.device)
+        self._counter += s[self._COUNTER[0]].to(self.device)
         self.error |= s["error"].to(self.device)
         return self
 
     def _sorted(self):
         """(order, labels_sorted) on the device, no sync: the live slots first, in (label ascending, score descending, image_id
-        ascending, position ascending); the slots past the cursor sort behind every class."""
+        ascending, position or rank ascending); the slots past the cursor sort behind every class."""
         cap = self.record_capacity
         live = torch.arange(cap, device=self.device) < self.cursor
-        o1 = torch.sort((self.rec_image.to(torch.int64) << 32) | self.rec_position.to(torch.int64), stable=True)[1]
+        o1 = torch.sort((self.rec_image.to(torch.int64) << 32) | self._rec_order.to(torch.int64), stable=True)[1]
         lab = torch.where(live, self.rec_label, torch.full_like(self.rec_label, 0x7FFFFFFF))
         key = ((lab.to(torch.int64) << 32) | _score_key(self.rec_score))[o1]
         o2 = torch.sort(key, stable=True)[1]
@@ -215,15 +244,48 @@ class DetectionEvaluator(object):
         return order, lab[order].contiguous()
 
     def _raise_on_error(self, err, n_all):
+        name = type(self).__name__
         if err:
             what = [w for b, w in ((_lib.EVAL_ERR_UPSTREAM_ABORT, "a frame's detection count was -1 (an aborted proposal scan upstream)"),
-                                   (_lib.EVAL_ERR_GT_OVERFLOW, "a frame had more ground truths than the GroundTruth capacity"),
+                                   (_lib.EVAL_ERR_GT_OVERFLOW, "a frame had more ground truths than the %s capacity" % self._GT.__name__),
                                    (_lib.EVAL_ERR_COUNT_RANGE, "a frame's detection count exceeded its capacity"),
                                    (_lib.EVAL_ERR_LABEL_RANGE, "a label outside 0 .. num_classes - 2")) if err & b]
-            raise FrcnnError("DetectionEvaluator: error word %d: %s" % (err, "; ".join(what)))
+            raise FrcnnError("%s: error word %d: %s" % (name, err, "; ".join(what)))
         if n_all > self.record_capacity:
-            raise FrcnnError("DetectionEvaluator: the record store is full: %d of %d records were dropped (record_capacity = %d)"
-                             % (n_all - self.record_capacity, n_all, self.record_capacity))
+            raise FrcnnError("%s: the record store is full: %d of %d records were dropped (record_capacity = %d)"
+                             % (name, n_all - self.record_capacity, n_all, self.record_capacity))
+
+    def records_sorted(self):
+        """The records on the host in the order (label ascending, score descending, image_id ascending, position or rank ascending):
+        score f32, label i32, image_id i32, position or rank i32, flags u32 [n] or [n, 4] (per area range 2 bits per threshold:
+        _lib.EVAL_TP / EVAL_FP / EVAL_IGNORED).  For tests and for precision / recall curves."""
+        order, _ = self._sorted()
+        n_all, err = int(self.cursor.item()), int(self.error.item())
+        self._raise_on_error(err, n_all)
+        out = {k: r[order[:n_all]].cpu().numpy() for k, r in zip(self._keys(), self._records())}
+        out["flags"] = out["flags"].view(np.uint32)
+        return out
+
+
+class DetectionEvaluator(_RecordStore):
+    """VOC AP at T IoU thresholds in one pass.  update() is one HIP launch on the current stream and has no host sync; summarize() does
+    the only device -> host copy."""
+    _COLUMN, _FLAGS_WIDTH, _COUNTER, _OP = "position", 1, ("npos", ()), ("eval_update", _lib.OP_EVAL)
+    _GT, _CONFIG_WORDS = GroundTruth, "classes or thresholds"
+
+    def __init__(self, num_classes, iou_thresholds=(0.5,), record_capacity=1 << 20, gt_capacity=128, device=None):
+        super().__init__(num_classes, [float(t) for t in iou_thresholds], record_capacity, gt_capacity)
+        self._allocate(device)
+
+    def _config(self):
+        return {"iou_thresholds": self.iou_thresholds, "num_classes": self.num_classes}
+
+    def update(self, dets, gt):
+        """Scores one frame: dets = ops.Detections of the frame, gt = its GroundTruth.  No sync; capturable into a graph with detect."""
+        self._check_gt(gt)
+        ops.eval_update(dets, gt.boxes, gt.labels, gt.difficult, gt.n, gt.frame, self.thresholds, self.num_classes, self.npos, self.rec_score,
+                        self.rec_label, self.rec_image, self.rec_position, self.rec_flags, self.cursor, self.error,
+                        workspace=self._workspace(dets.labels.numel(), gt.capacity))
 
     def summarize(self):
         """{"ap": float64 [T, C-1] (NaN for the classes without a countable ground truth), "map": float64 [T] (the mean over the other
@@ -245,17 +307,6 @@ class DetectionEvaluator(object):
         return {"ap": ap_h, "map": mean, "npos": host[3 * k:3 * k + nc].copy(), "n_records": int(host[3 * k + nc]),
                 "tp": host[k:2 * k].reshape(T, nc).copy(), "fp": host[2 * k:3 * k].reshape(T, nc).copy()}
 
-    def records_sorted(self):
-        """The records on the host in the order (label ascending, score descending, image_id ascending, position ascending): score
-        f32, label i32, image_id i32, position i32, flags u32 (2 bits per threshold: _lib.EVAL_TP / EVAL_FP / EVAL_IGNORED).  For tests
-        and for precision / recall curves."""
-        order, _ = self._sorted()
-        n_all, err = int(self.cursor.item()), int(self.error.item())
-        self._raise_on_error(err, n_all)
-        out = {k: r[order[:n_all]].cpu().numpy() for k, r in zip(("score", "label", "image_id", "position", "flags"), self._records())}
-        out["flags"] = out["flags"].view(np.uint32)
-        return out
-
 
 # ---------------------------------------------------------------------------------------------------------------------------------
 # the COCO protocol (bbox, useCats = 1)
@@ -264,35 +315,10 @@ COCO_MAX_DET = 100
 COCO_AREA_RANGES = ((0.0, 1e10), (0.0, 32.0 ** 2), (32.0 ** 2, 96.0 ** 2), (96.0 ** 2, 1e10))      # all, small, medium, large
 
 
-class CocoGroundTruth(object):
-    """Fixed-capacity device buffers of one frame's COCO annotations: boxes [capacity,4] f64 pixel xywh, area f64, labels i32, iscrowd
-    u8, n i32[1], frame i32[3] = (original width, original height, image_id).  The same contract as GroundTruth: one allocation, a
-    pinned staging ring, set() copies in place and never reallocates, n keeps the true count on overflow."""
-
-    def __init__(self, capacity, device):
-        capacity = int(capacity)
-        if not 1 <= capacity <= MAX_GT:
-            raise ValueError("CocoGroundTruth: capacity %d outside 1 .. %d" % (capacity, MAX_GT))
-        self.capacity = capacity
-        self.device = torch.device(device)
-        # one allocation, so that a frame from the host is ONE copy: (w, h, image_id, n) | boxes f64 | area f64 | labels | iscrowd
-        self._o_area, self._o_lab, self._o_crowd = 16 + 32 * capacity, 16 + 40 * capacity, 16 + 44 * capacity
-        nbytes = 16 + 45 * capacity
-        self._buf = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
-        self.frame = self._buf[0:12].view(torch.int32)
-        self.n = self._buf[12:16].view(torch.int32)
-        self.boxes = self._buf[16:self._o_area].view(torch.float64).view(capacity, 4)
-        self.area = self._buf[self._o_area:self._o_lab].view(torch.float64)
-        self.labels = self._buf[self._o_lab:self._o_crowd].view(torch.int32)
-        self.iscrowd = self._buf[self._o_crowd:]
-        self._ring = [torch.zeros(nbytes, dtype=torch.uint8) for _ in range(8)]
-        if self.device.type == "cuda":
-            self._ring = [h.pin_memory() for h in self._ring]
-        self._events = [None] * len(self._ring)
-        self._k = 0
-
-    _stage = GroundTruth._stage
-    _sent = GroundTruth._sent
+class CocoGroundTruth(_FrameBuffer):
+    """One frame's COCO annotations on the device: boxes [capacity,4] f64 pixel xywh, area f64, labels i32, iscrowd u8, n i32[1], frame
+    i32[3] = (original width, original height, image_id).  The same contract as GroundTruth."""
+    _FIELDS = (("boxes", np.float64, 4), ("area", np.float64, 1), ("labels", np.int32, 1), ("iscrowd", np.uint8, 1))
 
     def set(self, boxes_xywh, labels, iscrowd=None, area=None, orig_wh=None, image_id=0):
         """boxes_xywh [n,4] pixel xywh (float64 is kept), labels [n] (0-based), iscrowd [n] (0 / 1 or None), area [n] (the annotations'
@@ -301,160 +327,44 @@ class CocoGroundTruth(object):
         number and the evaluator's update reports the overflow."""
         if orig_wh is None:
             raise ValueError("CocoGroundTruth.set: orig_wh = (w, h) is required")
-        n = int(len(labels))
-        m = min(n, self.capacity)
-        head = np.array([int(orig_wh[0]), int(orig_wh[1]), int(image_id), n], np.int32)
         if isinstance(boxes_xywh, torch.Tensor) and boxes_xywh.is_cuda:
-            b = boxes_xywh.reshape(-1, 4)[:m].to(torch.float64)
-            self.boxes[:m].copy_(b)
-            self.area[:m].copy_(b[:, 2] * b[:, 3] if area is None else area[:m].to(torch.float64))
-            self.labels[:m].copy_(labels[:m].to(torch.int32))
-            if iscrowd is None:
-                self.iscrowd[:m].zero_()
-            else:
-                self.iscrowd[:m].copy_(iscrowd[:m].to(torch.uint8))
-            k, host = self._stage()
-            host[:16].copy_(torch.from_numpy(head.view(np.uint8)))
-            self._buf[:16].copy_(host[:16], non_blocking=True)
-            self._sent(k)
-            return self
-        k, host = self._stage()
-        h = host.numpy()
-        b = np.ascontiguousarray(np.asarray(boxes_xywh, np.float64).reshape(-1, 4)[:m])
-        ar = b[:, 2] * b[:, 3] if area is None else np.ascontiguousarray(np.asarray(area, np.float64).reshape(-1)[:m])
-        h[:16] = head.view(np.uint8)
-        h[16:16 + 32 * m] = b.view(np.uint8).reshape(-1)
-        h[self._o_area:self._o_area + 8 * m] = ar.view(np.uint8)
-        h[self._o_lab:self._o_lab + 4 * m] = np.ascontiguousarray(np.asarray(labels, np.int32)[:m]).view(np.uint8)
-        h[self._o_crowd:self._o_crowd + m] = 0 if iscrowd is None else (np.asarray(iscrowd)[:m] != 0).astype(np.uint8)
-        self._buf.copy_(host, non_blocking=True)
-        self._sent(k)
-        return self
+            boxes_xywh = boxes_xywh.reshape(-1, 4).to(torch.float64)
+        else:
+            boxes_xywh = np.asarray(boxes_xywh, np.float64).reshape(-1, 4)
+            iscrowd = None if iscrowd is None else np.asarray(iscrowd) != 0
+        if area is None:
+            area = boxes_xywh[:, 2] * boxes_xywh[:, 3]
+        return self._set((boxes_xywh, area, labels, iscrowd), int(len(labels)), orig_wh, image_id)
 
 
-class CocoDetectionEvaluator(object):
+class CocoDetectionEvaluator(_RecordStore):
     """COCOeval (bbox, useCats = 1) over a record store in HBM.  update() is one HIP launch on the current stream and has no host sync;
     summarize() runs the accumulate kernel, does the only device -> host copy and takes the 12 means with numpy as pycocotools does."""
+    _COLUMN, _FLAGS_WIDTH, _COUNTER, _OP = "rank", 4, ("npig", (4,)), ("coco_eval_update", _lib.OP_COCO_EVAL)
+    _GT, _CONFIG_WORDS = CocoGroundTruth, "classes, thresholds or maxDets"
 
     def __init__(self, num_classes, record_capacity=1 << 20, gt_capacity=128, device=None, iou_thresholds=None, max_dets=(1, 10, 100)):
         thr = np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True) if iou_thresholds is None \
             else np.array([float(t) for t in iou_thresholds], np.float64)
         md = tuple(int(v) for v in max_dets)
-        if not 2 <= int(num_classes) <= MAX_CLASSES:
-            raise ValueError("CocoDetectionEvaluator: num_classes %d outside 2 .. %d" % (num_classes, MAX_CLASSES))
-        if not 1 <= len(thr) <= MAX_THRESHOLDS:
-            raise ValueError("CocoDetectionEvaluator: %d IoU thresholds, 1 .. %d supported" % (len(thr), MAX_THRESHOLDS))
-        if not 1 <= int(gt_capacity) <= MAX_GT:
-            raise ValueError("CocoDetectionEvaluator: gt_capacity %d outside 1 .. %d" % (gt_capacity, MAX_GT))
-        if int(record_capacity) < 1:
-            raise ValueError("CocoDetectionEvaluator: record_capacity must be >= 1")
+        super().__init__(num_classes, thr, record_capacity, gt_capacity)
         if len(md) != 3 or list(md) != sorted(md) or md[0] < 1 or md[2] > COCO_MAX_DET:
             raise ValueError("CocoDetectionEvaluator: max_dets must be three ascending values in 1 .. %d" % COCO_MAX_DET)
-        dev = torch.device(device if device is not None else "cuda")
-        if dev.type != "cuda":
-            raise RuntimeError("CocoDetectionEvaluator runs only on a HIP device (no CPU fallback)")
-        self.device = dev
-        self.num_classes = int(num_classes)
-        self.iou_thresholds = tuple(float(t) for t in thr)
         self.max_dets = md
-        self.record_capacity = int(record_capacity)
-        self.gt_capacity = int(gt_capacity)
-        self.thresholds = torch.from_numpy(thr.copy()).to(dev)
+        self._allocate(device)
         self.rec_thresholds_host = np.linspace(.0, 1.00, int(np.round((1.00 - .0) / .01)) + 1, endpoint=True)
-        self.rec_thresholds = torch.from_numpy(self.rec_thresholds_host.copy()).to(dev)
-        cap = self.record_capacity
-        self.rec_score = torch.zeros(cap, dtype=torch.float32, device=dev)
-        self.rec_label = torch.zeros(cap, dtype=torch.int32, device=dev)
-        self.rec_image = torch.zeros(cap, dtype=torch.int32, device=dev)
-        self.rec_rank = torch.zeros(cap, dtype=torch.int32, device=dev)
-        self.rec_flags = torch.zeros((cap, 4), dtype=torch.int32, device=dev)     # per area range: 2 bits per threshold
-        self.npig = torch.zeros((self.num_classes - 1, 4), dtype=torch.int64, device=dev)
-        self.cursor = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.error = torch.zeros(1, dtype=torch.int32, device=dev)
-        self._ws = {}
+        self.rec_thresholds = torch.from_numpy(self.rec_thresholds_host.copy()).to(self.device)
 
-    # ---- per frame ----------------------------------------------------------------------------------------------------------
-    def _workspace(self, D, G):
-        """The update kernel's key segments: owned by this evaluator, so that a captured graph keeps a valid address."""
-        ws = self._ws.get((D, G))
-        if ws is None:
-            nb = _lib.workspace_bytes(_lib.OP_COCO_EVAL, D, G)
-            if nb == 0:
-                raise FrcnnError("coco_eval_update: detection capacity %d / ground-truth capacity %d outside the kernel's limits" % (D, G))
-            ws = torch.zeros(nb, dtype=torch.uint8, device=self.device)
-            self._ws[(D, G)] = ws
-        return ws
+    def _config(self):
+        return {"config": (self.iou_thresholds, self.num_classes, self.max_dets)}
 
     def update(self, dets, gt):
         """Scores one frame: dets = ops.Detections of the frame (rows in any order), gt = its CocoGroundTruth.  No sync; capturable
         into a graph with detect."""
-        if gt.capacity > self.gt_capacity:
-            raise ValueError("CocoDetectionEvaluator: CocoGroundTruth capacity %d > gt_capacity %d" % (gt.capacity, self.gt_capacity))
+        self._check_gt(gt)
         ops.coco_eval_update(dets, gt.boxes, gt.area, gt.labels, gt.iscrowd, gt.n, gt.frame, self.thresholds, self.num_classes, self.max_dets[-1],
                              self.npig, self.rec_score, self.rec_label, self.rec_image, self.rec_rank, self.rec_flags, self.cursor, self.error,
                              workspace=self._workspace(dets.labels.numel(), gt.capacity))
-
-    def reset(self):
-        self.cursor.zero_()
-        self.npig.zero_()
-        self.error.zero_()
-
-    # ---- per test set -------------------------------------------------------------------------------------------------------
-    _KEYS = ("score", "label", "image_id", "rank", "flags")
-
-    def _records(self):
-        return (self.rec_score, self.rec_label, self.rec_image, self.rec_rank, self.rec_flags)
-
-    def _config(self):
-        return (self.iou_thresholds, self.num_classes, self.max_dets)
-
-    def state(self):
-        """The evaluator's state as device tensors (one sync for the record count): the live records in slot order, npig, n_records
-        (what update counted: more than len(score) when the store overflowed) and the error word."""
-        n_all = int(self.cursor.item())
-        n = min(n_all, self.record_capacity)
-        s = dict(zip(self._KEYS, (r[:n].clone() for r in self._records())))
-        s.update(npig=self.npig.clone(), n_records=n_all, error=self.error.clone(), config=self._config())
-        return s
-
-    def merge(self, other):
-        """Appends the records of `other` (a CocoDetectionEvaluator, or a state() of one, of the same classes, thresholds and maxDets)
-        and adds its counters: evaluating shards separately and merging equals one evaluator over all of them."""
-        s = other.state() if isinstance(other, CocoDetectionEvaluator) else other
-        if s["config"] != self._config():
-            raise ValueError("CocoDetectionEvaluator.merge: the evaluators differ in classes, thresholds or maxDets")
-        n_all = int(self.cursor.item())
-        n = min(n_all, self.record_capacity)
-        m = min(int(s["score"].numel()), self.record_capacity - n)
-        for dst, key in zip(self._records(), self._KEYS):
-            dst[n:n + m].copy_(s[key][:m].to(self.device))
-        self.cursor += int(s["n_records"])                     # keeps counting past the capacity: summarize() reports the loss
-        self.npig += s["npig"].to(self.device)
-        self.error |= s["error"].to(self.device)
-        return self
-
-    def _sorted(self):
-        """(order, labels_sorted) on the device, no sync: the live slots first, in (label ascending, score descending, image_id
-        ascending, rank ascending); the slots past the cursor sort behind every class."""
-        cap = self.record_capacity
-        live = torch.arange(cap, device=self.device) < self.cursor
-        o1 = torch.sort((self.rec_image.to(torch.int64) << 32) | self.rec_rank.to(torch.int64), stable=True)[1]
-        lab = torch.where(live, self.rec_label, torch.full_like(self.rec_label, 0x7FFFFFFF))
-        key = ((lab.to(torch.int64) << 32) | _score_key(self.rec_score))[o1]
-        o2 = torch.sort(key, stable=True)[1]
-        order = o1[o2]
-        return order, lab[order].contiguous()
-
-    def _raise_on_error(self, err, n_all):
-        if err:
-            what = [w for b, w in ((_lib.EVAL_ERR_UPSTREAM_ABORT, "a frame's detection count was -1 (an aborted proposal scan upstream)"),
-                                   (_lib.EVAL_ERR_GT_OVERFLOW, "a frame had more ground truths than the CocoGroundTruth capacity"),
-                                   (_lib.EVAL_ERR_COUNT_RANGE, "a frame's detection count exceeded its capacity"),
-                                   (_lib.EVAL_ERR_LABEL_RANGE, "a label outside 0 .. num_classes - 2")) if err & b]
-            raise FrcnnError("CocoDetectionEvaluator: error word %d: %s" % (err, "; ".join(what)))
-        if n_all > self.record_capacity:
-            raise FrcnnError("CocoDetectionEvaluator: the record store is full: %d of %d records were dropped (record_capacity = %d)"
-                             % (n_all - self.record_capacity, n_all, self.record_capacity))
 
     def summarize(self):
         """{"stats": float64 [12] (COCOeval.stats: AP, AP50, AP75, APs, APm, APl, AR@maxDets[0], AR@maxDets[1], AR@maxDets[2], ARs, ARm,
@@ -473,17 +383,6 @@ class CocoDetectionEvaluator(object):
         rec = host[np_:np_ + nr].copy().view(np.float64).reshape(T, nc, 4, 3)
         return {"stats": coco_stats(prec, rec, np.array(self.iou_thresholds, np.float64)), "precision": prec, "recall": rec,
                 "npig": host[np_ + nr:np_ + nr + 4 * nc].reshape(nc, 4).copy(), "n_records": n_all}
-
-    def records_sorted(self):
-        """The records on the host in the order (label ascending, score descending, image_id ascending, rank ascending): score f32,
-        label i32, image_id i32, rank i32, flags u32 [n, 4] (per area range 2 bits per threshold: _lib.EVAL_TP / EVAL_FP /
-        EVAL_IGNORED).  For tests and for precision / recall curves."""
-        order, _ = self._sorted()
-        n_all, err = int(self.cursor.item()), int(self.error.item())
-        self._raise_on_error(err, n_all)
-        out = {k: r[order[:n_all]].cpu().numpy() for k, r in zip(self._KEYS, self._records())}
-        out["flags"] = out["flags"].view(np.uint32)
-        return out
 
 
 def coco_stats(precision, recall, iou_thresholds):

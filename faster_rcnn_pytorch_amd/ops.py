@@ -378,6 +378,34 @@ def detect_postprocess(head_cls, head_reg, rois, n_rois, threshold, nms_threshol
     return Detections(boxes, labels, scores, count, class_counts, prob, n_rois)
 
 
+def _eval_update_args(op, dets, n_gt, frame, thresholds, counter, rec_score, rec_label, rec_image, rec_order, rec_flags, flags_width,
+                      cursor, error_word):
+    """What eval_update and coco_eval_update check alike: the Detections' fields, n_gt, frame, thresholds, the counter = (name, tensor,
+    elements), the record columns -- rec_order = (name, tensor) is the protocol's fourth -- with rec_flags of flags_width words per record,
+    cursor and error_word, and that what the kernel reads or writes in place is contiguous.  Returns the checked tensors in this order."""
+    boxes = _req(dets.boxes, name="dets.boxes")
+    labels = _req(dets.labels, torch.int32, "dets.labels")
+    scores = _req(dets.scores, name="dets.scores")
+    count = _req(dets.count, torch.int32, "dets.count")
+    n_gt = _req(n_gt, torch.int32, "n_gt")
+    frame = _req(frame, torch.int32, "frame")
+    thresholds = _req(thresholds, torch.float64, "thresholds")
+    npos = _req(counter[1], torch.int64, counter[0])
+    cursor = _req(cursor, torch.int64, "cursor")
+    error_word = _req(error_word, torch.int32, "error_word")
+    recs = (_req(rec_score, name="rec_score"), _req(rec_label, torch.int32, "rec_label"), _req(rec_image, torch.int32, "rec_image"),
+            _req(rec_order[1], torch.int32, rec_order[0]), _req(rec_flags, torch.int32, "rec_flags"))
+    D, cap = labels.numel(), rec_score.numel()
+    if boxes.numel() != 4 * D or scores.numel() != D or frame.numel() != 3 or npos.numel() != counter[2] \
+            or any(r.numel() != cap for r in recs[:4]) or rec_flags.numel() != flags_width * cap or count.numel() < 1 or n_gt.numel() < 1:
+        raise ValueError("%s: shapes disagree" % op)
+    for t in (dets.boxes, dets.labels, dets.scores, dets.count, counter[1], cursor, error_word, rec_score, rec_label, rec_image, rec_order[1],
+              rec_flags):
+        if not t.is_contiguous():
+            raise ValueError("%s: the detections and the evaluator's buffers must be contiguous (they are written or read in place)" % op)
+    return boxes, labels, scores, count, n_gt, frame, thresholds, npos, recs, cursor, error_word
+
+
 def eval_update(dets, gt_boxes, gt_labels, gt_difficult, n_gt, frame, thresholds, num_classes, npos, rec_score, rec_label, rec_image,
                 rec_position, rec_flags, cursor, error_word, workspace=None):
     """One frame of the VOC AP protocol (evaluation/voc_eval.py:84-91, 46-56, 156-197) in one launch and no host sync: matches the live
@@ -388,28 +416,15 @@ def eval_update(dets, gt_boxes, gt_labels, gt_difficult, n_gt, frame, thresholds
     store: rec_score f32, rec_label / rec_image / rec_position i32, rec_flags i32 (bit pattern: 2 bits per threshold, _lib.EVAL_TP /
     EVAL_FP / EVAL_IGNORED), all [record_capacity]; cursor i64[1]; error_word i32[1] (_lib.EVAL_ERR_*); npos i64[C-1].  See
     include/frcnn_hip.h.  faster_rcnn_pytorch_amd.evaluation.DetectionEvaluator owns these buffers."""
-    boxes = _req(dets.boxes, name="dets.boxes")
-    labels = _req(dets.labels, torch.int32, "dets.labels")
-    scores = _req(dets.scores, name="dets.scores")
-    count = _req(dets.count, torch.int32, "dets.count")
     gt_boxes = _req(gt_boxes, name="gt_boxes")
     gt_labels = _req(gt_labels, torch.int32, "gt_labels")
     gt_difficult = _req(gt_difficult, torch.uint8, "gt_difficult")
-    n_gt = _req(n_gt, torch.int32, "n_gt")
-    frame = _req(frame, torch.int32, "frame")
-    thresholds = _req(thresholds, torch.float64, "thresholds")
-    npos = _req(npos, torch.int64, "npos")
-    cursor = _req(cursor, torch.int64, "cursor")
-    error_word = _req(error_word, torch.int32, "error_word")
-    recs = (_req(rec_score, name="rec_score"), _req(rec_label, torch.int32, "rec_label"), _req(rec_image, torch.int32, "rec_image"),
-            _req(rec_position, torch.int32, "rec_position"), _req(rec_flags, torch.int32, "rec_flags"))
+    boxes, labels, scores, count, n_gt, frame, thresholds, npos, recs, cursor, error_word = _eval_update_args(
+        "eval_update", dets, n_gt, frame, thresholds, ("npos", npos, num_classes - 1), rec_score, rec_label, rec_image,
+        ("rec_position", rec_position), rec_flags, 1, cursor, error_word)
     D, G, T, cap = labels.numel(), gt_labels.numel(), thresholds.numel(), rec_score.numel()
-    if boxes.numel() != 4 * D or scores.numel() != D or gt_boxes.numel() != 4 * G or gt_difficult.numel() != G or frame.numel() != 3 \
-            or npos.numel() != num_classes - 1 or any(r.numel() != cap for r in recs) or count.numel() < 1 or n_gt.numel() < 1:
+    if gt_boxes.numel() != 4 * G or gt_difficult.numel() != G:
         raise ValueError("eval_update: shapes disagree")
-    for t in (dets.boxes, dets.labels, dets.scores, dets.count, npos, cursor, error_word, rec_score, rec_label, rec_image, rec_position, rec_flags):
-        if not t.is_contiguous():
-            raise ValueError("eval_update: the detections and the evaluator's buffers must be contiguous (they are written or read in place)")
     dev = boxes.device
     nb = _lib.workspace_bytes(_lib.OP_EVAL, D, G)
     ws = workspace if workspace is not None else _ctrl_workspace(dev, "eval", max(nb, 1))
@@ -453,30 +468,16 @@ def coco_eval_update(dets, gt_boxes, gt_area, gt_labels, gt_iscrowd, n_gt, frame
     read when the kernel runs.  The record store: rec_score f32, rec_label / rec_image / rec_rank i32 [record_capacity], rec_flags i32
     [record_capacity, 4] (per area range 2 bits per threshold: _lib.EVAL_TP / EVAL_FP / EVAL_IGNORED); cursor i64[1]; error_word i32[1]
     (_lib.EVAL_ERR_*); npig i64[C-1, 4].  See include/frcnn_hip.h.  evaluation.CocoDetectionEvaluator owns these buffers."""
-    boxes = _req(dets.boxes, name="dets.boxes")
-    labels = _req(dets.labels, torch.int32, "dets.labels")
-    scores = _req(dets.scores, name="dets.scores")
-    count = _req(dets.count, torch.int32, "dets.count")
     gt_boxes = _req(gt_boxes, torch.float64, "gt_boxes")
     gt_area = _req(gt_area, torch.float64, "gt_area")
     gt_labels = _req(gt_labels, torch.int32, "gt_labels")
     gt_iscrowd = _req(gt_iscrowd, torch.uint8, "gt_iscrowd")
-    n_gt = _req(n_gt, torch.int32, "n_gt")
-    frame = _req(frame, torch.int32, "frame")
-    thresholds = _req(thresholds, torch.float64, "thresholds")
-    npig = _req(npig, torch.int64, "npig")
-    cursor = _req(cursor, torch.int64, "cursor")
-    error_word = _req(error_word, torch.int32, "error_word")
-    recs = (_req(rec_score, name="rec_score"), _req(rec_label, torch.int32, "rec_label"), _req(rec_image, torch.int32, "rec_image"),
-            _req(rec_rank, torch.int32, "rec_rank"), _req(rec_flags, torch.int32, "rec_flags"))
+    boxes, labels, scores, count, n_gt, frame, thresholds, npig, recs, cursor, error_word = _eval_update_args(
+        "coco_eval_update", dets, n_gt, frame, thresholds, ("npig", npig, 4 * (num_classes - 1)), rec_score, rec_label, rec_image,
+        ("rec_rank", rec_rank), rec_flags, 4, cursor, error_word)
     D, G, T, cap = labels.numel(), gt_labels.numel(), thresholds.numel(), rec_score.numel()
-    if boxes.numel() != 4 * D or scores.numel() != D or gt_boxes.numel() != 4 * G or gt_area.numel() != G or gt_iscrowd.numel() != G \
-            or frame.numel() != 3 or npig.numel() != 4 * (num_classes - 1) or any(r.numel() != cap for r in recs[:4]) \
-            or rec_flags.numel() != 4 * cap or count.numel() < 1 or n_gt.numel() < 1:
+    if gt_boxes.numel() != 4 * G or gt_area.numel() != G or gt_iscrowd.numel() != G:
         raise ValueError("coco_eval_update: shapes disagree")
-    for t in (dets.boxes, dets.labels, dets.scores, dets.count, npig, cursor, error_word, rec_score, rec_label, rec_image, rec_rank, rec_flags):
-        if not t.is_contiguous():
-            raise ValueError("coco_eval_update: the detections and the evaluator's buffers must be contiguous (they are written or read in place)")
     dev = boxes.device
     nb = _lib.workspace_bytes(_lib.OP_COCO_EVAL, D, G)
     ws = workspace if workspace is not None else _workspace(dev, nb)

@@ -252,3 +252,43 @@ def test_evaluator_refuses_bad_configuration_without_a_device(L):
     assert gt.n.tolist() == [3] and gt.frame.tolist() == [640, 480, 7]                  # n keeps the true count on overflow
     assert gt.boxes.tolist() == [[1, 2, 3, 4], [5, 6, 7, 8]] and gt.area.tolist() == [12, 56]
     assert gt.labels.tolist() == [0, 1] and gt.iscrowd.tolist() == [0, 1]
+
+
+# ------------------------------------------------------------------------------------------------------------ frame-buffer layout
+# what eval_update_kernel and coco_update_kernel read: a 16-byte head (w, h, image_id, n) and then the fields, each [capacity, width]
+LAYOUTS = {"GroundTruth": (("boxes", np.float32, 4), ("labels", np.int32, 1), ("difficult", np.uint8, 1)),
+           "CocoGroundTruth": (("boxes", np.float64, 4), ("area", np.float64, 1), ("labels", np.int32, 1), ("iscrowd", np.uint8, 1))}
+
+
+@pytest.mark.parametrize("c", [1, 3, 64])
+@pytest.mark.parametrize("cls", sorted(LAYOUTS))
+def test_frame_buffer_bytes_are_head_then_fields_in_table_order(L, cls, c):
+    """The raw bytes of the one allocation against a hand-packed expectation, for 0, c and c + 2 rows from host arrays: field k starts
+    at 16 + sum(itemsize * width of the fields before it) * c, n keeps the true count on overflow, the rows past min(n, c) stay as
+    they were (zero)."""
+    from faster_rcnn_pytorch_amd import evaluation
+    rng = np.random.RandomState(c)
+    for n in (0, c, c + 2):
+        cols = {"boxes": rng.randint(1, 4000, (n, 4)) / 8.0, "area": rng.randint(1, 10 ** 6, n) / 4.0, "labels": rng.randint(0, 90, n),
+                "difficult": rng.randint(0, 2, n), "iscrowd": rng.randint(0, 2, n)}
+        gt = getattr(evaluation, cls)(c, "cpu")
+        if cls == "GroundTruth":
+            gt.set(cols["boxes"], cols["labels"], cols["difficult"], (641 + n, 479), 70000 + n)
+        else:
+            gt.set(cols["boxes"], cols["labels"], cols["iscrowd"], cols["area"], orig_wh=(641 + n, 479), image_id=70000 + n)
+        m = min(n, c)
+        want = [np.array([641 + n, 479, 70000 + n, n], np.int32).view(np.uint8)]
+        for name, dt, w in LAYOUTS[cls]:
+            field = np.zeros((c, w), dt)
+            field[:m] = np.asarray(cols[name]).reshape(n, w)[:m]
+            want.append(field.view(np.uint8).reshape(-1))
+            view = getattr(gt, name)
+            assert tuple(view.shape) == ((c, w) if w > 1 else (c,)) and np.array_equal(view.numpy().reshape(c, w), field), name
+        want = np.concatenate(want)
+        raw = np.frombuffer(bytes(gt.frame.untyped_storage()), np.uint8)
+        assert raw.size == 16 + sum(np.dtype(dt).itemsize * w for _, dt, w in LAYOUTS[cls]) * c
+        assert np.array_equal(raw, want)
+        assert gt.n.tolist() == [n] and gt.frame.tolist() == [641 + n, 479, 70000 + n] and gt.capacity == c
+    if cls == "CocoGroundTruth":                                 # area = None is w * h of the box
+        gt = evaluation.CocoGroundTruth(c, "cpu").set(cols["boxes"], cols["labels"], orig_wh=(8, 8))
+        assert np.array_equal(gt.area.numpy(), (cols["boxes"][:, 2] * cols["boxes"][:, 3])[:c]) and gt.iscrowd.tolist() == [0] * c

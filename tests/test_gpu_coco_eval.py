@@ -303,3 +303,40 @@ def test_detect_graph_with_the_coco_evaluator_replayed_on_three_frames(vgg):
     for k in ("precision", "recall", "npig", "stats"):
         assert np.array_equal(rg[k], re_[k]), k
     _same_result(rg, r)
+
+
+# ------------------------------------------------------------------------------------------------------------ 6. scan boundaries
+RECORDS = (63, 64, 65, 255, 256, 257, 0)                        # per category: both sides of a wave and of the 256-thread chunk
+
+
+def _boundary_frames():
+    """Three frames (at most 100 detections of a category in each) whose categories end with RECORDS records; category 6 has ground
+    truths and no detection.  Detections are exact, shifted or unrelated copies of the ground truths, pixel multiples of 1/8."""
+    rng = np.random.RandomState(17)
+    frames = []
+    for i in range(3):
+        gx, gy = rng.randint(0, 300, 28) * 1.0, rng.randint(0, 300, 28) * 1.0
+        gwh = np.array([16, 24, 40, 64, 100, 120])[rng.randint(0, 6, (28, 2))] * 1.0
+        gtl = np.arange(28) % 7
+        px, dl = [], []
+        for k, total in enumerate(RECORDS):
+            mine = np.nonzero(gtl == k)[0]
+            for _ in range(total // 3 + (i < total % 3)):
+                g = mine[rng.randint(0, len(mine))]
+                s = rng.randint(-3, 4, 2) * gwh[g] / 8.0 * (rng.rand() < 0.6)        # a shift by eighths of the box, or none
+                if rng.rand() < 0.25:
+                    s = s + 450.0                                                    # far from every ground truth
+                px.append([gx[g] + s[0], gy[g] + s[1], gx[g] + s[0] + gwh[g, 0], gy[g] + s[1] + gwh[g, 1]])
+                dl.append(k)
+        frames.append(ref.one_frame(np.clip(px, 0, 1024), rng.randint(1, 50, len(dl)) / 50.0, np.stack([gx, gy, gwh[:, 0], gwh[:, 1]], 1),
+                                    iscrowd=rng.rand(28) < 0.1, labels=dl, gt_labels=gtl, w=1024, h=1024, image_id=5 + i))
+    return frames
+
+
+def test_accumulate_scan_at_wave_and_chunk_boundaries():
+    frames = _boundary_frames()
+    r = ref.run(frames, 8)
+    assert np.bincount(r["records"]["label"], minlength=7).tolist() == list(RECORDS) and (r["npig"][:, 0] > 0).all()
+    codes = (r["records"]["flags"][:, 0] & 3)
+    assert all(len(set(codes[r["records"]["label"] == k])) >= 2 for k in range(6))      # true and false positives in every segment
+    _check(frames, 8, r, det_capacity=512)

@@ -324,3 +324,33 @@ def test_detect_graph_without_an_evaluator_is_unchanged(vgg):
     for x, e in ((xa, ea), (xb, eb), (xa, ea)):
         r = dg(x).to_host()
         assert len(e[1]) > 0 and all(torch.equal(p, q) for p, q in zip(r, e))
+
+
+# ------------------------------------------------------------------------------------------------------------ 6. scan boundaries
+SEGMENTS = (0, 1, 63, 64, 65, 255, 256, 257, 513)               # records per class: both sides of a wave and of the 256-thread chunk
+
+
+def test_ap_scan_at_wave_and_chunk_boundaries():
+    """ops.eval_average_precision on hand-built sorted records, two thresholds, random TP / FP / IGNORED codes.  Class 1 (one record)
+    has npos = 0, class 3 (64 records) no true positive, class 0 no record at all.  tp / fp totals are the counts of the codes; AP
+    within npos_c * 2^-52 of the restatement, NaN exactly where npos = 0."""
+    _, ops = _mods()
+    rng = np.random.RandomState(3)
+    nc, n, cap = len(SEGMENTS), sum(SEGMENTS), sum(SEGMENTS) + 26
+    label = np.repeat(np.arange(nc), SEGMENTS).astype(np.int32)
+    codes = rng.choice([eval_ref.TP, eval_ref.FP, eval_ref.IGNORED], (n, 2), p=[0.35, 0.45, 0.2]).astype(np.uint32)
+    codes[label == 3] = rng.choice([eval_ref.FP, eval_ref.IGNORED], (64, 2))
+    flags = codes[:, 0] | codes[:, 1] << 2
+    tp = np.array([[((codes[:, t] == eval_ref.TP) & (label == c)).sum() for c in range(nc)] for t in range(2)])
+    fp = np.array([[((codes[:, t] == eval_ref.FP) & (label == c)).sum() for c in range(nc)] for t in range(2)])
+    npos = tp.max(0) + rng.randint(0, 4, nc)                     # recall <= 1
+    npos[0], npos[1], npos[3] = 3, 0, 5
+    assert tp[:, 3].sum() == 0 and (tp[:, 4:] > 0).all() and (fp[:, 4:] > 0).all()
+    dead = np.full(cap - n, 0x7FFFFFFF, np.int32)                # the slots past the cursor, as _sorted() leaves them
+    ap_d, tp_d, fp_d = ops.eval_average_precision(torch.from_numpy(np.concatenate([label, dead])).to(DEV),
+                                                  torch.from_numpy(np.concatenate([flags, dead.view(np.uint32)]).view(np.int32)).to(DEV),
+                                                  torch.tensor([n], dtype=torch.int64, device=DEV), torch.from_numpy(npos).to(DEV), 2, nc + 1)
+    assert np.array_equal(tp_d.cpu().numpy(), tp) and np.array_equal(fp_d.cpu().numpy(), fp)
+    ap_r, _ = eval_ref.average_precision({"flags": flags, "label": label}, npos, 2)
+    assert ap_r[0, 0] == 0.0 and ap_r[0, 3] == 0.0 and (ap_r[:, 4:] > 0).all()
+    _ap_within_bound(ap_d.cpu().numpy(), ap_r, npos)
