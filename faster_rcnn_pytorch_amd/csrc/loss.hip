@@ -1,7 +1,9 @@
 // loss.hip -- FRCNNLoss (losses/loss.py:5-85) as ONE streaming kernel whose last workgroup adds up the partial sums.
 //   RPN : CE(ignore -1) over [N,2] + SmoothL1(beta 1/9) over the positives, both / #(label >= 0)     (loss.py:20-40)
 //   head: CE over [R,C]            + SmoothL1(beta 1)   over the positives, both / R                   (loss.py:43-61)
-// A head class outside [0, C) (the failure mark of frcnn_head_targets) makes the head CE, hence the total, NaN.
+// A head class outside [0, C) (the failure mark of frcnn_head_targets; compared in 64 bits, so 2^32 + 3 is no class 3) makes the head CE,
+// hence the total, NaN; an RPN label above 1 (the reference's cross_entropy throws there) does the same to the RPN CE.  The class gradient
+// of such a row is the plain softmax (no one-hot is subtracted); its regression terms count as for any other label > 0.
 // The reference spends ~15 eager launches and two boolean-mask host syncs (loss.py:33,56) per forward and about as
 // many per backward.  Here one pass over the predictions produces the four sums AND the un-normalised gradients
 // (softmax - onehot, SmoothL1'), so backward is four scalar multiplies.  RPN rows: one lane per anchor, grid-stride over at
@@ -65,7 +67,7 @@ __global__ __launch_bounds__(256) void det_loss_kernel(const float2 *__restrict_
                 const float m = fmaxf(c.x, c.y);
                 const float e0 = expf(c.x - m), e1 = expf(c.y - m);
                 const float s = e0 + e1;
-                ce += m + logf(s) - (t == 0 ? c.x : c.y);
+                ce += t <= 1 ? m + logf(s) - (t == 0 ? c.x : c.y) : __builtin_nanf("");        // a label above 1 is no class of the RPN: NaN, as for the head
                 gc = make_float2(e0 / s - (t == 0 ? 1.f : 0.f), e1 / s - (t == 1 ? 1.f : 0.f));
                 ++valid;
             }
@@ -80,7 +82,8 @@ __global__ __launch_bounds__(256) void det_loss_kernel(const float2 *__restrict_
         const int nb_head = gridDim.x - nb_rpn;
         for (int r = ((int)blockIdx.x - nb_rpn) * 4 + w; r < R; r += nb_head * 4) {
             const float *row = head_cls + (size_t)r * NC;
-            const int t = (int)t_cls[r];
+            const int64_t t64 = t_cls[r];                              // compared in 64 bits: (int)(2^32 + 3) would pass for class 3
+            const int t = (t64 >= 0 && t64 < NC) ? (int)t64 : -1;
             float m = -__builtin_inff();
             for (int c = lane; c < NC; c += 64) m = fmaxf(m, row[c]);
             m = wave_max(m);
@@ -92,9 +95,9 @@ __global__ __launch_bounds__(256) void det_loss_kernel(const float2 *__restrict_
             if (lane == 0) {
                 // a class outside [0, NC) is the target maker's failure mark (targets.hip: upstream NMS abort, or fewer than R
                 // samples): the loss becomes NaN instead of reading out of bounds, so the failure shows at the caller's loss.item()
-                hce += (t >= 0 && t < NC) ? m + logf(s) - row[t] : __builtin_nanf("");
+                hce += t >= 0 ? m + logf(s) - row[t] : __builtin_nanf("");
                 float4 gr = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (t > 0) {
+                if (t64 > 0) {
                     const float4 p = head_reg[r], q = t_reg[r];
                     hsl += sl1(p.x, q.x, 1.f, &gr.x) + sl1(p.y, q.y, 1.f, &gr.y) + sl1(p.z, q.z, 1.f, &gr.z) + sl1(p.w, q.w, 1.f, &gr.w);
                 }

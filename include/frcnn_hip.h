@@ -401,9 +401,14 @@ int frcnn_ms_roi_align_bwd(const float *grad_out, float *const *grad_feats_host,
 /* ---- detection losses (losses/loss.py:5-85) ------------------------------------------------- */
 /* FRCNNLoss forward AND the un-normalised input gradients in one pass.  out7 (device): total, rpn_cls, rpn_reg,
  * head_cls, head_reg losses, then 1/#(rpn label >= 0) and 1/R (the scales backward multiplies the gradients by).
- * g_* have the shapes of the predictions.  workspace >= 32 KiB, DEDICATED to this entry point and ZERO before the first call:
- * its first word is the ticket by which the last workgroup to finish adds up the partial sums (one launch, no finalize kernel);
- * that workgroup leaves the ticket zero, so consecutive calls (and HIP-graph replays) need no clearing in between.            */
+ * g_* have the shapes of the predictions; every row is written (zeros for an ignored row), so their contents on entry
+ * do not matter.
+ * Labels that are no class: a head class outside [0, NC) (compared in 64 bits, so 2^32 + 3 is no class 3) and an RPN
+ * label above 1 are both the failure mark.  That part's CE term and the total become NaN (the reference's cross_entropy
+ * throws there); the row's class gradient is the plain softmax (finite, no one-hot subtracted); the row counts in
+ * #(rpn label >= 0), and its regression terms count as for any other label > 0 (the 64-bit label decides).
+ * workspace >= 32 KiB, DEDICATED to this entry point and ZERO before the first call: its first word is the ticket
+ * by which the last workgroup to finish adds up the partial sums (one launch, no finalize kernel); that workgroup leaves the ticket zero, so consecutive calls (and HIP-graph replays) need no clearing in between.            */
 int frcnn_detection_loss(const float *rpn_cls /*[N,2]*/, const float *rpn_reg /*[N,4]*/, const int64_t *t_rpn_cls /*[N]*/,
                          const float *t_rpn_reg /*[N,4]*/, int64_t N,
                          const float *head_cls /*[R,NC]*/, const float *head_reg /*[R,4]*/, const int64_t *t_cls /*[R]*/,
