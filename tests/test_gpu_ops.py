@@ -932,7 +932,7 @@ def test_ms_roi_align_fwd_bwd_vs_oracle(ops):
     out.backward(T(go))
     for l, f in enumerate(fts):
         gf_o = orc.roi_align_bwd(go, feats[l].shape, rois, 0.25 / (1 << l), 2, False, lv, l)
-        assert np.allclose(f.grad[0].cpu().numpy(), gf_o, rtol=1e-4, atol=1e-4)  # atomics: order-nondeterministic
+        assert np.allclose(f.grad[0].cpu().numpy(), gf_o, rtol=1e-4, atol=1e-4)  # another (fixed) fp32 order than the oracle's scatter; bit for bit: test_gpu_roi_align_exact.py
 
 
 @pytest.mark.parametrize("regime", ["proposal_like", "spread"])
