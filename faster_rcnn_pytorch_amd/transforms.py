@@ -17,6 +17,13 @@ Mosaic augmentation (config.py:16 --mosaic_transform), on the kernels of csrc/mo
   datasets/transforms_.py:150-178      crop_ incl. the hand-back of the uncropped frame when no box survives
   datasets/transforms_.py:278-288      RandomSizeCrop (DeviceMosaicStage.draw_regions: the same distribution, not the same stream)
   datasets/build.py:15-19              the ordinary transform the canvas then enters (DeviceMosaicStage.__call__)
+
+Photometric distortion and zoom-out (the richer recipe of datasets/build.py:28-42), on the kernels of csrc/photometric.hip:
+  datasets/transforms_.py:38-58, 240-247   photometric_distort_, RandomPhotoDistortion (draw_photometric, photometric_plan, photometric_distort)
+  datasets/transforms_.py:130-147, 291-299 zoom_out_, RandomZoomOut (draw_zoom_out, zoom_out)
+  DeviceAugmentStage: photometric, zoom-out, then the DeviceInputStage.  The coins (random.random() < p) stay with the caller.
+RandomSizeCrop alone (transforms_.py:278-288) has no device form: crop_ hands back the uncropped frame when no box survives, so the
+output SHAPE would depend on data in device memory and reading it would be a host synchronisation (docs/PARITY.md).
 """
 import collections
 import ctypes as C
@@ -220,3 +227,134 @@ class DeviceMosaicStage:
         x, b, meta = self.final(r.canvas_u8, r.boxes, flip)
         meta["fallback"] = r.fallback
         return x, b, r.labels, r.count, meta
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# photometric distortion and zoom-out
+# ---------------------------------------------------------------------------------------------------------------------------
+BRIGHTNESS, CONTRAST, SATURATION, HUE = 0, 1, 2, 3
+
+
+def photometric_plan(order, factors):
+    """The host side of photometric_distort_ (transforms_.py:50-57): order = the op ids in the order drawn (each of BRIGHTNESS, CONTRAST,
+    SATURATION, HUE at most once; fewer than four is allowed), factors = {op: factor} or a sequence indexed by op -> the int32[8] plan
+    frcnn_photometric reads: four (op, param) slots, -1 for an unused slot.  param: the factor rounded to binary32, as bits (Image.blend
+    takes a C float); for HUE the shift uint8(int32(factor * 255)): the product in binary64, truncated toward zero, mod 256."""
+    order = [int(op) for op in order]
+    if len(order) > 4 or len(set(order)) != len(order) or any(op < 0 or op > 3 for op in order):
+        raise ValueError("photometric_plan: order %s must name each of the ops 0..3 at most once" % (order,))
+    plan = np.full(8, -1, np.int32)
+    for k, op in enumerate(order):
+        f = float(factors[op])
+        if not math.isfinite(f):
+            raise ValueError("photometric_plan: factor %r of op %d is not finite" % (f, op))
+        plan[2 * k] = op
+        plan[2 * k + 1] = (int(f * 255.0) & 0xFF) if op == HUE else int(np.array(f, np.float32).view(np.int32))
+    return plan
+
+
+def draw_photometric(rng=random):
+    """photometric_distort_'s draws (transforms_.py:50-56): a shuffled order, uniform(0.5, 1.5) for brightness / contrast / saturation and
+    uniform(-18/255, 18/255) for hue, each drawn when its op comes up.  The reference's DISTRIBUTION, not its random stream (as
+    DeviceMosaicStage.draw_regions).  rng: anything with shuffle and uniform.  -> (order, factors) for photometric_plan."""
+    order = [BRIGHTNESS, CONTRAST, SATURATION, HUE]
+    rng.shuffle(order)
+    factors = {}
+    for op in order:
+        factors[op] = rng.uniform(-18 / 255., 18 / 255.) if op == HUE else rng.uniform(0.5, 1.5)
+    return order, factors
+
+
+def draw_zoom_out(h, w, max_scale=3, rng=random):
+    """zoom_out_'s draws (transforms_.py:134-140) for an h x w frame -> ((new_h, new_w), (top, left)).  The distribution, not the stream."""
+    scale = rng.uniform(1, max_scale)
+    new_h, new_w = int(scale * h), int(scale * w)
+    left = rng.randint(0, new_w - w)
+    top = rng.randint(0, new_h - h)
+    return (new_h, new_w), (top, left)
+
+
+def _frame(img, name="img"):
+    img = _req(img, torch.uint8, name)
+    if img.dim() != 3 or img.shape[2] != 3:
+        raise ValueError("%s must be [h, w, 3] uint8 (HWC RGB), got %s" % (name, tuple(img.shape)))
+    return img
+
+
+def photometric_distort(img, plan, out=None):
+    """photometric_distort_ for a uint8 HWC frame on the device -> a new uint8 HWC frame.  plan: photometric_plan's array (copied to the
+    device here), or an int32[8] DEVICE tensor, which the kernels read when they run: inside a captured graph pass a device tensor and
+    write the next draw into it between replays.  No host synchronisation, two launches whatever the plan says."""
+    img = _frame(img)
+    dev = img.device
+    if isinstance(plan, torch.Tensor):
+        plan = _req(plan, torch.int32, "plan")
+    else:
+        plan = torch.from_numpy(np.ascontiguousarray(plan, dtype=np.int32)).to(dev)
+    if plan.numel() != 8:
+        raise ValueError("plan must hold 8 int32 (four (op, param) slots), got %s" % (tuple(plan.shape),))
+    h, w = int(img.shape[0]), int(img.shape[1])
+    out = torch.empty_like(img) if out is None else _frame(out, "out")
+    if out.shape != img.shape:
+        raise ValueError("out must have the shape of img")
+    nb = int(lib.frcnn_photometric_workspace(h, w))
+    if nb == 0:
+        raise ValueError("photometric_distort: unsupported shape %d x %d (sides of 1 .. 32767)" % (h, w))
+    ws = _workspace(dev, nb)
+    with torch.cuda.device(dev):
+        check(lib.frcnn_photometric(_ptr(img), h, w, _ptr(plan), _ptr(out), _ptr(ws), nb, _stream()), "photometric_distort")
+    return out
+
+
+def zoom_out(img, boxes, new_hw, top_left):
+    """zoom_out_ for a uint8 HWC frame on the device: -> (canvas uint8 [new_h, new_w, 3] filled with the frame's per-channel median and
+    the frame pasted at (top, left); boxes + float32(left, top, left, top), or None for boxes=None).  new_hw and top_left are host
+    integers (draw_zoom_out); the histogram and the median never leave the device."""
+    img = _frame(img)
+    dev = img.device
+    h, w = int(img.shape[0]), int(img.shape[1])
+    (new_h, new_w), (top, left) = (int(v) for v in new_hw), (int(v) for v in top_left)
+    n = 0
+    boxes_out = None
+    if boxes is not None:
+        boxes = _req(boxes, torch.float32, "boxes").reshape(-1, 4)
+        n = int(boxes.shape[0])
+        boxes_out = torch.empty_like(boxes)
+    nb = int(lib.frcnn_zoom_out_workspace(h, w, new_h, new_w))
+    if nb == 0:
+        raise ValueError("zoom_out: unsupported shapes %d x %d -> %d x %d (sides of 1 .. 32767, the canvas no smaller than the frame)"
+                         % (h, w, new_h, new_w))
+    canvas = torch.empty((new_h, new_w, 3), dtype=torch.uint8, device=dev)
+    ws = _workspace(dev, nb)
+    with torch.cuda.device(dev):
+        check(lib.frcnn_zoom_out(_ptr(img), h, w, new_h, new_w, top, left, _ptr(boxes) if n else None, n, _ptr(canvas),
+                                 _ptr(boxes_out) if n else None, _ptr(ws), nb, _stream()), "zoom_out")
+    return canvas, boxes_out
+
+
+class DeviceAugmentStage:
+    """The richer recipe's per-frame chain on the device: [photometric_distort_] -> [zoom_out_] -> DeviceInputStage (flip, resize,
+    ToTensor, Normalize, pad).  The reference's recipe (datasets/build.py:28-42) flips BEFORE it zooms out; here the flip is the input
+    stage's, behind the zoom-out.  `left` is uniform over its range, and flipping a pasted canvas mirrors the paste position to
+    new_w - w - left, which is uniform over the same range: the distribution of results is the same, only the stream of draws is not.
+
+    stage(img_u8_hwc, boxes=None, plan=None, zoom=None, flip=False) -> what DeviceInputStage returns, for the augmented frame.
+    plan: None (no photometric distortion), photometric_plan's array or a device int32[8] tensor.  zoom: None or draw_zoom_out's
+    ((new_h, new_w), (top, left)).  The coins of RandomPhotoDistortion / RandomZoomOut / RandomHorizontalFlip are the caller's."""
+
+    def __init__(self, size=800, max_size=1333, mean=IMAGENET_MEAN, std=IMAGENET_STD, size_divisible=32, max_scale=3):
+        self.final = DeviceInputStage(size, max_size, mean, std, size_divisible)
+        self.max_scale = max_scale
+
+    def draw(self, h, w, p_photometric=0.5, p_zoom=0.5, p_flip=0.5, rng=random):
+        """The recipe's coins and draws for an h x w frame -> (plan or None, zoom or None, flip)."""
+        plan = photometric_plan(*draw_photometric(rng)) if rng.random() < p_photometric else None
+        zoom = draw_zoom_out(h, w, self.max_scale, rng) if rng.random() < p_zoom else None
+        return plan, zoom, rng.random() < p_flip
+
+    def __call__(self, img, boxes=None, plan=None, zoom=None, flip=False):
+        if plan is not None:
+            img = photometric_distort(img, plan)
+        if zoom is not None:
+            img, boxes = zoom_out(img, boxes, zoom[0], zoom[1])
+        return self.final(img, boxes, flip)

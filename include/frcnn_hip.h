@@ -555,6 +555,41 @@ int frcnn_mosaic(const uint8_t *const src_hwc[4], const int32_t *src_hw, int siz
                  const float *boxes, const int64_t *labels, const int32_t *tile_offsets, uint8_t *canvas, float *boxes_out,
                  int64_t *labels_out, int32_t *count_dev, uint8_t *fallback_dev, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- photometric distortion and zoom-out (the richer training recipe, datasets/build.py:28-42) ---------------------------------
+ * frcnn_photometric replaces photometric_distort_ (datasets/transforms_.py:38-58; RandomPhotoDistortion :240-247, whose coin and draws
+ * stay with the caller) for one uint8 HWC RGB frame in HBM: [h, w, 3] -> [h, w, 3].  Bit-identical to Pillow 12.2 for the calls
+ * torchvision's PIL backend makes:
+ *   blend(a, b, alpha)  Image.blend: alpha binary32, t = a + alpha * (b - a) rounded after each operation; alpha in [0, 1]: (uint8) t,
+ *                       otherwise 0 for t <= 0, 255 for t >= 255, else (uint8) t.  a = the degenerate byte, b = the image byte
+ *   brightness (op 0)   a = 0                         saturation (op 2)   a = the pixel's L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16
+ *   contrast   (op 1)   a = int(sum(L) / count + 0.5) in binary64 over the image AS IT STANDS when contrast is applied (exact 64-bit sum)
+ *   hue        (op 3)   convert("HSV"), H += shift mod 256, convert("RGB") in Pillow's mixed binary32 / binary64 arithmetic; a shift of
+ *                       0 still goes through both conversions and is not the identity
+ * plan_dev: int32[8] in DEVICE memory, read by the kernels (a captured graph sees what the buffer holds at each replay): four slots
+ * (op, param) applied in order, every op on the uint8 result of the one before.  param: the binary32 bits of alpha (ops 0-2), the hue
+ * shift 0..255 (op 3: uint8(int32(factor * 255)), the product in binary64, truncated toward zero).  A slot whose op is outside 0..3
+ * is skipped; so is an op from its second appearance on.  No host synchronisation and two launches whatever the plan says.
+ * out must not overlap src.  src, out 4-byte aligned.  workspace: frcnn_photometric_workspace(h, w) bytes (0 for shapes it refuses),
+ * 8-byte aligned, any content: nothing of an earlier call is read.
+ * FRCNN_ERR_INVALID_ARG, before anything is launched: a NULL pointer, a side outside 1 .. 32767, a misaligned pointer, out overlapping
+ * src.  FRCNN_ERR_WORKSPACE: a short workspace.  */
+size_t frcnn_photometric_workspace(int h, int w);
+int frcnn_photometric(const uint8_t *src_hwc, int h, int w, const int32_t *plan_dev, uint8_t *out_hwc, void *workspace,
+                      size_t workspace_bytes, void *stream);
+/* frcnn_zoom_out replaces zoom_out_ (datasets/transforms_.py:130-147; RandomZoomOut :291-299, whose coin and draws stay with the
+ * caller): a [new_h, new_w, 3] canvas filled with the frame's per-channel MEDIAN (the reference's `mean_color` is
+ * ImageStat.Stat(image)._getmedian(): the first level whose cumulative count exceeds count / 2), the frame pasted at (left, top), boxes
+ * + float32(left, top, left, top).  new_h = int(scale * h), new_w = int(scale * w), top and left are the CALLER's host integers: shapes
+ * stay host-known.  The histogram and the median stay on the device: three launches (kernels only), capturable.  n = 0 is legal
+ * (boxes and boxes_out may then be NULL).  src, canvas 4-byte aligned and not overlapping; boxes, boxes_out 16-byte aligned.
+ * workspace: frcnn_zoom_out_workspace(h, w, new_h, new_w) bytes (0 for shapes it refuses), 4-byte aligned, any content.
+ * FRCNN_ERR_INVALID_ARG, before anything is launched: a NULL pointer, n < 0, a side of the frame or the canvas outside 1 .. 32767, a
+ * canvas smaller than the frame, top outside 0 .. new_h - h or left outside 0 .. new_w - w, a misaligned pointer, the canvas
+ * overlapping src.  FRCNN_ERR_WORKSPACE: a short workspace.  */
+size_t frcnn_zoom_out_workspace(int h, int w, int new_h, int new_w);
+int frcnn_zoom_out(const uint8_t *src_hwc, int h, int w, int new_h, int new_w, int top, int left, const float *boxes /*[n,4] xyxy*/, int64_t n,
+                   uint8_t *canvas, float *boxes_out, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- in-library kernel timing (HIP events on the launch stream) -------------------------------------- */
 /* When enabled, every kernel launch made by this library is bracketed by two hipEventRecord on the
  * caller's stream.  frcnn_prof_collect() synchronises those events (call it after the stream is idle)
