@@ -97,6 +97,8 @@ SIGNATURES = {
     "frcnn_photometric": (_i, [_vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "frcnn_zoom_out_workspace": (_sz, [_i, _i, _i, _i]),
     "frcnn_zoom_out": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "frcnn_resize_crop_workspace": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "frcnn_resize_crop": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "frcnn_diag_occupy": (_i, [_i, _i, _vp]),
     "frcnn_prof_enable": (_i, [_i]),
     "frcnn_prof_collect": (_i, []),

@@ -22,8 +22,14 @@ Photometric distortion and zoom-out (the richer recipe of datasets/build.py:28-4
   datasets/transforms_.py:38-58, 240-247   photometric_distort_, RandomPhotoDistortion (draw_photometric, photometric_plan, photometric_distort)
   datasets/transforms_.py:130-147, 291-299 zoom_out_, RandomZoomOut (draw_zoom_out, zoom_out)
   DeviceAugmentStage: photometric, zoom-out, then the DeviceInputStage.  The coins (random.random() < p) stay with the caller.
-RandomSizeCrop alone (transforms_.py:278-288) has no device form: crop_ hands back the uncropped frame when no box survives, so the
+transforms_.py's RandomSizeCrop alone (:278-288) has no device form: crop_ hands back the uncropped frame when no box survives, so the
 output SHAPE would depend on data in device memory and reading it would be a host synchronisation (docs/PARITY.md).
+
+Crop and the multi-scale crop recipe (sketched in datasets/build.py:27-39) of the WIRED pipeline, on the kernels of csrc/crop.hip:
+  new_datasets/transforms.py:16-56     crop: always crops, drops boxes that lose a side (crop; a device count behind fixed-capacity lists)
+  new_datasets/transforms.py:162-192   RandomCrop, RandomSizeCrop, CenterCrop (draw_random_crop, draw_random_size_crop, center_crop_region)
+  new_datasets/transforms.py:205-239   RandomResize, RandomSelect (DeviceMultiScaleStage.draw)
+Not built: pad / RandomPad (:135-145, 216-223; no recipe uses them) and everything about masks.
 """
 import collections
 import ctypes as C
@@ -358,3 +364,136 @@ class DeviceAugmentStage:
         if zoom is not None:
             img, boxes = zoom_out(img, boxes, zoom[0], zoom[1])
         return self.final(img, boxes, flip)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# crop and the multi-scale crop recipe (new_datasets/transforms.py)
+# ---------------------------------------------------------------------------------------------------------------------------
+class CropResult(collections.namedtuple("CropResult", "img_u8 boxes labels area iscrowd count")):
+    """img_u8 uint8 [ch, cw, 3]; boxes float32 [n, 4], labels int64 [n], area float32 [n] and iscrowd int64 [n] (None when none was
+    given) with the first `count` rows live, in input order, and zeros behind them; count int32 [1] on the device."""
+    __slots__ = ()
+
+    def to_host(self):
+        """What the reference's crop returns: (uint8 array, boxes[:count], labels[:count], area[:count], iscrowd[:count] or None).
+        Synchronises."""
+        n = int(self.count.item())
+        return (self.img_u8.cpu().numpy(), self.boxes[:n].cpu().numpy(), self.labels[:n].cpu().numpy(), self.area[:n].cpu().numpy(),
+                None if self.iscrowd is None else self.iscrowd[:n].cpu().numpy())
+
+
+def crop(img, boxes, labels, region, resize_hw=None, area=None, iscrowd=None, count=None):
+    """resize(img, resize_hw) followed by crop(region) (new_datasets/transforms.py:76-132, 16-56) for a uint8 HWC frame on the device,
+    without a host read-back -> CropResult.  resize_hw = (H1, W1), None for a plain crop; region = (i, j, h, w) host integers inside the
+    resized frame.  boxes float32 [n, 4] pixel xyxy of the SOURCE frame, labels int64 [n], iscrowd int64 [n] or None.  area is accepted
+    because the reference's target carries one, and never read: crop replaces every area by that of the clipped box (:33-35).  count:
+    None, or a device int32 tensor whose first element says how many leading rows are live (a list an earlier device stage compacted).
+    Only the image region is computed; fixed shapes and a device count, so the call can be captured into a graph."""
+    img = _frame(img)
+    dev = img.device
+    h, w = int(img.shape[0]), int(img.shape[1])
+    H1, W1 = (h, w) if resize_hw is None else (int(resize_hw[0]), int(resize_hw[1]))
+    i, j, ch, cw = (int(v) for v in region)
+    boxes = _req(boxes, torch.float32, "boxes").reshape(-1, 4)
+    labels = _req(labels, torch.int64, "labels").reshape(-1)
+    n = int(boxes.shape[0])
+    if iscrowd is not None:
+        iscrowd = _req(iscrowd, torch.int64, "iscrowd").reshape(-1)
+    for name, t in (("labels", labels), ("area", area), ("iscrowd", iscrowd)):
+        if t is not None and int(t.numel()) != n:
+            raise ValueError("%s has %d rows, boxes has %d" % (name, int(t.numel()), n))
+    if count is not None:
+        count = _req(count, torch.int32, "count")
+        if count.numel() < 1:
+            raise ValueError("count must hold one int32")
+    nb = int(lib.frcnn_resize_crop_workspace(h, w, H1, W1, ch, cw)) or 256           # 0: shapes the call itself refuses, and says why
+    out = torch.empty((max(ch, 0), max(cw, 0), 3), dtype=torch.uint8, device=dev)
+    boxes_out, labels_out = torch.empty_like(boxes), torch.empty_like(labels)
+    area_out = torch.empty(n, dtype=torch.float32, device=dev)
+    iscrowd_out = None if iscrowd is None else torch.empty_like(iscrowd)
+    count_out = torch.empty(1, dtype=torch.int32, device=dev)
+    ws = _workspace(dev, nb)
+    with torch.cuda.device(dev):
+        check(lib.frcnn_resize_crop(_ptr(img), h, w, H1, W1, i, j, ch, cw, _ptr(boxes), _ptr(labels), _ptr(iscrowd), n, _ptr(count), _ptr(out),
+                                    _ptr(boxes_out), _ptr(labels_out), _ptr(area_out), _ptr(iscrowd_out), _ptr(count_out), _ptr(ws), nb,
+                                    _stream()), "crop")
+    return CropResult(out, boxes_out, labels_out, area_out, iscrowd_out, count_out)
+
+
+def draw_random_crop(h, w, size, rng=random):
+    """RandomCrop(size) (transforms.py:162-168) on an h x w frame: torchvision's get_params -- the whole frame when the sizes are equal,
+    else the corner uniform over the positions that fit -> (i, j, th, tw).  The reference's DISTRIBUTION, not its random stream
+    (get_params draws from torch's generator).  size = (th, tw); rng: anything with randint(a, b), both ends included."""
+    th, tw = int(size[0]), int(size[1])
+    if th > h or tw > w:
+        raise ValueError("a %d x %d crop does not fit a %d x %d frame" % (th, tw, h, w))
+    if (h, w) == (th, tw):
+        return 0, 0, h, w
+    return rng.randint(0, h - th), rng.randint(0, w - tw), th, tw
+
+
+def draw_random_size_crop(h, w, min_size, max_size, rng=random):
+    """RandomSizeCrop(min_size, max_size) (transforms.py:176-180) on an h x w frame: w in [min_size, min(w, max_size)], then h likewise,
+    then RandomCrop's corner -> (i, j, ch, cw).  The distribution, not the stream."""
+    if min(h, w, max_size) < min_size:
+        raise ValueError("a %d x %d frame is smaller than min_size %d" % (h, w, min_size))
+    cw = rng.randint(min_size, min(w, max_size))
+    ch = rng.randint(min_size, min(h, max_size))
+    return draw_random_crop(h, w, (ch, cw), rng)
+
+
+def center_crop_region(h, w, size):
+    """CenterCrop(size) (transforms.py:187-192): size = (crop_h, crop_w); Python's round (half to even) -> (top, left, crop_h, crop_w)."""
+    crop_h, crop_w = int(size[0]), int(size[1])
+    return int(round((h - crop_h) / 2.)), int(round((w - crop_w) / 2.)), crop_h, crop_w
+
+
+MultiScalePlan = collections.namedtuple("MultiScalePlan", "flip resize_hw region size")
+MultiScalePlan.__doc__ = """flip: the flip coin.  resize_hw, region: None on the plain branch; on the crop branch the (H1, W1) of the
+first resize and the (i, j, ch, cw) cropped from it.  size: the scale of the final resize."""
+
+
+class DeviceMultiScaleStage:
+    """The multi-scale recipe of the wired pipeline (sketched in datasets/build.py:27-39), on the device:
+
+        RandomHorizontalFlip, RandomSelect(RandomResize(scales, max_size),
+                                           Compose([RandomResize(crop_sizes), RandomSizeCrop(crop_min, crop_max), RandomResize(scales, max_size)]), p),
+        ToTensor, Normalize, the pad-to-size_divisible collate
+
+    draw(h, w, rng) -> MultiScalePlan.  stage(img, boxes, labels, plan, area=None, iscrowd=None) -> (x [1, 3, PH, PW] float32, normalised
+    boxes [n, 4], labels [n], count int32 [1] on the device, meta).  Rows at and above count are padding, as in DeviceMosaicStage (the
+    plain branch keeps every row: count = n).  meta also carries 'area' and 'iscrowd': the crop's on the crop branch, the given ones on the
+    plain branch -- in pixels of the frame that enters the final resize (the input stage has no area path; the detector reads neither).
+    The recipe flips FIRST; here the flip is the input stage's, behind the crop (as DeviceAugmentStage does for the zoom-out).  The crop's
+    corner is uniform over its range and mirroring maps that range onto itself, so the distribution of what is cut out is the same; the
+    stream of draws is not, and flipping after the first resize is not the same BYTES as resizing the flipped frame (the resampler's
+    22-bit coefficients are not mirror-symmetric to the last bit; neither is the boxes' rounding).  What is pinned is the chain in the
+    order run here: resize, crop, hflip, resize, ToTensor, Normalize."""
+
+    def __init__(self, scales, max_size=1333, crop_sizes=(400, 500, 600), crop_min=384, crop_max=600, p=0.5, mean=IMAGENET_MEAN,
+                 std=IMAGENET_STD, size_divisible=32):
+        self.scales, self.max_size, self.crop_sizes = [int(s) for s in scales], max_size, [int(s) for s in crop_sizes]
+        self.crop_min, self.crop_max, self.p = int(crop_min), int(crop_max), float(p)
+        self.mean, self.std, self.size_divisible = tuple(mean), tuple(std), size_divisible
+
+    def draw(self, h, w, rng=random, p_flip=0.5):
+        """The recipe's coins and draws for an h x w frame, in the recipe's order (the flip coin, RandomSelect's coin, then the branch's own
+        draws).  rng: anything with random, choice and randint."""
+        flip = rng.random() < p_flip
+        if rng.random() < self.p:
+            return MultiScalePlan(flip, None, None, rng.choice(self.scales))
+        hw1 = get_size((w, h), rng.choice(self.crop_sizes), None)
+        region = draw_random_size_crop(hw1[0], hw1[1], self.crop_min, self.crop_max, rng)
+        return MultiScalePlan(flip, hw1, region, rng.choice(self.scales))
+
+    def __call__(self, img, boxes, labels, plan, area=None, iscrowd=None):
+        final = DeviceInputStage(plan.size, self.max_size, self.mean, self.std, self.size_divisible)
+        boxes = _req(boxes, torch.float32, "boxes").reshape(-1, 4)
+        if plan.region is None:
+            count = torch.full((1,), int(boxes.shape[0]), dtype=torch.int32, device=boxes.device)
+        else:
+            r = crop(img, boxes, labels, plan.region, plan.resize_hw, area, iscrowd)
+            img, boxes, labels, area, iscrowd, count = r
+        x, b, meta = final(img, boxes, plan.flip)
+        meta["area"], meta["iscrowd"] = area, iscrowd
+        return x, b, labels, count, meta

@@ -590,6 +590,33 @@ size_t frcnn_zoom_out_workspace(int h, int w, int new_h, int new_w);
 int frcnn_zoom_out(const uint8_t *src_hwc, int h, int w, int new_h, int new_w, int top, int left, const float *boxes /*[n,4] xyxy*/, int64_t n,
                    uint8_t *canvas, float *boxes_out, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- crop, with the resize in front of it (the multi-scale recipe sketched in datasets/build.py:27-39) -----------------------------
+ * frcnn_resize_crop replaces resize (new_datasets/transforms.py:76-132) followed by crop (:16-56; the region is the CALLER's: RandomCrop
+ * :162-168, RandomSizeCrop :171-180 and CenterCrop :183-192 only choose it) for one uint8 HWC RGB frame in HBM:
+ *   image  Pillow's 8-bit bilinear resize to H1 x W1 (horizontal pass, uint8, vertical pass), of which only the region (i, j, ch, cw) is
+ *          computed -> out_hwc [ch, cw, 3], the bytes of F.resize then F.crop on a PIL image.  (H1, W1) == (h, w): a plain crop, a byte
+ *          copy of the region (Pillow returns a copy for an equal size).
+ *   boxes  [n, 4] pixel xyxy of the SOURCE frame: * float32(W1/w, H1/h) (the ratios formed in double, :111-117), - (j, i, j, i), min with
+ *          (cw, ch) (NaN propagates), clamp at 0 (NaN stays) (:29-32); area_out = (x2 - x1) * (y2 - y1) (:33); a row is kept when
+ *          x2 > x1 and y2 > y1 (:48-49: a NaN box is dropped).  boxes / labels / area / iscrowd of the kept rows are compacted in input
+ *          order into boxes_out [n, 4], labels_out [n], area_out [n], iscrowd_out [n], zeros behind them; *count_dev = their number.
+ *          There is no area INPUT: crop replaces every area by that of the clipped box, so the product resize forms (:122) is never
+ *          seen.  area_out may be NULL; iscrowd and iscrowd_out are given together or not at all.
+ *   count_in_dev  NULL, or a device int32: only the first min(max(*count_in_dev, 0), n) rows are live (a list that an earlier device
+ *          stage compacted); the rows behind them are ignored.
+ * Binary32 throughout, operation for operation.  This crop always crops (datasets/transforms_.py:crop_, which may hand back the uncropped
+ * frame, is frcnn_mosaic's), so every shape is the host's.  No host synchronisation; four launches (two for a plain crop), whatever the
+ * boxes say; capturable.  n = 0 is legal (the list pointers may then be NULL).  boxes, boxes_out 16-byte aligned; no output overlaps
+ * its input.  workspace: frcnn_resize_crop_workspace(h, w, H1, W1, ch, cw) bytes (0 for shapes it refuses), 4-byte aligned, any content.
+ * FRCNN_ERR_INVALID_ARG, before anything is launched: n < 0; a NULL pointer; a side of the frame or the resized frame outside
+ * 1 .. 32767; ch < 1 or cw < 1; a region that is not inside the resized frame (PIL would pad it with black; no recipe of the reference
+ * draws one); a misaligned or overlapping list.  FRCNN_ERR_WORKSPACE: a short workspace.  */
+size_t frcnn_resize_crop_workspace(int h, int w, int H1, int W1, int ch, int cw);
+int frcnn_resize_crop(const uint8_t *src_hwc, int h, int w, int H1, int W1, int i, int j, int ch, int cw, const float *boxes,
+                      const int64_t *labels, const int64_t *iscrowd, int64_t n, const int32_t *count_in_dev, uint8_t *out_hwc,
+                      float *boxes_out, int64_t *labels_out, float *area_out, int64_t *iscrowd_out, int32_t *count_dev,
+                      void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- in-library kernel timing (HIP events on the launch stream) -------------------------------------- */
 /* When enabled, every kernel launch made by this library is bracketed by two hipEventRecord on the
  * caller's stream.  frcnn_prof_collect() synchronises those events (call it after the stream is idle)
