@@ -17,8 +17,12 @@ OP_TOPK, OP_NMS, OP_REGION_PROPOSAL, OP_RPN_TARGETS, OP_HEAD_TARGETS, OP_PREPROC
 OP_DETECT = 11
 OP_EVAL = 12
 OP_COCO_EVAL = 13
+OP_EVAL_MERGE = 14
 EVAL_TP, EVAL_FP, EVAL_IGNORED = 1, 2, 3                     # a record's flags: 2 bits per threshold
 EVAL_ERR_UPSTREAM_ABORT, EVAL_ERR_GT_OVERFLOW, EVAL_ERR_COUNT_RANGE, EVAL_ERR_LABEL_RANGE = 1, 2, 4, 8
+EVAL_ERR_LEDGER_OVERFLOW = 16
+EVAL_ERR_SHARD_TRUNCATED = 32
+EVAL_MERGE_MAX_SHARDS = 64
 
 _vp, _i, _i64, _f, _u64, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_uint64, C.c_size_t
 
@@ -89,6 +93,8 @@ SIGNATURES = {
     "frcnn_coco_eval_update": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
                                      _vp, _vp, _vp, _sz, _vp]),
     "frcnn_coco_eval_accumulate": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "frcnn_eval_ledger_append": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "frcnn_eval_merge": (_i, [_i, _i64, _i64, _i, _i64] + [_vp] * 11 + [_vp] * 5 + [_i64] + [_vp] * 3 + [_i64] + [_vp] * 6 + [_vp, _sz, _vp]),
     "frcnn_preprocess_image": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "frcnn_preprocess_boxes": (_i, [_vp, _i64, _i, _i, _i, _i, _i, _vp, _vp]),
     "frcnn_mosaic_workspace": (_sz, [_vp, _i, _i]),

@@ -10,6 +10,8 @@
 #define EVAL_ERR_GT_OVERFLOW 2         // n_gt > the ground-truth capacity
 #define EVAL_ERR_COUNT_RANGE 4         // count > the detection capacity
 #define EVAL_ERR_LABEL_RANGE 8         // a label outside 0 .. C-2
+#define EVAL_ERR_LEDGER_OVERFLOW 16    // more frames than the image ledger holds (eval_merge.hip)
+#define EVAL_ERR_SHARD_TRUNCATED 32    // a merged shard counted more records or ledger rows than its buffer holds (eval_merge.hip)
 
 #define EVAL_MAX_P 2048                // RoI rows per frame: a detection capacity is at most (C-1) * EVAL_MAX_P
 #define EVAL_MAX_C 256

@@ -28,7 +28,21 @@ summarize, i.e. pycocotools' COCOeval for iouType "bbox" with useCats = 1) -- ru
 The evaluator takes the xyxy boxes of detect; the reference also passes predict's boxes through cxcy_to_xy (test.py:68), which is the
 caller's business.  Restated from the published algorithm and NOT pinned to pycocotools' own code, which is not available to this
 project's tests (docs/PARITY.md); tests/test_coco_crosscheck.py compares with it wherever it can be imported.
-Not built: the segm and keypoints IoU types, useCats = 0."""
+Not built: the segm and keypoints IoU types, useCats = 0.
+
+On N GPUs (the reference's test loop is distributed: test.py:60-128, evaluation/coco_eval.py:46-49, 161-190) every rank evaluates its shard
+with an evaluator built with image_capacity > 0, which keeps one ledger row per frame (image_id, the frame's record slots, its share of
+the counter), and then calls
+
+    ev.synchronize_between_processes()                # all ranks; afterwards every rank holds the merged store
+    res = ev.summarize()
+
+The merge keeps the FIRST occurrence of every image_id in (rank, order of update) -- the reference's np.unique(..., return_index=True) --,
+so the images a DistributedSampler evaluates twice to pad the shards count once.  merge_shards(states) is the same merge without the
+collective; both run in HIP (csrc/eval_merge.hip).  For the VOC protocol this is the project's extension: the reference evaluates VOC
+on rank 0 only."""
+import zlib
+
 import numpy as np
 import torch
 
@@ -140,7 +154,7 @@ class _RecordStore(object):
     _GT = None                          # the frame-buffer class update() takes
     _CONFIG_WORDS = None                # what merge() says two evaluators may differ in
 
-    def __init__(self, num_classes, thr, record_capacity, gt_capacity):
+    def __init__(self, num_classes, thr, record_capacity, gt_capacity, image_capacity=0):
         """Validates and keeps the configuration; _allocate(device) follows once the subclass has checked its own extras."""
         name = type(self).__name__
         if not 2 <= int(num_classes) <= MAX_CLASSES:
@@ -155,6 +169,9 @@ class _RecordStore(object):
         self.iou_thresholds = tuple(float(t) for t in thr)
         self.record_capacity = int(record_capacity)
         self.gt_capacity = int(gt_capacity)
+        if int(image_capacity) < 0:
+            raise ValueError("%s: image_capacity must be >= 0 (0 = no image ledger)" % name)
+        self.image_capacity = int(image_capacity)
 
     def _allocate(self, device):
         dev = torch.device(device if device is not None else "cuda")
@@ -175,6 +192,16 @@ class _RecordStore(object):
         self.cursor = torch.zeros(1, dtype=torch.int64, device=dev)
         self.error = torch.zeros(1, dtype=torch.int32, device=dev)
         self._ws = {}
+        if self.image_capacity:
+            # the image ledger: one row per update -- image_id, the record slots [begin, end) the frame took, its share of the counter --
+            # and the snapshots of cursor and counter the next row is measured from.  Owned here, so that a captured graph replays.
+            ic, cw = self.image_capacity, self._counter.numel()
+            self.led_image = torch.zeros(ic, dtype=torch.int32, device=dev)
+            self.led_range = torch.zeros((ic, 2), dtype=torch.int64, device=dev)
+            self.led_delta = torch.zeros((ic, cw), dtype=torch.int32, device=dev)
+            self.led_count = torch.zeros(1, dtype=torch.int64, device=dev)
+            self._snap_cursor = torch.zeros(1, dtype=torch.int64, device=dev)
+            self._snap_counter = torch.zeros(cw, dtype=torch.int64, device=dev)
 
     # ---- per frame ----------------------------------------------------------------------------------------------------------
     def _workspace(self, D, G):
@@ -193,10 +220,19 @@ class _RecordStore(object):
         if gt.capacity > self.gt_capacity:
             raise ValueError("%s: %s capacity %d > gt_capacity %d" % (type(self).__name__, self._GT.__name__, gt.capacity, self.gt_capacity))
 
+    def _ledger_append(self, gt):
+        """The ledger row of the frame the update before it scored: one further launch on the same stream, no sync, capturable."""
+        if self.image_capacity:
+            ops.eval_ledger_append(gt.frame, self.cursor, self._counter, self._snap_cursor, self._snap_counter, self.led_image, self.led_range,
+                                   self.led_delta, self.led_count, self.error)
+
     def reset(self):
         self.cursor.zero_()
         self._counter.zero_()
         self.error.zero_()
+        if self.image_capacity:
+            for t in (self.led_image, self.led_range, self.led_delta, self.led_count, self._snap_cursor, self._snap_counter):
+                t.zero_()
 
     # ---- per test set -------------------------------------------------------------------------------------------------------
     def _keys(self):
@@ -207,17 +243,28 @@ class _RecordStore(object):
 
     def state(self):
         """The evaluator's state as device tensors (one sync for the record count): the live records in slot order, the counter,
-        n_records (what update counted: more than len(score) when the store overflowed), the error word and the configuration."""
-        n_all = int(self.cursor.item())
+        n_records (what update counted: more than len(score) when the store overflowed), the error word and the configuration.  With an
+        image ledger also its live rows -- led_image, led_range, led_delta -- and n_images (what update counted)."""
+        if self.image_capacity:
+            n_all, m_all = (int(v) for v in torch.cat([self.cursor, self.led_count]).tolist())
+        else:
+            n_all = int(self.cursor.item())
         n = min(n_all, self.record_capacity)
         s = dict(zip(self._keys(), (r[:n].clone() for r in self._records())))
         s.update(n_records=n_all, error=self.error.clone(), **self._config())
         s[self._COUNTER[0]] = self._counter.clone()
+        if self.image_capacity:
+            m = min(m_all, self.image_capacity)
+            s.update(led_image=self.led_image[:m].clone(), led_range=self.led_range[:m].clone(), led_delta=self.led_delta[:m].clone(), n_images=m_all)
         return s
 
     def merge(self, other):
         """Appends the records of `other` (an evaluator of this class, or a state() of one, of the same configuration) and adds its
-        counters: evaluating shards separately and merging equals one evaluator over all of them."""
+        counters: evaluating shards separately and merging equals one evaluator over all of them.  Appends only: an image that two
+        shards have seen counts twice, so an evaluator with an image ledger refuses it and names merge_shards()."""
+        if self.image_capacity:
+            raise ValueError("%s.merge appends without looking at image ids and keeps no ledger: an evaluator built with image_capacity > 0 "
+                             "merges with merge_shards(states) or synchronize_between_processes()" % type(self).__name__)
         s = other.state() if isinstance(other, type(self)) else other
         if any((tuple(s[k]) if isinstance(v, tuple) else s[k]) != v for k, v in self._config().items()):
             raise ValueError("%s.merge: the evaluators differ in %s" % (type(self).__name__, self._CONFIG_WORDS))
@@ -230,6 +277,117 @@ class _RecordStore(object):
         self._counter += s[self._COUNTER[0]].to(self.device)
         self.error |= s["error"].to(self.device)
         return self
+
+    # ---- across shards -----------------------------------------------------------------------------------------------------
+    def _need_ledger(self, what):
+        if not self.image_capacity:
+            raise ValueError("%s.%s needs the image ledger: build the evaluator with image_capacity > 0" % (type(self).__name__, what))
+
+    def _check_config(self, cfg, what):
+        if any((tuple(cfg[k]) if isinstance(v, tuple) else cfg[k]) != v for k, v in self._config().items()):
+            raise ValueError("%s.%s: the evaluators differ in %s" % (type(self).__name__, what, self._CONFIG_WORDS))
+
+    def _shard(self, s, what):
+        """One shard as device tensors with device counts: an evaluator of this class as it stands (its whole buffers and its device
+        counts: no sync, capturable) or a state() of one.  The counts are the LIVE ones (a shard's padding is no record); a shard that had
+        lost records to its own capacity says so in its error word."""
+        if isinstance(s, _RecordStore):
+            if type(s) is not type(self):
+                raise ValueError("%s.%s: a shard is a %s" % (type(self).__name__, what, type(s).__name__))
+            s._need_ledger(what + " (a shard)")
+            self._check_config(s._config(), what)
+            v = dict(zip(("score", "label", "image_id", "order", "flags"), s._records()))
+            lost = torch.where(s.cursor > s.record_capacity, _lib.EVAL_ERR_SHARD_TRUNCATED, 0).to(torch.int32)
+            v.update(led_image=s.led_image, led_range=s.led_range, led_delta=s.led_delta, n_records=s.cursor.clamp(max=s.record_capacity),
+                     n_images=s.led_count.clamp(max=s.image_capacity), error=s.error | lost)
+        else:
+            if "led_image" not in s:
+                raise ValueError("%s.%s: a shard's state() has no image ledger (image_capacity = 0)" % (type(self).__name__, what))
+            self._check_config(s, what)
+            v = dict(zip(("score", "label", "image_id", "order", "flags"), (s[k] for k in self._keys())))
+            v.update({k: s[k] for k in ("led_image", "led_range", "led_delta")})
+            lost = _lib.EVAL_ERR_SHARD_TRUNCATED if int(s["n_records"]) > int(s["score"].shape[0]) else 0
+            v.update(n_records=torch.tensor([min(int(s["n_records"]), int(s["score"].shape[0]))], dtype=torch.int64),
+                     n_images=torch.tensor([min(int(s["n_images"]), int(s["led_image"].shape[0]))], dtype=torch.int64),
+                     error=s["error"].reshape(1) | lost)
+        return {k: t.to(self.device) for k, t in v.items()}
+
+    def _merge(self, shards):
+        ops.eval_merge(shards, dict(score=self.rec_score, label=self.rec_label, image_id=self.rec_image, order=self._rec_order, flags=self.rec_flags,
+                                    led_image=self.led_image, led_range=self.led_range, led_delta=self.led_delta, counter=self._counter,
+                                    cursor=self.cursor, led_count=self.led_count, error=self.error, snap_cursor=self._snap_cursor,
+                                    snap_counter=self._snap_counter))
+        return self
+
+    @staticmethod
+    def _padded(cols, rows):
+        """[W, rows, ...] of the shards' columns [n_w, ...], zero behind each."""
+        out = torch.zeros((len(cols), rows) + tuple(cols[0].shape[1:]), dtype=cols[0].dtype, device=cols[0].device)
+        for w, c in enumerate(cols):
+            out[w, :c.shape[0]].copy_(c)
+        return out
+
+    def merge_shards(self, states):
+        """REPLACES this evaluator's content by the merge of `states`, a list in rank order of evaluators of this class and configuration
+        (taken as they stand: no sync, capturable) or of their state() dicts, all with an image ledger.  The reference's merge
+        (evaluation/coco_eval.py:161-190): occurrences are ordered (shard, ledger row) and an occurrence is kept iff no earlier one has
+        its image_id, so duplicates inside one shard go too.  The kept records arrive in (shard, slot) order, bit for bit; the kept
+        ledger rows in the same order with rebased ranges; the counter is the sum of their deltas; the cursor counts the kept records
+        even past record_capacity and summarize() reports the loss; the error word is the OR of the shards' words.  summarize() and
+        records_sorted() then equal those of one evaluator fed every distinct image once.  Merge into a fresh or reset evaluator (or
+        pass this evaluator itself as one of the shards: they are copied first)."""
+        self._need_ledger("merge_shards")
+        views = [self._shard(s, "merge_shards") for s in states]
+        if not 1 <= len(views) <= _lib.EVAL_MERGE_MAX_SHARDS:
+            raise ValueError("%s.merge_shards: %d shards outside 1 .. %d" % (type(self).__name__, len(views), _lib.EVAL_MERGE_MAX_SHARDS))
+        sr = max(4, (max(v["score"].shape[0] for v in views) + 3) // 4 * 4)
+        si = max(1, max(v["led_image"].shape[0] for v in views))
+        shards = {k: self._padded([v[k] for v in views], sr) for k in ("score", "label", "image_id", "order", "flags")}
+        shards.update({k: self._padded([v[k] for v in views], si) for k in ("led_image", "led_range", "led_delta")})
+        shards.update({k: torch.cat([v[k].reshape(1) for v in views]) for k in ("n_records", "n_images", "error")})
+        return self._merge(shards)
+
+    def synchronize_between_processes(self, group=None):
+        """Named after the reference's CocoEvaluator.synchronize_between_processes (evaluation/coco_eval.py:46-49): EVERY rank of `group`
+        calls it after its last update, and afterwards every rank's evaluator holds the merge of all shards in rank order
+        (merge_shards).  A collective: it reads the live counts on the host, checks that the ranks agree in class and configuration,
+        all-gathers the columns, the ledger and the deltas padded to the largest count -- device tensors on the nccl backend, through
+        the host on any other (gloo) -- and merges in HIP.  Without an initialised process group it is merge_shards([self.state()]):
+        deduplication only."""
+        import torch.distributed as dist
+        self._need_ledger("synchronize_between_processes")
+        name = type(self).__name__
+        if not (dist.is_available() and dist.is_initialized()):
+            return self.merge_shards([self.state()])
+        v = self._shard(self.state(), "synchronize_between_processes")
+        W = dist.get_world_size(group)
+        if W > _lib.EVAL_MERGE_MAX_SHARDS:
+            raise ValueError("%s.synchronize_between_processes: %d ranks, at most %d supported" % (name, W, _lib.EVAL_MERGE_MAX_SHARDS))
+        on_device = dist.get_backend(group) == "nccl"
+
+        def gather(t):
+            t = t.contiguous()
+            if on_device:
+                out = torch.empty((W,) + tuple(t.shape), dtype=t.dtype, device=self.device)
+                dist.all_gather_into_tensor(out, t, group=group)
+                return out
+            h = t.cpu()
+            outs = [torch.empty_like(h) for _ in range(W)]
+            dist.all_gather(outs, h, group=group)
+            return torch.stack(outs).to(self.device)
+
+        cfg = zlib.crc32(repr((name, sorted(self._config().items()))).encode())
+        head = gather(torch.cat([torch.tensor([cfg, v["score"].shape[0], v["led_image"].shape[0]], dtype=torch.int64, device=self.device),
+                                 v["n_records"], v["n_images"], v["error"].to(torch.int64)]))
+        head_h = head.cpu()
+        if bool((head_h[:, 0] != cfg).any()):
+            raise ValueError("%s.synchronize_between_processes: the ranks' evaluators differ in class, %s" % (name, self._CONFIG_WORDS))
+        sr = max(4, (int(head_h[:, 1].max()) + 3) // 4 * 4)
+        si = max(1, int(head_h[:, 2].max()))
+        shards = {k: gather(self._padded([v[k]], sr)[0]) for k in ("score", "label", "image_id", "order", "flags")}
+        shards.update({k: gather(self._padded([v[k]], si)[0]) for k in ("led_image", "led_range", "led_delta")})
+        shards.update(n_records=head[:, 3].contiguous(), n_images=head[:, 4].contiguous(), error=head[:, 5].to(torch.int32))
+        return self._merge(shards)
 
     def _sorted(self):
         """(order, labels_sorted) on the device, no sync: the live slots first, in (label ascending, score descending, image_id
@@ -249,7 +407,9 @@ class _RecordStore(object):
             what = [w for b, w in ((_lib.EVAL_ERR_UPSTREAM_ABORT, "a frame's detection count was -1 (an aborted proposal scan upstream)"),
                                    (_lib.EVAL_ERR_GT_OVERFLOW, "a frame had more ground truths than the %s capacity" % self._GT.__name__),
                                    (_lib.EVAL_ERR_COUNT_RANGE, "a frame's detection count exceeded its capacity"),
-                                   (_lib.EVAL_ERR_LABEL_RANGE, "a label outside 0 .. num_classes - 2")) if err & b]
+                                   (_lib.EVAL_ERR_LABEL_RANGE, "a label outside 0 .. num_classes - 2"),
+                                   (_lib.EVAL_ERR_LEDGER_OVERFLOW, "more frames than the image ledger holds (image_capacity = %d)" % self.image_capacity),
+                                   (_lib.EVAL_ERR_SHARD_TRUNCATED, "a merged shard had lost records or ledger rows to its own capacity")) if err & b]
             raise FrcnnError("%s: error word %d: %s" % (name, err, "; ".join(what)))
         if n_all > self.record_capacity:
             raise FrcnnError("%s: the record store is full: %d of %d records were dropped (record_capacity = %d)"
@@ -273,8 +433,10 @@ class DetectionEvaluator(_RecordStore):
     _COLUMN, _FLAGS_WIDTH, _COUNTER, _OP = "position", 1, ("npos", ()), ("eval_update", _lib.OP_EVAL)
     _GT, _CONFIG_WORDS = GroundTruth, "classes or thresholds"
 
-    def __init__(self, num_classes, iou_thresholds=(0.5,), record_capacity=1 << 20, gt_capacity=128, device=None):
-        super().__init__(num_classes, [float(t) for t in iou_thresholds], record_capacity, gt_capacity)
+    def __init__(self, num_classes, iou_thresholds=(0.5,), record_capacity=1 << 20, gt_capacity=128, device=None, image_capacity=0):
+        """image_capacity > 0 keeps an image ledger of that many frames (one further launch per update): what merge_shards() and
+        synchronize_between_processes() need."""
+        super().__init__(num_classes, [float(t) for t in iou_thresholds], record_capacity, gt_capacity, image_capacity)
         self._allocate(device)
 
     def _config(self):
@@ -286,6 +448,7 @@ class DetectionEvaluator(_RecordStore):
         ops.eval_update(dets, gt.boxes, gt.labels, gt.difficult, gt.n, gt.frame, self.thresholds, self.num_classes, self.npos, self.rec_score,
                         self.rec_label, self.rec_image, self.rec_position, self.rec_flags, self.cursor, self.error,
                         workspace=self._workspace(dets.labels.numel(), gt.capacity))
+        self._ledger_append(gt)
 
     def summarize(self):
         """{"ap": float64 [T, C-1] (NaN for the classes without a countable ground truth), "map": float64 [T] (the mean over the other
@@ -343,11 +506,14 @@ class CocoDetectionEvaluator(_RecordStore):
     _COLUMN, _FLAGS_WIDTH, _COUNTER, _OP = "rank", 4, ("npig", (4,)), ("coco_eval_update", _lib.OP_COCO_EVAL)
     _GT, _CONFIG_WORDS = CocoGroundTruth, "classes, thresholds or maxDets"
 
-    def __init__(self, num_classes, record_capacity=1 << 20, gt_capacity=128, device=None, iou_thresholds=None, max_dets=(1, 10, 100)):
+    def __init__(self, num_classes, record_capacity=1 << 20, gt_capacity=128, device=None, iou_thresholds=None, max_dets=(1, 10, 100),
+                 image_capacity=0):
+        """image_capacity > 0 keeps an image ledger of that many frames (one further launch per update): what merge_shards() and
+        synchronize_between_processes() need."""
         thr = np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True) if iou_thresholds is None \
             else np.array([float(t) for t in iou_thresholds], np.float64)
         md = tuple(int(v) for v in max_dets)
-        super().__init__(num_classes, thr, record_capacity, gt_capacity)
+        super().__init__(num_classes, thr, record_capacity, gt_capacity, image_capacity)
         if len(md) != 3 or list(md) != sorted(md) or md[0] < 1 or md[2] > COCO_MAX_DET:
             raise ValueError("CocoDetectionEvaluator: max_dets must be three ascending values in 1 .. %d" % COCO_MAX_DET)
         self.max_dets = md
@@ -365,6 +531,7 @@ class CocoDetectionEvaluator(_RecordStore):
         ops.coco_eval_update(dets, gt.boxes, gt.area, gt.labels, gt.iscrowd, gt.n, gt.frame, self.thresholds, self.num_classes, self.max_dets[-1],
                              self.npig, self.rec_score, self.rec_label, self.rec_image, self.rec_rank, self.rec_flags, self.cursor, self.error,
                              workspace=self._workspace(dets.labels.numel(), gt.capacity))
+        self._ledger_append(gt)
 
     def summarize(self):
         """{"stats": float64 [12] (COCOeval.stats: AP, AP50, AP75, APs, APm, APl, AR@maxDets[0], AR@maxDets[1], AR@maxDets[2], ARs, ARm,

@@ -11,6 +11,7 @@ Mirrors (file:line under the reference):
   FRCNN.predict post-processing  models/model.py:368-402, models/new_model.py:420-470 (detect_postprocess)
   VOC AP evaluator               evaluation/voc_eval.py:67-225 (eval_update, eval_average_precision)
   COCO evaluator (bbox)          evaluation/coco_eval.py, test.py:60-88,124-128 (coco_eval_update, coco_eval_accumulate)
+  distributed evaluation         evaluation/coco_eval.py:46-49,161-190 (eval_ledger_append, eval_merge)
 
 PyTorch is plumbing here (device memory, streams, autograd glue).  Every op requires contiguous
 fp32 tensors on a HIP device and raises otherwise: there is no CPU path in the product.
@@ -513,6 +514,71 @@ def coco_eval_accumulate(labels_sorted, ranks_sorted, flags_sorted, n_records, n
                                              _ptr(rec_thresholds), R, T, int(num_classes), md[0], md[1], md[2], _ptr(precision), _ptr(recall),
                                              _ptr(ws), nb, _stream()), "coco_eval_accumulate")
     return precision, recall
+
+
+def eval_ledger_append(frame, cursor, counter, snap_cursor, snap_counter, led_image, led_range, led_delta, led_count, error_word):
+    """One row of an evaluator's image ledger, in one launch behind the update on the current stream and with no host sync: row led_count
+    receives image_id = frame[2], the record slots [snap_cursor, cursor) the frame took and delta = counter - snap_counter (int32, the
+    counter flattened), then the snapshots are replaced and led_count grows by one.  frame i32[3]; cursor, snap_cursor, led_count i64[1];
+    counter, snap_counter i64 of the same size; led_image i32 [image_capacity], led_range i64 [image_capacity, 2], led_delta i32
+    [image_capacity, counter.numel()]; error_word i32[1] (a full ledger sets _lib.EVAL_ERR_LEDGER_OVERFLOW and keeps counting).  See
+    include/frcnn_hip.h."""
+    frame = _req(frame, torch.int32, "frame")
+    i64 = [_req(t, torch.int64, n) for t, n in ((cursor, "cursor"), (counter, "counter"), (snap_cursor, "snap_cursor"),
+                                                  (snap_counter, "snap_counter"), (led_range, "led_range"), (led_count, "led_count"))]
+    i32 = [_req(t, torch.int32, n) for t, n in ((led_image, "led_image"), (led_delta, "led_delta"), (error_word, "error_word"))]
+    cap, cw = led_image.numel(), counter.numel()
+    if frame.numel() != 3 or snap_counter.numel() != cw or led_range.numel() != 2 * cap or led_delta.numel() != cap * cw:
+        raise ValueError("eval_ledger_append: shapes disagree")
+    for t in (cursor, counter, snap_cursor, snap_counter, led_image, led_range, led_delta, led_count, error_word):
+        if not t.is_contiguous():
+            raise ValueError("eval_ledger_append: the evaluator's buffers must be contiguous (they are written or read in place)")
+    with torch.cuda.device(frame.device):
+        check(lib.frcnn_eval_ledger_append(_ptr(frame), _ptr(i64[0]), _ptr(i64[1]), cw, _ptr(i64[2]), _ptr(i64[3]), _ptr(i32[0]), _ptr(i64[4]),
+                                           _ptr(i32[1]), cap, _ptr(i64[5]), _ptr(i32[2]), _stream()), "eval_ledger_append")
+
+
+def eval_merge(shards, dst, workspace=None):
+    """Merges W evaluator shards into a destination store on the device (evaluation/coco_eval.py:161-190 merge: the first occurrence of
+    every image id, in (shard, ledger row) order, is kept), with no host sync and a fixed number of launches: capturable.
+    shards: dict of padded buffers, one per column, as an all-gather returns them -- score f32, label / image_id / order i32 [W, SR] (SR a
+    multiple of 4), flags i32 [W, SR] or [W, SR, 4], led_image i32 [W, SI], led_range i64 [W, SI, 2], led_delta i32 [W, SI, CW],
+    n_records / n_images i64 [W] (the live counts, read on the device), error i32 [W].  dst: dict of the destination's buffers, replaced --
+    score, label, image_id, order, flags, led_image, led_range, led_delta, counter i64 (CW elements), cursor, led_count i64[1], error
+    i32[1], snap_cursor i64[1], snap_counter i64 like counter.  See include/frcnn_hip.h; the evaluators' merge_shards() builds both."""
+    kinds = {"score": torch.float32, "label": torch.int32, "image_id": torch.int32, "order": torch.int32, "flags": torch.int32,
+             "led_image": torch.int32, "led_range": torch.int64, "led_delta": torch.int32}
+    src = {k: _req(shards[k], dt, "shards[%r]" % k) for k, dt in kinds.items()}
+    src.update({k: _req(shards[k], dt, "shards[%r]" % k) for k, dt in (("n_records", torch.int64), ("n_images", torch.int64), ("error", torch.int32))})
+    out = {k: _req(dst[k], dt, "dst[%r]" % k) for k, dt in kinds.items()}
+    out.update({k: _req(dst[k], dt, "dst[%r]" % k) for k, dt in (("counter", torch.int64), ("cursor", torch.int64), ("led_count", torch.int64),
+                                                                   ("error", torch.int32), ("snap_cursor", torch.int64), ("snap_counter", torch.int64))})
+    for k, t in out.items():
+        if t is not dst[k]:
+            raise ValueError("eval_merge: dst[%r] must be contiguous (it is written in place)" % k)
+    if src["score"].dim() != 2 or src["led_image"].dim() != 2:
+        raise ValueError("eval_merge: shards are [W, capacity, ...] buffers")
+    W, SR = src["score"].shape
+    SI, RC, IC, CW = src["led_image"].shape[1], out["score"].numel(), out["led_image"].numel(), out["counter"].numel()
+    FW = out["flags"].numel() // max(RC, 1)
+    if any(src[k].numel() != W * SR for k in ("label", "image_id", "order")) or src["flags"].numel() != W * SR * FW or src["led_image"].shape[0] != W \
+            or src["led_range"].numel() != 2 * W * SI or src["led_delta"].numel() != W * SI * CW \
+            or any(src[k].numel() != W for k in ("n_records", "n_images", "error")) \
+            or any(out[k].numel() != RC for k in ("label", "image_id", "order")) or out["flags"].numel() != RC * FW \
+            or out["led_range"].numel() != 2 * IC or out["led_delta"].numel() != IC * CW or out["snap_counter"].numel() != CW:
+        raise ValueError("eval_merge: shapes disagree")
+    dev = out["score"].device
+    nb = _lib.workspace_bytes(_lib.OP_EVAL_MERGE, W * SR, W * SI)
+    if nb == 0:
+        raise _lib.FrcnnError("eval_merge: %d shards of %d records and %d images outside the kernel's limits" % (W, SR, SI))
+    ws = workspace if workspace is not None else _workspace(dev, nb)
+    with torch.cuda.device(dev):
+        check(lib.frcnn_eval_merge(W, SR, SI, FW, CW, *[_ptr(src[k]) for k in ("score", "label", "image_id", "order", "flags", "led_image", "led_range",
+                                                                                "led_delta", "n_records", "n_images", "error")],
+                                   *[_ptr(out[k]) for k in ("score", "label", "image_id", "order", "flags")], RC,
+                                   *[_ptr(out[k]) for k in ("led_image", "led_range", "led_delta")], IC,
+                                   *[_ptr(out[k]) for k in ("counter", "cursor", "led_count", "error", "snap_cursor", "snap_counter")],
+                                   _ptr(ws), ws.numel(), _stream()), "eval_merge")
 
 
 def region_proposal(reg, cls, anchors, min_size_norm, pre_nms_top_k, iou_threshold, post_nms_top_k, grid=None, want_src=False,

@@ -60,7 +60,8 @@ typedef enum {
     FRCNN_OP_RPN_CONV_F32 = 10,   /* n1 = C: frcnn_rpn_conv3x3_f32_fwd / _bwd_data / _wgrad (ticket words, transposed weights, slabs) */
     FRCNN_OP_DETECT = 11,         /* n1 = P RoI rows, n2 = C classes: frcnn_detect_postprocess (0 outside its limits) */
     FRCNN_OP_EVAL = 12,           /* n1 = detection capacity, n2 = ground-truth capacity: frcnn_eval_update (0 outside its limits) */
-    FRCNN_OP_COCO_EVAL = 13       /* n1 = detection capacity, n2 = ground-truth capacity: frcnn_coco_eval_update (0 outside its limits) */
+    FRCNN_OP_COCO_EVAL = 13,      /* n1 = detection capacity, n2 = ground-truth capacity: frcnn_coco_eval_update (0 outside its limits) */
+    FRCNN_OP_EVAL_MERGE = 14      /* n1 = W * shard record capacity, n2 = W * shard image capacity: frcnn_eval_merge (0 outside its limits) */
 } frcnn_op;
 
 /* FRCNN_ABI_VERSION, or FRCNN_ERR_UNSUPPORTED (message in frcnn_last_error) when the objects the library was linked from were compiled
@@ -515,6 +516,42 @@ int frcnn_coco_eval_accumulate(const int32_t *labels_sorted, const int32_t *rank
                                int64_t capacity, const int64_t *npig /*[C-1,4]*/, const double *rec_thresholds_dev /*[R]*/, int R, int T, int C,
                                int max_det_0, int max_det_1, int max_det_2, double *precision, double *recall, void *workspace,
                                size_t workspace_bytes, void *stream);
+
+/* ---- detection evaluators: the image ledger and the merge of shards across ranks (test.py:60-128, evaluation/coco_eval.py:46-49,161-190) -- */
+/* One ledger row per frame, in one launch on the stream of the update before it (frcnn_eval_update or frcnn_coco_eval_update), with no
+ * host sync (graph-capturable).  Row *led_count receives image_id = frame_dev[2], the record slots [*snap_cursor, *cursor) the frame took
+ * and delta[w] = int32(counter[w] - snap_counter[w]) for the counter_words words of the protocol's counter (VOC: C-1, COCO: 4 (C-1));
+ * then *snap_cursor = *cursor, snap_counter = counter and *led_count += 1.  The snapshots belong to the caller and start at zero with
+ * the store.  A full ledger writes no row, keeps counting and sets *error_word |= 16.
+ * Limits: image_capacity >= 1; 1 <= counter_words <= 1020 (FRCNN_ERR_UNSUPPORTED otherwise). */
+int frcnn_eval_ledger_append(const int32_t *frame_dev /*[3]: w, h, image_id*/, const int64_t *cursor /*[1]*/, const int64_t *counter /*[counter_words]*/,
+                             int64_t counter_words, int64_t *snap_cursor /*[1]*/, int64_t *snap_counter /*[counter_words]*/, int32_t *led_image,
+                             int64_t *led_range /*[image_capacity,2]*/, int32_t *led_delta /*[image_capacity,counter_words]*/,
+                             int64_t image_capacity, int64_t *led_count /*[1]*/, int32_t *error_word /*[1]*/, void *stream);
+/* Merges W shards of one evaluator class into a destination store, whose previous content is replaced: the reference's merge
+ * (evaluation/coco_eval.py:161-190: all_gather, then np.unique(img_ids, return_index=True)).  Occurrences are ordered (shard, ledger
+ * row); an occurrence is KEPT iff no earlier occurrence has its image_id -- duplicates inside one shard are dropped too; every int32 is
+ * a legal id.  Shards arrive as one padded buffer per column, [W, shard capacity, ...] (the result of an all-gather as it is); the live
+ * counts sh_n_records / sh_n_images (int64 [W], clipped to the capacities) and sh_error are read on the device: no host sync, a fixed
+ * number of launches whatever the data, graph-capturable.  A row's range is clipped to its shard's live records before it is used;
+ * the ranges of a shard ascend, as frcnn_eval_ledger_append writes them.
+ * Effects: the records of kept occurrences in (shard, slot) order, all five columns bit for bit (slots past record_capacity are counted,
+ * not written); the kept ledger rows in the same order with rebased ranges (rows past image_capacity are counted, not written);
+ * counter = the sum of the kept rows' delta; *cursor = the kept records; *led_count = the kept rows; *error_word = the OR of sh_error,
+ * | 16 when the kept rows exceed image_capacity, | 32 when a shard's count exceeds its capacity (it had lost some); *snap_cursor / snap_counter follow, so that updates may go on.
+ * flags_width: 1 (VOC) or 4 (COCO) words per record.  FRCNN_ERR_INVALID_ARG: a NULL pointer, a negative capacity, a
+ * shard_record_capacity that is no multiple of 4, another flags_width, record columns that are not 16-byte aligned, a destination
+ * buffer that overlaps a shard buffer, the workspace or another destination buffer.  FRCNN_ERR_UNSUPPORTED: W outside 1 .. 64,
+ * counter_words outside 1 .. 1020, W * shard_record_capacity >= 2^31 - 4096, W * shard_image_capacity >= 2^30.  FRCNN_ERR_WORKSPACE:
+ * fewer than frcnn_workspace_bytes(FRCNN_OP_EVAL_MERGE, W * shard_record_capacity, W * shard_image_capacity) bytes (any content). */
+int frcnn_eval_merge(int W, int64_t shard_record_capacity, int64_t shard_image_capacity, int flags_width, int64_t counter_words,
+                     const float *sh_score, const int32_t *sh_label, const int32_t *sh_image, const int32_t *sh_order, const uint32_t *sh_flags,
+                     const int32_t *sh_led_image, const int64_t *sh_led_range, const int32_t *sh_led_delta, const int64_t *sh_n_records /*[W]*/,
+                     const int64_t *sh_n_images /*[W]*/, const int32_t *sh_error /*[W]*/, float *rec_score, int32_t *rec_label,
+                     int32_t *rec_image, int32_t *rec_order, uint32_t *rec_flags, int64_t record_capacity, int32_t *led_image,
+                     int64_t *led_range, int32_t *led_delta, int64_t image_capacity, int64_t *counter, int64_t *cursor /*[1]*/,
+                     int64_t *led_count /*[1]*/, int32_t *error_word /*[1]*/, int64_t *snap_cursor /*[1]*/, int64_t *snap_counter,
+                     void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- input stage in front of the path ------------------------------------------------------
  * One uint8 HWC RGB frame in HBM -> [hflip] -> PIL-bilinear resize to (oh, ow) -> /255 -> (x - mean) / std -> float CHW
