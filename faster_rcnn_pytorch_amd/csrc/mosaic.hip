@@ -5,8 +5,8 @@
 // box survives the crop (transforms_.py:174-176), so which pixels a tile is made of depends on its boxes: that decision is taken by
 // the box kernel and stays in device memory, where the image kernels read it.  Six launches, whatever the boxes say:
 //   mosaic_boxes_kernel   : ONE workgroup walks the four tiles in order: pass 1 asks whether any box survives, pass 2 compacts the
-//                           survivors (or all boxes) in order, 256 at a time (ballot + popcount inside a wave, four wave totals through
-//                           LDS, a running base across chunks and tiles); writes the region used, the flag, the count, zeros past it
+//                           survivors (or all boxes) in order, 256 at a time (in_compact_slot, one running base across chunks and
+//                           tiles); writes the region used, the flag, the count, zeros past it
 //   mosaic_coeffs_kernel  : Pillow's windows of both resizes of every tile; the second resize's come from the region in device memory
 //   mosaic_h1/v1_kernel   : first resize, only the columns / rows the region needs (outputs are independent per pixel) -> a real
 //                           uint8 image, as the reference has between its two resizes
@@ -18,7 +18,7 @@
 #include "frcnn_internal.h"
 #include "frcnn_layout.h"
 FRCNN_LAYOUT_STAMP(mosaic);
-#include "resample_dev.h"
+#include "input_dev.h"
 
 struct MosaicTile {
     const uint8_t *src;
@@ -27,8 +27,7 @@ struct MosaicTile {
     float r1w, r1h;                       // transforms_.py:118-125: new / old, formed in double
     float r2w[2], r2h[2];                 // the second resize's ratios: [0] the crop was taken, [1] it was not
     int box_lo, box_hi;                   // this tile's rows of the tile-major box list
-    int ks1x, ks1y, ks2x, ks2y;           // row strides of the coefficient tables (second resize: the worst case, the whole frame)
-    int32_t *bx1, *by1, *kx1, *ky1, *bx2, *by2, *kx2, *ky2;
+    RsAxis x1, y1, x2, y2;                // both resizes' window tables, row = output index (second resize: strides for the worst case, the whole frame)
     uint8_t *tmp1, *img1, *tmp2;          // [h, W1, 3], [H1, W1, 3] (both in frame coordinates), [H1, size, 3] (region rows)
 };
 struct MosaicDesc { MosaicTile t[4]; int size; int32_t *regions; /* [4][4] device: the region each tile used */ };
@@ -37,11 +36,8 @@ static_assert(sizeof(MosaicDesc) <= 4096, "MosaicDesc must fit the kernarg segme
 // crop_ (transforms_.py:155-168) for one resized box: the clipped box and whether it is kept
 __device__ __forceinline__ bool mosaic_crop_keep(float4 b, float fi, float fj, float fh, float fw, float4 *c)
 {
-    float x1 = tmin(b.x - fj, fw), y1 = tmin(b.y - fi, fh), x2 = tmin(b.z - fj, fw), y2 = tmin(b.w - fi, fh);     // :156-157
-    x1 = x1 < 0.0f ? 0.0f : x1; y1 = y1 < 0.0f ? 0.0f : y1; x2 = x2 < 0.0f ? 0.0f : x2; y2 = y2 < 0.0f ? 0.0f : y2;     // :158 (NaN stays)
-    *c = make_float4(x1, y1, x2, y2);
-    const bool keep = x2 > x1 && y2 > y1;                                                                        // :161
-    const float bw = b.z - b.x, bh = b.w - b.y, cw = x2 - x1, ch = y2 - y1;                                     // :165-166
+    const bool keep = in_clip_box(b, fi, fj, fh, fw, c);                                                         // :156-161
+    const float bw = b.z - b.x, bh = b.w - b.y, cw = c->z - c->x, ch = c->w - c->y;                             // :165-166
     return keep && (cw * ch) / (bw * bh) > 0.3f;                                                                 // :167 (NaN compares false)
 }
 
@@ -50,7 +46,7 @@ __global__ __launch_bounds__(256) void mosaic_boxes_kernel(MosaicDesc d, const f
                                                           int32_t *__restrict__ count_dev, uint8_t *__restrict__ fallback_dev)
 {
     __shared__ int s_any, s_wave[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const float fsize = (float)d.size;
     int base = 0;                                                     // live rows so far: the same in every thread
     for (int t = 0; t < 4; ++t) {
@@ -75,7 +71,7 @@ __global__ __launch_bounds__(256) void mosaic_boxes_kernel(MosaicDesc d, const f
         }
         const float r2w = T.r2w[fb], r2h = T.r2h[fb];
         const float sx = (t & 1) ? fsize : 0.0f, sy = (t >> 1) ? fsize : 0.0f;       // mosaic_transform.py:82-85
-        for (int c0 = T.box_lo; c0 < T.box_hi; c0 += 256) {            // uniform trip count: every thread reaches both barriers
+        for (int c0 = T.box_lo; c0 < T.box_hi; c0 += 256) {            // uniform trip count: every thread makes every in_compact_slot call
             const int i = c0 + tid;
             bool keep = false;
             float4 o = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -86,18 +82,11 @@ __global__ __launch_bounds__(256) void mosaic_boxes_kernel(MosaicDesc d, const f
                 keep = mosaic_crop_keep(b1, fi, fj, fh, fw, &c) || fb;
                 o = fb ? b1 : c;
             }
-            const unsigned long long m = __ballot(keep);
-            if (lane == 0) s_wave[wave] = __popcll(m);
-            __syncthreads();
-            int off = base;
-            for (int q = 0; q < wave; ++q) off += s_wave[q];
+            const int off = in_compact_slot(keep, base, s_wave);
             if (keep) {
-                off += __popcll(m & ((1ull << lane) - 1ull));
                 boxes_out[off] = make_float4(o.x * r2w + sx, o.y * r2h + sy, o.z * r2w + sx, o.w * r2h + sy);
                 labels_out[off] = labels[i];
             }
-            base += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-            __syncthreads();
         }
     }
     for (int i = base + tid; i < n_total; i += 256) { boxes_out[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); labels_out[i] = 0; }
@@ -119,16 +108,14 @@ __global__ __launch_bounds__(256) void mosaic_coeffs_kernel(MosaicDesc d)
     int ri, rj, rh, rw;
     if (!mosaic_region(d, t, &ri, &rj, &rh, &rw)) return;
     int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < T.W1) { rs_coeffs_row(i, T.w, T.W1, T.ks1x, T.bx1, T.kx1); return; }
+    if (i < T.W1) { rs_axis_coeffs(T.x1, i, i, T.w, T.W1); return; }
     i -= T.W1;
-    if (i < T.H1) { rs_coeffs_row(i, T.h, T.H1, T.ks1y, T.by1, T.ky1); return; }
+    if (i < T.H1) { rs_axis_coeffs(T.y1, i, i, T.h, T.H1); return; }
     i -= T.H1;
-    if (i < d.size) { rs_coeffs_row(i, rw, d.size, T.ks2x, T.bx2, T.kx2); return; }      // rw <= W1: the window fits the stride
+    if (i < d.size) { rs_axis_coeffs(T.x2, i, i, rw, d.size); return; }      // rw <= W1: the window fits the stride
     i -= d.size;
-    if (i < d.size) rs_coeffs_row(i, rh, d.size, T.ks2y, T.by2, T.ky2);
+    if (i < d.size) rs_axis_coeffs(T.y2, i, i, rh, d.size);
 }
-
-__device__ __forceinline__ void mosaic_store3(uint8_t *o, const uint8_t px[3]) { o[0] = px[0]; o[1] = px[1]; o[2] = px[2]; }
 
 // first resize, horizontal: the region's columns, on the source rows its rows' windows reach
 __global__ __launch_bounds__(256) void mosaic_h1_kernel(MosaicDesc d)
@@ -138,14 +125,11 @@ __global__ __launch_bounds__(256) void mosaic_h1_kernel(MosaicDesc d)
     int ri, rj, rh, rw;
     if (!mosaic_region(d, t, &ri, &rj, &rh, &rw)) return;
     const int x0 = blockIdx.x * 256 + threadIdx.x;
-    const int ylo = T.by1[2 * ri], yhi = T.by1[2 * (ri + rh - 1)] + T.by1[2 * (ri + rh - 1) + 1];
+    const int ylo = T.y1.b[2 * ri], yhi = T.y1.b[2 * (ri + rh - 1)] + T.y1.b[2 * (ri + rh - 1) + 1];
     if (x0 >= rw || (int)blockIdx.y >= yhi - ylo) return;
     const int xx = rj + x0, y = ylo + blockIdx.y;
     if (y < 0 || y >= T.h) return;
-    const int xmin = T.bx1[2 * xx], n = T.bx1[2 * xx + 1];
-    uint8_t px[3];
-    rs_window_rgb(T.src + ((size_t)y * T.w + xmin) * 3, 3, n, T.kx1 + (size_t)xx * T.ks1x, px);
-    mosaic_store3(T.tmp1 + ((size_t)y * T.W1 + xx) * 3, px);
+    rs_pass_px(T.x1, xx, T.src + (size_t)y * T.w * 3, 3, 0, T.tmp1 + ((size_t)y * T.W1 + xx) * 3);
 }
 
 // first resize, vertical: the region's pixels of the resized uint8 frame
@@ -158,10 +142,7 @@ __global__ __launch_bounds__(256) void mosaic_v1_kernel(MosaicDesc d)
     const int x0 = blockIdx.x * 256 + threadIdx.x;
     if (x0 >= rw || (int)blockIdx.y >= rh) return;
     const int xx = rj + x0, yy = ri + blockIdx.y;
-    const int ymin = T.by1[2 * yy], n = T.by1[2 * yy + 1];
-    uint8_t px[3];
-    rs_window_rgb(T.tmp1 + ((size_t)ymin * T.W1 + xx) * 3, (ptrdiff_t)T.W1 * 3, n, T.ky1 + (size_t)yy * T.ks1y, px);
-    mosaic_store3(T.img1 + ((size_t)yy * T.W1 + xx) * 3, px);
+    rs_pass_px(T.y1, yy, T.tmp1 + (size_t)xx * 3, (ptrdiff_t)T.W1 * 3, 0, T.img1 + ((size_t)yy * T.W1 + xx) * 3);
 }
 
 // second resize, horizontal: the region as an image of its own, [rh, rw] -> [rh, size]
@@ -173,10 +154,7 @@ __global__ __launch_bounds__(256) void mosaic_h2_kernel(MosaicDesc d)
     if (!mosaic_region(d, t, &ri, &rj, &rh, &rw)) return;
     const int xx = blockIdx.x * 256 + threadIdx.x, r = blockIdx.y;
     if (xx >= d.size || r >= rh) return;
-    const int xmin = T.bx2[2 * xx], n = T.bx2[2 * xx + 1];
-    uint8_t px[3];
-    rs_window_rgb(T.img1 + ((size_t)(ri + r) * T.W1 + rj + xmin) * 3, 3, n, T.kx2 + (size_t)xx * T.ks2x, px);
-    mosaic_store3(T.tmp2 + ((size_t)r * d.size + xx) * 3, px);
+    rs_pass_px(T.x2, xx, T.img1 + ((size_t)(ri + r) * T.W1 + rj) * 3, 3, 0, T.tmp2 + ((size_t)r * d.size + xx) * 3);      // the region is img1's sub-image at (ri, rj)
 }
 
 // second resize, vertical, stored into the tile's quadrant (mosaic_transform.py:15-26,88-91: equal tiles, so the centre offsets are 0)
@@ -188,11 +166,8 @@ __global__ __launch_bounds__(256) void mosaic_v2_kernel(MosaicDesc d, uint8_t *_
     if (!mosaic_region(d, t, &ri, &rj, &rh, &rw)) return;
     const int xx = blockIdx.x * 256 + threadIdx.x, yy = blockIdx.y;
     if (xx >= d.size) return;
-    const int ymin = T.by2[2 * yy], n = T.by2[2 * yy + 1];
-    uint8_t px[3];
-    rs_window_rgb(T.tmp2 + ((size_t)ymin * d.size + xx) * 3, (ptrdiff_t)d.size * 3, n, T.ky2 + (size_t)yy * T.ks2y, px);
     const size_t cy = (size_t)(t >> 1) * d.size + yy, cx = (size_t)(t & 1) * d.size + xx;
-    mosaic_store3(canvas + (cy * (2 * (size_t)d.size) + cx) * 3, px);
+    rs_pass_px(T.y2, yy, T.tmp2 + (size_t)xx * 3, (ptrdiff_t)d.size * 3, 0, canvas + (cy * (2 * (size_t)d.size) + cx) * 3);
 }
 
 // resize_'s size logic (transforms_.py:93-114), in its own order of double operations; max_size <= 0: no cap
@@ -209,35 +184,30 @@ static void mosaic_first_size(int h, int w, int size, int max_size, int *H1, int
 
 static bool mosaic_shapes_ok(const int32_t *src_hw, int size, int max_size, int H1[4], int W1[4])
 {
-    if (!src_hw || size < 1 || 2 * (int64_t)size >= (1 << 15)) return false;
+    if (!src_hw || !in_side_ok(size) || !in_side_ok(2 * size)) return false;
     for (int t = 0; t < 4; ++t) {
         const int h = src_hw[2 * t], w = src_hw[2 * t + 1];
-        if (h < 1 || w < 1 || h >= (1 << 15) || w >= (1 << 15)) return false;
+        if (!in_side_ok(h) || !in_side_ok(w)) return false;
         mosaic_first_size(h, w, size, max_size, &H1[t], &W1[t]);
-        if (H1[t] < 1 || W1[t] < 1 || H1[t] >= (1 << 15) || W1[t] >= (1 << 15)) return false;
+        if (!in_side_ok(H1[t]) || !in_side_ok(W1[t])) return false;
     }
     return true;
 }
 
 static size_t mosaic_ws_layout(void *base, const int32_t *src_hw, const int H1[4], const int W1[4], int size, MosaicDesc *d)
 {
-    size_t o = 0;
-    auto take = [&](size_t bytes) { void *q = base ? (char *)base + o : nullptr; o += align_up(bytes, 256); return q; };
+    InCarver c = {(char *)base, 0};
     d->size = size;
-    d->regions = (int32_t *)take(16 * sizeof(int32_t));
+    d->regions = c.get<int32_t>(16);
     for (int t = 0; t < 4; ++t) {
         MosaicTile &T = d->t[t];
         T.h = src_hw[2 * t]; T.w = src_hw[2 * t + 1]; T.H1 = H1[t]; T.W1 = W1[t];
-        T.ks1x = rs_ksize_host(T.w, T.W1); T.ks1y = rs_ksize_host(T.h, T.H1);
-        T.ks2x = rs_ksize_host(T.W1, size); T.ks2y = rs_ksize_host(T.H1, size);
-        T.bx1 = (int32_t *)take((size_t)T.W1 * 8); T.by1 = (int32_t *)take((size_t)T.H1 * 8);
-        T.kx1 = (int32_t *)take((size_t)T.W1 * T.ks1x * 4); T.ky1 = (int32_t *)take((size_t)T.H1 * T.ks1y * 4);
-        T.bx2 = (int32_t *)take((size_t)size * 8); T.by2 = (int32_t *)take((size_t)size * 8);
-        T.kx2 = (int32_t *)take((size_t)size * T.ks2x * 4); T.ky2 = (int32_t *)take((size_t)size * T.ks2y * 4);
-        T.tmp1 = (uint8_t *)take((size_t)T.h * T.W1 * 3); T.img1 = (uint8_t *)take((size_t)T.H1 * T.W1 * 3);
-        T.tmp2 = (uint8_t *)take((size_t)T.H1 * size * 3);
+        T.x1 = rs_axis_take(c, T.w, T.W1, T.W1); T.y1 = rs_axis_take(c, T.h, T.H1, T.H1);
+        T.x2 = rs_axis_take(c, T.W1, size, size); T.y2 = rs_axis_take(c, T.H1, size, size);
+        T.tmp1 = c.get<uint8_t>((size_t)T.h * T.W1 * 3); T.img1 = c.get<uint8_t>((size_t)T.H1 * T.W1 * 3);
+        T.tmp2 = c.get<uint8_t>((size_t)T.H1 * size * 3);
     }
-    return o;
+    return c.o;
 }
 
 FRCNN_EXPORT size_t frcnn_mosaic_workspace(const int32_t *src_hw, int size, int max_size)
@@ -254,8 +224,9 @@ FRCNN_EXPORT int frcnn_mosaic(const uint8_t *const src_hwc[4], const int32_t *sr
 {
     FRCNN_REQUIRE(src_hwc && src_hw && regions && tile_offsets && canvas && count_dev && fallback_dev && workspace, "mosaic: NULL pointer");
     for (int t = 0; t < 4; ++t) FRCNN_REQUIRE(src_hwc[t], "mosaic: NULL source frame %d", t);
+    // only the upper limit here, not in_side_ok(): a side < 1 keeps falling through to the 'bad shape' message below
     for (int t = 0; t < 4; ++t)
-        FRCNN_REQUIRE(src_hw[2 * t] < (1 << 15) && src_hw[2 * t + 1] < (1 << 15), "mosaic: frame %d too large (%d x %d, sides must be < 32768)", t,
+        FRCNN_REQUIRE(src_hw[2 * t] <= IN_SIDE_MAX && src_hw[2 * t + 1] <= IN_SIDE_MAX, "mosaic: frame %d too large (%d x %d, sides must be < 32768)", t,
                       src_hw[2 * t], src_hw[2 * t + 1]);
     int H1[4], W1[4];
     FRCNN_REQUIRE(mosaic_shapes_ok(src_hw, size, max_size, H1, W1), "mosaic: bad shape (sides >= 1, size >= 1, 2 * size and every resized side < 32768)");

@@ -24,9 +24,9 @@
 #include "frcnn_layout.h"
 FRCNN_LAYOUT_STAMP(photometric);
 #include "photometric_dev.h"
+#include "input_dev.h"
 
 #define PM_MAX_BLOCKS 4096                // partial sums the workspace holds; the grid is min(work, 8 per CU, this)
-#define PM_SIDE_MAX 32767
 #define ZO_HIST_BLOCKS 128                // workgroups of the histogram pass = rows of counts the workspace holds
 #define ZO_WS_PART 16                     // the workspace in dwords: [0, 3) the medians, from here [ZO_HIST_BLOCKS][768] counts
 
@@ -192,13 +192,6 @@ __global__ __launch_bounds__(256) void zo_fill_kernel(const uint8_t *__restrict_
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------
-static bool pm_side_ok(int v) { return v >= 1 && v <= PM_SIDE_MAX; }
-static bool pm_overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + nb && pb < pa + na;
-}
-
 // workgroups of 256 for `groups` four-pixel groups: at most 8 per CU of the current device, at most PM_MAX_BLOCKS, at least 1
 static int pm_grid(uint32_t groups, unsigned *grid)
 {
@@ -220,7 +213,7 @@ static int pm_grid(uint32_t groups, unsigned *grid)
 
 FRCNN_EXPORT size_t frcnn_photometric_workspace(int h, int w)
 {
-    if (!pm_side_ok(h) || !pm_side_ok(w)) return 0;
+    if (!in_side_ok(h) || !in_side_ok(w)) return 0;
     return PM_MAX_BLOCKS * sizeof(uint64_t);
 }
 
@@ -228,11 +221,11 @@ FRCNN_EXPORT int frcnn_photometric(const uint8_t *src_hwc, int h, int w, const i
                                    size_t workspace_bytes, void *stream)
 {
     FRCNN_REQUIRE(src_hwc && plan_dev && out_hwc && workspace, "photometric: NULL pointer");
-    FRCNN_REQUIRE(pm_side_ok(h) && pm_side_ok(w), "photometric: bad shape %d x %d (sides of 1 .. 32767)", h, w);
+    FRCNN_REQUIRE(in_side_ok(h) && in_side_ok(w), "photometric: bad shape %d x %d (sides of 1 .. 32767)", h, w);
     const size_t bytes = (size_t)h * (size_t)w * 3;
     FRCNN_REQUIRE(((uintptr_t)src_hwc & 3) == 0 && ((uintptr_t)out_hwc & 3) == 0 && ((uintptr_t)workspace & 7) == 0 && ((uintptr_t)plan_dev & 3) == 0,
                   "photometric: src and out must be 4-byte aligned, the workspace 8-byte aligned");
-    FRCNN_REQUIRE(!pm_overlap(src_hwc, bytes, out_hwc, bytes), "photometric: out overlaps src (pass 2 reads the source again)");
+    FRCNN_REQUIRE(!in_overlap(src_hwc, bytes, out_hwc, bytes), "photometric: out overlaps src (pass 2 reads the source again)");
     const size_t need = frcnn_photometric_workspace(h, w);
     if (workspace_bytes < need) return frcnn_set_error(FRCNN_ERR_WORKSPACE, "photometric: workspace %zu < %zu", workspace_bytes, need);
     const uint32_t npix = (uint32_t)h * (uint32_t)w;
@@ -249,7 +242,7 @@ FRCNN_EXPORT int frcnn_photometric(const uint8_t *src_hwc, int h, int w, const i
 
 FRCNN_EXPORT size_t frcnn_zoom_out_workspace(int h, int w, int new_h, int new_w)
 {
-    if (!pm_side_ok(h) || !pm_side_ok(w) || !pm_side_ok(new_h) || !pm_side_ok(new_w) || new_h < h || new_w < w) return 0;
+    if (!in_side_ok(h) || !in_side_ok(w) || !in_side_ok(new_h) || !in_side_ok(new_w) || new_h < h || new_w < w) return 0;
     return (ZO_WS_PART + (size_t)ZO_HIST_BLOCKS * 768) * sizeof(uint32_t);
 }
 
@@ -258,7 +251,7 @@ FRCNN_EXPORT int frcnn_zoom_out(const uint8_t *src_hwc, int h, int w, int new_h,
 {
     FRCNN_REQUIRE(src_hwc && canvas && workspace, "zoom_out: NULL pointer");
     FRCNN_REQUIRE(n >= 0 && (n == 0 || (boxes && boxes_out)), "zoom_out: NULL box pointer with %lld boxes (or a negative count)", (long long)n);
-    FRCNN_REQUIRE(pm_side_ok(h) && pm_side_ok(w) && pm_side_ok(new_h) && pm_side_ok(new_w),
+    FRCNN_REQUIRE(in_side_ok(h) && in_side_ok(w) && in_side_ok(new_h) && in_side_ok(new_w),
                   "zoom_out: bad shape %d x %d -> %d x %d (sides of 1 .. 32767, the canvas included)", h, w, new_h, new_w);
     FRCNN_REQUIRE(new_h >= h && new_w >= w, "zoom_out: the canvas %d x %d is smaller than the frame %d x %d", new_h, new_w, h, w);
     FRCNN_REQUIRE(top >= 0 && left >= 0 && top <= new_h - h && left <= new_w - w,
@@ -267,7 +260,7 @@ FRCNN_EXPORT int frcnn_zoom_out(const uint8_t *src_hwc, int h, int w, int new_h,
                   "zoom_out: src, canvas and workspace must be 4-byte aligned");
     FRCNN_REQUIRE(n == 0 || (((uintptr_t)boxes & 15) == 0 && ((uintptr_t)boxes_out & 15) == 0), "zoom_out: boxes and boxes_out must be 16-byte aligned");
     const size_t sbytes = (size_t)h * (size_t)w * 3, cbytes = (size_t)new_h * (size_t)new_w * 3;
-    FRCNN_REQUIRE(!pm_overlap(src_hwc, sbytes, canvas, cbytes), "zoom_out: the canvas overlaps src");
+    FRCNN_REQUIRE(!in_overlap(src_hwc, sbytes, canvas, cbytes), "zoom_out: the canvas overlaps src");
     const size_t need = frcnn_zoom_out_workspace(h, w, new_h, new_w);
     if (workspace_bytes < need) return frcnn_set_error(FRCNN_ERR_WORKSPACE, "zoom_out: workspace %zu < %zu", workspace_bytes, need);
     const uint32_t npix = (uint32_t)h * (uint32_t)w, ncanvas = (uint32_t)new_h * (uint32_t)new_w;

@@ -11,50 +11,44 @@
 //   resample_h_kernel      : lane = (row, out column): u8 x 3 gathers through the (optionally mirrored) window
 //   resample_v_norm_kernel : lane = (out row, out column) of the PADDED frame: vertical window, /255, -mean, /std in
 //                            binary32 in the reference's operation order, three coalesced plane stores; zeros in the pad
-// The window, the 3-channel window sum and the clip live in resample_dev.h (shared with mosaic.hip).
+// The window, the 3-channel window sum and the clip live in resample_dev.h, the window table of an axis and one output pixel of a pass
+// in input_dev.h (both shared with mosaic.hip and crop.hip).
 // Bit-exact against Pillow through the oracle (tests/test_preprocess.py).  HBM-bound in principle (1.5 MB in, 10 MB out
 // for 480x640 -> 800x1066) but at these sizes the two passes are launch/latency bound (~10 us).
 #include "frcnn_common.h"
 #include "frcnn_internal.h"
 #include "frcnn_layout.h"
 FRCNN_LAYOUT_STAMP(preprocess);
-#include "resample_dev.h"           // the resampler's device code, shared with mosaic.hip
+#include "input_dev.h"
 
-__global__ __launch_bounds__(256) void resample_coeffs_kernel(int in_x, int out_x, int ks_x, int32_t *__restrict__ bx, int32_t *__restrict__ kx,
-                                                             int in_y, int out_y, int ks_y, int32_t *__restrict__ by, int32_t *__restrict__ ky)
+__global__ __launch_bounds__(256) void resample_coeffs_kernel(int in_x, int out_x, RsAxis ax, int in_y, int out_y, RsAxis ay)
 {
     int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < out_x) { rs_coeffs_row(i, in_x, out_x, ks_x, bx, kx); return; }
+    if (i < out_x) { rs_axis_coeffs(ax, i, i, in_x, out_x); return; }
     i -= out_x;
-    if (i < out_y) rs_coeffs_row(i, in_y, out_y, ks_y, by, ky);
+    if (i < out_y) rs_axis_coeffs(ay, i, i, in_y, out_y);
 }
 
-__global__ __launch_bounds__(256) void resample_h_kernel(const uint8_t *__restrict__ src, int h, int w, int flip, int ow, int ks,
-                                                        const int32_t *__restrict__ bx, const int32_t *__restrict__ kx, uint8_t *__restrict__ tmp)
+__global__ __launch_bounds__(256) void resample_h_kernel(const uint8_t *__restrict__ src, int h, int w, int flip, int ow, RsAxis ax,
+                                                        uint8_t *__restrict__ tmp)
 {
     const int xx = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
     if (xx >= ow) return;
-    const int xmin = bx[2 * xx], n = bx[2 * xx + 1];
     const uint8_t *row = src + (size_t)y * w * 3;
-    uint8_t px[3];
-    rs_window_rgb(row + (flip ? w - 1 - xmin : xmin) * 3, flip ? -3 : 3, n, kx + (size_t)xx * ks, px);
-    uint8_t *o = tmp + ((size_t)y * ow + xx) * 3;
-    o[0] = px[0]; o[1] = px[1]; o[2] = px[2];
+    rs_pass_px(ax, xx, flip ? row + (w - 1) * 3 : row, flip ? -3 : 3, 0, tmp + ((size_t)y * ow + xx) * 3);      // mirrored: source x at w - 1 - x
 }
 
 struct NormConst { float mean[3], std[3]; };
 
-__global__ __launch_bounds__(256) void resample_v_norm_kernel(const uint8_t *__restrict__ tmp, int oh, int ow, int ph, int pw, int ks,
-                                                             const int32_t *__restrict__ by, const int32_t *__restrict__ ky, NormConst nc,
-                                                             float *__restrict__ out, uint8_t *__restrict__ out_u8)
+__global__ __launch_bounds__(256) void resample_v_norm_kernel(const uint8_t *__restrict__ tmp, int oh, int ow, int ph, int pw, RsAxis ay,
+                                                             NormConst nc, float *__restrict__ out, uint8_t *__restrict__ out_u8)
 {
     const int xx = blockIdx.x * 256 + threadIdx.x, yy = blockIdx.y;
     if (xx >= pw) return;
     float v0 = 0.0f, v1 = 0.0f, v2 = 0.0f;
     if (yy < oh && xx < ow) {
-        const int ymin = by[2 * yy], n = by[2 * yy + 1];
         uint8_t px[3];
-        rs_window_rgb(tmp + ((size_t)ymin * ow + xx) * 3, (ptrdiff_t)ow * 3, n, ky + (size_t)yy * ks, px);
+        rs_pass_rgb(ay, yy, tmp + (size_t)xx * 3, (ptrdiff_t)ow * 3, 0, px);
         const uint8_t u0 = px[0], u1 = px[1], u2 = px[2];
         if (out_u8) { uint8_t *q = out_u8 + ((size_t)yy * ow + xx) * 3; q[0] = u0; q[1] = u1; q[2] = u2; }
         v0 = ((float)u0 / 255.0f - nc.mean[0]) / nc.std[0];          // F.to_tensor .div(255); F.normalize sub_(mean).div_(std)
@@ -80,20 +74,16 @@ __global__ __launch_bounds__(256) void preprocess_boxes_kernel(const float4 *__r
     out[i] = make_float4(b.x / fow, b.y / foh, b.z / fow, b.w / foh); // :276-280
 }
 
-struct PreWs { int32_t *bx, *by, *kx, *ky; uint8_t *tmp; size_t total; int ksx, ksy; };
+struct PreWs { RsAxis x, y; uint8_t *tmp; size_t total; };
 
 static PreWs pre_ws_layout(void *base, int h, int w, int oh, int ow)
 {
     PreWs p;
-    p.ksx = rs_ksize_host(w, ow); p.ksy = rs_ksize_host(h, oh);
-    size_t o = 0;
-    auto take = [&](size_t bytes) { void *q = base ? (char *)base + o : nullptr; o += align_up(bytes, 256); return q; };
-    p.bx = (int32_t *)take((size_t)ow * 8);
-    p.by = (int32_t *)take((size_t)oh * 8);
-    p.kx = (int32_t *)take((size_t)ow * p.ksx * 4);
-    p.ky = (int32_t *)take((size_t)oh * p.ksy * 4);
-    p.tmp = (uint8_t *)take((size_t)h * ow * 3);
-    p.total = o;
+    InCarver c = {(char *)base, 0};
+    p.x = rs_axis_take(c, w, ow, ow);
+    p.y = rs_axis_take(c, h, oh, oh);
+    p.tmp = c.get<uint8_t>((size_t)h * ow * 3);
+    p.total = c.o;
     return p;
 }
 
@@ -110,7 +100,7 @@ FRCNN_EXPORT int frcnn_preprocess_image(const uint8_t *src_hwc, int h, int w, in
 {
     FRCNN_REQUIRE(h >= 1 && w >= 1 && oh >= 1 && ow >= 1 && pad_h >= oh && pad_w >= ow, "preprocess_image: bad shape %dx%d -> %dx%d pad %dx%d", h, w,
                   oh, ow, pad_h, pad_w);
-    FRCNN_REQUIRE(h < (1 << 15) && w < (1 << 15) && pad_h < (1 << 15) && pad_w < (1 << 15), "preprocess_image: frame too large");
+    FRCNN_REQUIRE(in_side_ok(h) && in_side_ok(w) && in_side_ok(pad_h) && in_side_ok(pad_w), "preprocess_image: frame too large");
     FRCNN_REQUIRE(src_hwc && mean_host && std_host && (out_chw || out_u8) && workspace, "preprocess_image: NULL pointer");
     for (int c = 0; c < 3; ++c) FRCNN_REQUIRE(std_host[c] != 0.0f, "preprocess_image: std[%d] == 0", c);
     PreWs p = pre_ws_layout(workspace, h, w, oh, ow);
@@ -118,12 +108,11 @@ FRCNN_EXPORT int frcnn_preprocess_image(const uint8_t *src_hwc, int h, int w, in
     hipStream_t s = (hipStream_t)stream;
     NormConst nc;
     for (int c = 0; c < 3; ++c) { nc.mean[c] = mean_host[c]; nc.std[c] = std_host[c]; }
-    FRCNN_LAUNCH(resample_coeffs_kernel, dim3((unsigned)((ow + oh + 255) / 256)), dim3(256), 0, s, w, ow, p.ksx, p.bx, p.kx, h, oh,
-                 p.ksy, p.by, p.ky);
+    FRCNN_LAUNCH(resample_coeffs_kernel, dim3((unsigned)((ow + oh + 255) / 256)), dim3(256), 0, s, w, ow, p.x, h, oh, p.y);
     FRCNN_LAUNCH(resample_h_kernel, dim3((unsigned)((ow + 255) / 256), (unsigned)h), dim3(256), 0, s, src_hwc, h, w, flip ? 1 : 0, ow,
-                 p.ksx, p.bx, p.kx, p.tmp);
+                 p.x, p.tmp);
     FRCNN_LAUNCH(resample_v_norm_kernel, dim3((unsigned)((pad_w + 255) / 256), (unsigned)(out_chw ? pad_h : oh)), dim3(256), 0, s,
-                 p.tmp, oh, ow, pad_h, pad_w, p.ksy, p.by, p.ky, nc, out_chw, out_u8);
+                 p.tmp, oh, ow, pad_h, pad_w, p.y, nc, out_chw, out_u8);
     FRCNN_CHECK_LAUNCH("preprocess kernels");
     return FRCNN_OK;
 }

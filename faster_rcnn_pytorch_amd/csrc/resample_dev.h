@@ -1,6 +1,7 @@
-// resample_dev.h -- Pillow's 8-bit separable bilinear resampler, the pieces preprocess.hip, mosaic.hip and crop.hip share: the window size, one
-// output index's coefficient window in fp64 (IEEE +,-,*,/ only -> the same integers as the CPU), one 3-channel window sum, the clip.
-// Everything past the coefficients is 32-bit integer arithmetic, so every user of these functions produces Pillow's bytes.
+// resample_dev.h -- the arithmetic of Pillow's 8-bit separable bilinear resampler: the window size, one output index's coefficient
+// window in fp64 (IEEE +,-,*,/ only -> the same integers as the CPU), one 3-channel window sum, the clip.  Everything past the
+// coefficients is 32-bit integer arithmetic, so every user of these functions produces Pillow's bytes.  The transforms reach them
+// through input_dev.h (the window table of an axis, one output pixel of a pass).
 #pragma once
 #include "frcnn_common.h"
 #include <cmath>
@@ -20,8 +21,7 @@ static inline int rs_ksize_host(int in_size, int out_size)
 // Output index i of an in_size -> out_size resize: bounds[2i] = first source index, bounds[2i + 1] = number of taps (<= the window size of
 // this shape), kk[i * ks .. i * ks + ks) = the 22-bit fixed-point weights, zero past the taps.  ks is the row stride of the table: at
 // least the window size of the shape (a table sized for a larger shape may hold a smaller one).
-// rs_coeffs_at writes the window of output index i to a row of the caller's choice (bounds2[0..2), kk_row[0..ks)): crop.hip keeps a
-// table of the region's rows only.
+// rs_coeffs_at writes the window of output index i to a row of the caller's choice (bounds2[0..2), kk_row[0..ks)).
 __device__ __forceinline__ void rs_coeffs_at(int i, int in_size, int out_size, int ks, int32_t *__restrict__ bounds2, int32_t *__restrict__ kk_row)
 {
     const double scale = (double)in_size / (double)out_size;
@@ -52,11 +52,6 @@ __device__ __forceinline__ void rs_coeffs_at(int i, int in_size, int out_size, i
     }
     bounds2[0] = xmin;
     bounds2[1] = xmax;
-}
-
-__device__ __forceinline__ void rs_coeffs_row(int i, int in_size, int out_size, int ks, int32_t *__restrict__ bounds, int32_t *__restrict__ kk)
-{
-    rs_coeffs_at(i, in_size, out_size, ks, bounds + 2 * i, kk + (size_t)i * ks);
 }
 
 __device__ __forceinline__ uint8_t rs_clip8(int32_t v)

@@ -76,9 +76,7 @@ def padded_size(h, w, size_divisible=32):
 
 def preprocess_image(img, out_hw, pad_hw=None, flip=False, mean=IMAGENET_MEAN, std=IMAGENET_STD, want_u8=False):
     """uint8 HWC [h, w, 3] on a HIP device -> float32 [3, pad_h, pad_w] (and optionally the resized uint8 [oh, ow, 3])."""
-    img = _req(img, torch.uint8, "img")
-    if img.dim() != 3 or img.shape[2] != 3:
-        raise ValueError("img must be [h, w, 3] uint8 (HWC RGB), got %s" % (tuple(img.shape),))
+    img = _frame(img)
     h, w = int(img.shape[0]), int(img.shape[1])
     oh, ow = int(out_hw[0]), int(out_hw[1])
     ph, pw = (oh, ow) if pad_hw is None else (int(pad_hw[0]), int(pad_hw[1]))
@@ -161,10 +159,7 @@ def mosaic(imgs, boxes, labels, regions, size, max_size=1333, counts=None):
     frame when no box survives); the result has fixed shapes and a device count, so the call can be captured into a graph."""
     if len(imgs) != 4:
         raise ValueError("mosaic takes four frames, got %d" % len(imgs))
-    imgs = [_req(im, torch.uint8, "imgs[%d]" % k) for k, im in enumerate(imgs)]
-    for im in imgs:
-        if im.dim() != 3 or im.shape[2] != 3:
-            raise ValueError("every frame must be [h, w, 3] uint8 (HWC RGB), got %s" % (tuple(im.shape),))
+    imgs = [_frame(im, "imgs[%d]" % k) for k, im in enumerate(imgs)]
     dev = imgs[0].device
     if counts is None:
         if len(boxes) != 4 or len(labels) != 4:
