@@ -7,9 +7,10 @@
 //   rpn_match_kernel  : device-RNG mode (the product's default): column maxima -> grid barrier -> labels + Philox keys + key histogram
 //                       -> (N <= 24 576) the last workgroup finishes the sampling: ONE launch; FPN size: + rpn_apply_kernel.
 //                       The IoU matrix is never materialised.
-//   rpn_colmax_kernel -> rpn_label_kernel -> rpn_sample_kernel : the staged form (parity mode: the sampler consumes the reference's
-//                       permutations; also device-RNG with a radix select, kept behind FRCNN_RPN_FUSED=0 / FRCNN_RPN_SAMPLE=block)
-//   rpn_samp_hist / rpn_samp_apply : the staged chip-wide sampler for grids that cannot be co-resident
+//   rpn_colmax_kernel -> rpn_label_kernel -> rpn_sample_kernel : the staged form of parity mode (the sampler consumes the reference's
+//                       permutations)
+//   rpn_colmax_kernel -> rpn_label_kernel<KEYS> -> rpn_apply_kernel : the staged form of device-RNG mode, for grids that cannot be
+//                       co-resident (and FRCNN_RPN_FUSED=0): the same labelling body and the same sampler as rpn_match_kernel
 //   head_targets_kernel: one workgroup does IoU + ordered compaction + sampling (key histogram + boundary-bin ranking) + encode for
 //                       <= 4096 candidates and writes the fixed [total] rows.
 // Sampling semantics in device-RNG mode: keep the candidates with the smallest (Philox4x32-10 key, position) pairs = the reference's
@@ -23,8 +24,8 @@
 FRCNN_LAYOUT_STAMP(targets);
 
 #define EPS_JACCARD 1e-5f
-#define RS_LDS_MAX 24576              // rpn_sample_kernel keeps the Philox keys of up to this many anchors in LDS (96 KB); also the largest N
-                                      // whose sampling the last workgroup of rpn_match_kernel finishes itself (one sweep round of 24 per thread)
+#define RS_LDS_MAX 24576              // the INLINE bound: the largest N whose sampling the last workgroup of rpn_match_kernel finishes itself
+                                      // (one sweep round of 24 anchors per thread)
 
 // IoU of candidate box `b` against gt `g` in the operand order of the reference variant
 __device__ __forceinline__ float iou_variant(int variant, float4 b, float4 g)
@@ -96,37 +97,75 @@ __global__ __launch_bounds__(256) void rpn_colmax_kernel(int variant, const floa
     }
 }
 
+// The labelling of one anchor that lies inside the image (models/model_.py:205-224): label (1 positive, 0 negative, -1 neither) from its
+// own IoU row and the final column maxima; *arg = its best GT box, which the caller encodes the regression target against (with the
+// encode in here the compiler schedules rpn_match_kernel differently; this way its code is what it was with the body written out).
+// AGENT: colkey was written by other workgroups of the SAME launch (agent-scope loads); otherwise by an earlier launch (plain loads).
+template <bool AGENT>
+__device__ __forceinline__ int rpn_label_anchor(int variant, float4 a, int i, const float4 *__restrict__ gt, int G,
+                                                const unsigned long long *__restrict__ colkey, int *arg_out)
+{
+    float best = -__builtin_inff();
+    int arg = 0;
+    bool match = false;
+    for (int g = 0; g < G; ++g) {
+        const float v = iou_variant(variant, a, gt[g]);
+        if (v > best) { best = v; arg = g; }
+        const unsigned long long *p = &colkey[(size_t)g * CK_STRIDE];
+        const unsigned long long ck = AGENT ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *p;
+        if (variant == 1) match |= (v == __uint_as_float((unsigned)(ck >> 32))) && ck != 0ull;
+        else match |= (0xFFFFFFFFu - (unsigned)ck) == (unsigned)i && ck != 0ull;
+    }
+    int lab = -1;
+    if (best < 0.3f) lab = 0;
+    if (match) lab = 1;
+    if (best >= 0.7f) lab = 1;
+    *arg_out = arg;
+    return lab;
+}
+
+// The device-RNG sampler's state (rpn_match_kernel below describes the scheme)
+#define RSB 2048                          // bins of the key histogram (top 11 bits)
+#define RPN_BL_CAP 4096                   // boundary-bin list capacity per class (expected length n / 2048)
+struct RpnSel2 { unsigned hist[2][RSB]; unsigned nb[2]; unsigned pad[14]; };          // [class 0 = neg, 1 = pos]; zero between calls
+struct RpnBList { unsigned long long e[2][RPN_BL_CAP]; };                             // (key << 32 | anchor index) of the boundary bin's candidates
+
+// KEYS (the staged form of device-RNG mode): the sampler's first half as in phase 2 of rpn_match_kernel -- the anchor's Philox key and
+// the key histogram -- for rpn_apply_kernel, the next launch.  (seed, offset) come from the snapshot rpn_colmax_kernel took, if given.
+template <bool KEYS>
 __global__ __launch_bounds__(256) void rpn_label_kernel(int variant, const float4 *__restrict__ anchors, int N,
                                                         const float4 *__restrict__ gt, int G,
                                                         const unsigned long long *__restrict__ colkey,
+                                                        unsigned long long seed, unsigned long long offset, const unsigned long long *__restrict__ philox_snap,
                                                         int64_t *__restrict__ out_cls, float4 *__restrict__ out_reg,
-                                                        int8_t *__restrict__ label8, int32_t *__restrict__ counts)
+                                                        int8_t *__restrict__ label8, unsigned *__restrict__ keys, RpnSel2 *__restrict__ sel,
+                                                        int32_t *__restrict__ counts)
 {
     __shared__ int s_cnt[2][4];
+    __shared__ unsigned s_hist[KEYS ? 2 * RSB : 1];
     const int i = blockIdx.x * 256 + threadIdx.x;
+    if constexpr (KEYS) {
+        if (philox_snap) { seed = philox_snap[0]; offset = philox_snap[1]; }
+        for (int b = threadIdx.x; b < 2 * RSB; b += 256) s_hist[b] = 0u;
+        __syncthreads();
+    }
     int lab = -1;
     if (i < N) {
         const float4 a = anchors[i];
         float4 reg = make_float4(0.f, 0.f, 0.f, 0.f);
         if (variant == 1 || anchor_inside(a)) {
-            float best = -__builtin_inff();
-            int arg = 0;
-            bool match = false;
-            for (int g = 0; g < G; ++g) {
-                const float v = iou_variant(variant, a, gt[g]);
-                if (v > best) { best = v; arg = g; }
-                const unsigned long long ck = colkey[(size_t)g * CK_STRIDE];
-                if (variant == 1) match |= (v == __uint_as_float((unsigned)(ck >> 32))) && ck != 0ull;
-                else match |= (0xFFFFFFFFu - (unsigned)ck) == (unsigned)i && ck != 0ull;
-            }
-            if (best < 0.3f) lab = 0;
-            if (match) lab = 1;
-            if (best >= 0.7f) lab = 1;
+            int arg;
+            lab = rpn_label_anchor<false>(variant, a, i, gt, G, colkey, &arg);
             reg = encode4(xy_to_cxcy4(gt[arg]), xy_to_cxcy4(a));
         }
         out_cls[i] = lab;
         out_reg[i] = reg;
         label8[i] = (int8_t)lab;
+        if (KEYS && lab >= 0) {
+            const unsigned k = philox_first(seed, offset, (unsigned)lab, (unsigned)i);
+            keys[i] = k;
+            atomicAdd(&s_hist[lab * RSB + (k >> 21)], 1u);
+        }
     }
     // block counts of positives / negatives
     const unsigned long long bp = __ballot(lab == 1), bn = __ballot(lab == 0);
@@ -136,6 +175,11 @@ __global__ __launch_bounds__(256) void rpn_label_kernel(int variant, const float
         const int c = s_cnt[threadIdx.x][0] + s_cnt[threadIdx.x][1] + s_cnt[threadIdx.x][2] + s_cnt[threadIdx.x][3];
         if (c) atomicAdd(&counts[threadIdx.x], c);
     }
+    if constexpr (KEYS)
+        for (int b = threadIdx.x; b < 2 * RSB; b += 256) {
+            const unsigned v = s_hist[b];
+            if (v) atomicAdd(&(&sel->hist[0][0])[b], v);
+        }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -231,26 +275,22 @@ __device__ void block_radix_select(int n, int keep, KeyFn key_of, FlagFn is_cand
 }
 
 // ------------------------------------------------------------------------------------------------
-// rpn_sample_kernel: models/model_.py:225-236
+// rpn_sample_kernel (parity mode, one workgroup): models/model_.py:225-236 with the reference's permutations
 //   if n_pos > 128: label[pos_indices[perm[128:]]] = -1
 //   if n_neg > 256 - n_pos: label[neg_indices[perm[(256 - min(n_pos,128)):]]] = -1
+// `list` (N ints of workspace) receives a class's candidates in ascending anchor order: what perm indexes.
 // ------------------------------------------------------------------------------------------------
-struct RpnSampleLds { int s_w[17]; unsigned s_hist[16 * 256]; unsigned s_pref[4]; int s_cnt; unsigned s_keys[RS_LDS_MAX]; };
-
-__device__ __forceinline__ void rpn_sample_body(RpnSampleLds &L, int N, int8_t *__restrict__ label8, int64_t *__restrict__ out_cls,
-                                                const int64_t *__restrict__ perm_pos, int n_perm_pos,
-                                                const int64_t *__restrict__ perm_neg, int n_perm_neg,
-                                                unsigned long long seed, unsigned long long offset,
-                                                int32_t *__restrict__ list, unsigned *__restrict__ keys,
-                                                int32_t *__restrict__ counts)
+__global__ __launch_bounds__(1024) void rpn_sample_kernel(int N, const int8_t *__restrict__ label8, int64_t *__restrict__ out_cls,
+                                                          const int64_t *__restrict__ perm_pos, int n_perm_pos,
+                                                          const int64_t *__restrict__ perm_neg, int n_perm_neg,
+                                                          int32_t *__restrict__ list, int32_t *__restrict__ counts)
 {
-    int *s_w = L.s_w; unsigned *s_hist = L.s_hist; unsigned *s_pref = L.s_pref; int &s_cnt = L.s_cnt; unsigned *s_keys = L.s_keys;
+    __shared__ int s_w[17];
     const int n_pos = counts[0], n_neg = counts[1];
     const int np_eff = min(n_pos, 128);
     const bool drop_pos = n_pos > 128;
     const bool drop_neg = n_neg > 256 - n_pos;
     if (!drop_pos && !drop_neg) return;
-    const bool host_mode = (perm_pos != nullptr) || (perm_neg != nullptr);
     const int chunk = (N + 1023) / 1024;
     const int lo = threadIdx.x * chunk, hi = min(lo + chunk, N);
 
@@ -260,116 +300,28 @@ __device__ __forceinline__ void rpn_sample_body(RpnSampleLds &L, int N, int8_t *
         const int n_c = cls_id == 1 ? n_pos : n_neg;
         const int keep = cls_id == 1 ? 128 : 256 - np_eff;
         const int8_t want = (int8_t)cls_id;
-        if (host_mode) {
-            const int64_t *perm = cls_id == 1 ? perm_pos : perm_neg;
-            const int n_perm = cls_id == 1 ? n_perm_pos : n_perm_neg;
-            if (perm == nullptr || n_perm != n_c) {         // uniform
-                if (threadIdx.x == 0) counts[2] = 1;
-                continue;
-            }
-            // ordered compaction (ascending index): contiguous ownership + block scan
-            int c = 0;
-            for (int i = lo; i < hi; ++i) c += label8[i] == want;
-            int tot;
-            int base = block_excl_scan_1024(c, s_w, &tot);
-            for (int i = lo; i < hi; ++i)
-                if (label8[i] == want) list[base++] = i;
-            __syncthreads();
-            for (int j = keep + threadIdx.x; j < n_c; j += 1024) {
-                const int64_t p = perm[j];
-                if (p >= 0 && p < n_c) { const int i = list[p]; out_cls[i] = -1; }
-                else counts[2] = 2;
-            }
-            __syncthreads();
-            // label8 is stale for the demoted entries from here on; the negative pass only looks at label 0
-        } else {
-            const unsigned stream_id = (unsigned)cls_id;
-            if (N <= RS_LDS_MAX) {
-                // compact the candidates (any order) into LDS keys + a global index list, then select in LDS
-                if (threadIdx.x == 0) s_cnt = 0;
-                __syncthreads();
-                for (int i0 = 0; i0 < N; i0 += 1024 * 8) {
-                    int8_t lab[8];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        const int i = i0 + u * 1024 + threadIdx.x;
-                        lab[u] = i < N ? label8[i] : (int8_t)-2;
-                    }
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        const int i = i0 + u * 1024 + threadIdx.x;
-                        const bool c = lab[u] == want;
-                        const unsigned long long bm = __ballot(c);
-                        if (bm != 0ull) {
-                            int base = 0;
-                            if ((threadIdx.x & 63) == 0) base = atomicAdd(&s_cnt, __builtin_popcountll(bm));
-                            base = __shfl(base, 0);
-                            if (c) {
-                                const int slot = base + __builtin_popcountll(bm & ((1ull << (threadIdx.x & 63)) - 1ull));
-                                s_keys[slot] = philox_first(seed, offset, stream_id, (unsigned)i);
-                                list[slot] = i;
-                            }
-                        }
-                    }
-                }
-                __syncthreads();
-                const int m = s_cnt;                         // == n_c
-                unsigned T; int rem, n_eq;
-                block_radix_select(m, keep, [&](int q) { return s_keys[q]; }, [&](int) { return true; }, s_hist, s_pref, &T, &rem, &n_eq);
-                for (int q = threadIdx.x; q < m; q += 1024) {
-                    const unsigned k = s_keys[q];
-                    bool kept = k < T;
-                    if (k == T) {
-                        if (rem == n_eq) kept = true;
-                        else {                               // rare: ties straddle the threshold -> first `rem` by anchor index stay
-                            const int me = list[q];
-                            int before = 0;
-                            for (int o = 0; o < m; ++o) before += (s_keys[o] == T && list[o] < me);
-                            kept = before < rem;
-                        }
-                    }
-                    if (!kept) out_cls[list[q]] = -1;
-                }
-                __syncthreads();
-                continue;
-            }
-            for (int i = threadIdx.x; i < N; i += 1024)
-                if (label8[i] == want) keys[i] = philox_first(seed, offset, stream_id, (unsigned)i);
-            __syncthreads();
-            unsigned T; int rem, n_eq;
-            block_radix_select(N, keep, [&](int i) { return keys[i]; }, [&](int i) { return label8[i] == want; }, s_hist, s_pref, &T, &rem, &n_eq);
-            if (rem == n_eq) {                               // no tie straddles the threshold (the common case)
-                for (int i = threadIdx.x; i < N; i += 1024)
-                    if (label8[i] == want && keys[i] > T) out_cls[i] = -1;
-            } else {                                         // ties at T: the first `rem` in index order stay
-                int c = 0;
-                for (int i = lo; i < hi; ++i) c += (label8[i] == want && keys[i] == T);
-                int tot;
-                int base = block_excl_scan_1024(c, s_w, &tot);
-                for (int i = lo; i < hi; ++i)
-                    if (label8[i] == want) {
-                        const unsigned k = keys[i];
-                        bool kept = k < T;
-                        if (k == T) { kept = base < rem; ++base; }
-                        if (!kept) out_cls[i] = -1;
-                    }
-            }
-            __syncthreads();
+        const int64_t *perm = cls_id == 1 ? perm_pos : perm_neg;
+        const int n_perm = cls_id == 1 ? n_perm_pos : n_perm_neg;
+        if (perm == nullptr || n_perm != n_c) {             // uniform
+            if (threadIdx.x == 0) counts[2] = 1;
+            continue;
         }
+        // ordered compaction (ascending index): contiguous ownership + block scan
+        int c = 0;
+        for (int i = lo; i < hi; ++i) c += label8[i] == want;
+        int tot;
+        int base = block_excl_scan_1024(c, s_w, &tot);
+        for (int i = lo; i < hi; ++i)
+            if (label8[i] == want) list[base++] = i;
+        __syncthreads();
+        for (int j = keep + threadIdx.x; j < n_c; j += 1024) {
+            const int64_t p = perm[j];
+            if (p >= 0 && p < n_c) { const int i = list[p]; out_cls[i] = -1; }
+            else counts[2] = 2;
+        }
+        __syncthreads();
+        // label8 is stale for the demoted entries from here on; the negative pass only looks at label 0
     }
-}
-
-__global__ __launch_bounds__(1024) void rpn_sample_kernel(int N, int8_t *__restrict__ label8, int64_t *__restrict__ out_cls,
-                                                          const int64_t *__restrict__ perm_pos, int n_perm_pos,
-                                                          const int64_t *__restrict__ perm_neg, int n_perm_neg,
-                                                          unsigned long long seed, unsigned long long offset,
-                                                          const unsigned long long *__restrict__ philox_snap,
-                                                          int32_t *__restrict__ list, unsigned *__restrict__ keys,
-                                                          int32_t *__restrict__ counts)
-{
-    __shared__ RpnSampleLds L;
-    if (philox_snap) { seed = philox_snap[0]; offset = philox_snap[1]; }
-    rpn_sample_body(L, N, label8, out_cls, perm_pos, n_perm_pos, perm_neg, n_perm_neg, seed, offset, list, keys, counts);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -421,10 +373,6 @@ extern "C" __attribute__((visibility("default"))) void frcnn_rpn_trace_read(void
 #endif
 #define RPN_BAR_SPINS (1 << 22)
 #define RPN_MAX_G 4096
-#define RSB 2048                          // bins of the key histogram (top 11 bits)
-#define RPN_BL_CAP 4096                   // boundary-bin list capacity per class (expected length n / 2048)
-struct RpnSel2 { unsigned hist[2][RSB]; unsigned nb[2]; unsigned pad[14]; };          // [class 0 = neg, 1 = pos]; zero between calls
-struct RpnBList { unsigned long long e[2][RPN_BL_CAP]; };                             // (key << 32 | anchor index) of the boundary bin's candidates
 
 // ascending search over the 2048-bin histogram: bin of the `want`-th smallest key (1-based), the count below it, the bin's size.
 // Any block size >= 256: threads 0 .. 255 own 8 bins each.  s_tmp: 8 ints.
@@ -639,19 +587,8 @@ __global__ __launch_bounds__(1024) void rpn_match_kernel(int variant, const floa
     if (i < N) {
         float4 reg = make_float4(0.f, 0.f, 0.f, 0.f);
         if (live) {
-            float best = -__builtin_inff();
-            int arg = 0;
-            bool match = false;
-            for (int g = 0; g < G; ++g) {
-                const float v = iou_variant(variant, a, gt[g]);
-                if (v > best) { best = v; arg = g; }
-                const unsigned long long ck = __hip_atomic_load(&colkey[(size_t)g * CK_STRIDE], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (variant == 1) match |= (v == __uint_as_float((unsigned)(ck >> 32))) && ck != 0ull;
-                else match |= (0xFFFFFFFFu - (unsigned)ck) == (unsigned)i && ck != 0ull;
-            }
-            if (best < 0.3f) lab = 0;
-            if (match) lab = 1;
-            if (best >= 0.7f) lab = 1;
+            int arg;
+            lab = rpn_label_anchor<true>(variant, a, i, gt, G, colkey, &arg);
             reg = encode4(xy_to_cxcy4(gt[arg]), xy_to_cxcy4(a));
         }
         // what the sampling workgroup reads back (or overwrites) in the SAME launch goes out write-through: with an acknowledged store
@@ -711,7 +648,8 @@ __global__ __launch_bounds__(1024) void rpn_match_kernel(int variant, const floa
     RPN_T(tid == 0, 6);
 }
 
-// the sampler's second half for FPN-sized N: the sweep chip-wide, the list by the workgroup that finishes last
+// the sampler's second half as a launch of its own (FPN-sized N behind rpn_match_kernel<false>; any N behind rpn_label_kernel<true>):
+// the sweep chip-wide, the list by the workgroup that finishes last
 __global__ __launch_bounds__(1024) void rpn_apply_kernel(int N, const int8_t *__restrict__ label8, const unsigned *__restrict__ keys, RpnCtl *__restrict__ ctl,
                                                          RpnSel2 *__restrict__ sel, RpnBList *__restrict__ bl, int64_t *__restrict__ out_cls,
                                                          int32_t *__restrict__ counts)
@@ -735,129 +673,6 @@ __global__ __launch_bounds__(1024) void rpn_apply_kernel(int N, const int8_t *__
     if (!s_flag) return;
     if (threadIdx.x == 0) __hip_atomic_store(&ctl->ticket2, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     rpn_apply_resolve(cn, cp, sel, bl, out_cls, counts, s_e);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Large N (FPN: 268 569 anchors): the single-workgroup sampler above would sweep the anchors ~6 times from one CU
-// (~0.5 ms).  Device-RNG mode therefore runs as four chip-wide launches: three radix-histogram levels (11 + 11 + 10
-// bits of the Philox key, both classes in the same pass) and an apply pass that demotes every candidate whose key is
-// above the exact threshold.  Each launch re-derives the digit chosen so far from the previous level's histogram.
-// ------------------------------------------------------------------------------------------------
-struct RpnSelCtl { unsigned hist[2][3][RSB]; };          // [class 0 = neg, 1 = pos][level][bin]
-
-// ascending search over a 2048-bin histogram: bin of the `want`-th smallest key (1-based) and the count below it
-__device__ __forceinline__ void find_bin_asc(const unsigned *__restrict__ hist, int nbins, int want, int *s_tmp /*[8]*/, int *bin, int *below, int *inbin)
-{
-    const int t = threadIdx.x;                           // 256 threads x 8 bins
-    unsigned c[8];
-    int local = 0;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) { const int b = 8 * t + q; c[q] = b < nbins ? hist[b] : 0u; local += (int)c[q]; }
-    const int lane = t & 63, wave = t >> 6;
-    int inc = local;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int v = __shfl_up(inc, o);
-        if (lane >= o) inc += v;
-    }
-    __syncthreads();
-    if (lane == 63) s_tmp[wave] = inc;
-    if (t == 0) { s_tmp[4] = 0; s_tmp[5] = 0; s_tmp[6] = 0; s_tmp[7] = 0; }
-    __syncthreads();
-    int base = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) if (w < wave) base += s_tmp[w];
-    const int excl = base + inc - local;
-    if (excl < want && want <= excl + local) {
-        int acc = excl, q = 0;
-        for (; q < 7; ++q) {
-            if (acc + (int)c[q] >= want) break;
-            acc += (int)c[q];
-        }
-        s_tmp[4] = 8 * t + q; s_tmp[5] = acc; s_tmp[6] = 1; s_tmp[7] = (int)c[q];
-    }
-    __syncthreads();
-    *bin = s_tmp[4]; *below = s_tmp[5]; *inbin = s_tmp[7];
-    __syncthreads();
-}
-
-struct RpnSelState { bool drop; int keep; unsigned prefix; int want; int inbin; };
-
-// what is known about class `c` after `levels` histogram levels
-__device__ __forceinline__ RpnSelState rpn_sel_state(const RpnSelCtl *ctl, const int32_t *counts, int c, int levels, int *s_tmp)
-{
-    const int n_pos = counts[0], n_neg = counts[1];
-    RpnSelState st;
-    st.drop = c == 1 ? (n_pos > 128) : (n_neg > 256 - n_pos);
-    st.keep = c == 1 ? 128 : 256 - min(n_pos, 128);
-    st.prefix = 0u; st.want = st.keep; st.inbin = 0;
-    for (int l = 0; l < levels; ++l) {                   // uniform
-        int bin, below, inbin;
-        find_bin_asc(ctl->hist[c][l], l < 2 ? 2048 : 1024, st.want, s_tmp, &bin, &below, &inbin);
-        st.prefix |= (unsigned)bin << (l == 0 ? 21 : (l == 1 ? 10 : 0));
-        st.want -= below;
-        st.inbin = inbin;
-    }
-    return st;
-}
-
-template <int LEVEL>
-__global__ __launch_bounds__(256) void rpn_samp_hist_kernel(const int8_t *__restrict__ label8, int N, unsigned long long seed,
-                                                            unsigned long long offset, const unsigned long long *__restrict__ philox_snap,
-                                                            RpnSelCtl *__restrict__ ctl, const int32_t *__restrict__ counts)
-{
-    if (philox_snap) { seed = philox_snap[0]; offset = philox_snap[1]; }
-    __shared__ unsigned s_hist[2][RSB];
-    __shared__ int s_tmp[8];
-    const RpnSelState sn = rpn_sel_state(ctl, counts, 0, LEVEL, s_tmp);
-    const RpnSelState sp = rpn_sel_state(ctl, counts, 1, LEVEL, s_tmp);
-    if (!sn.drop && !sp.drop) return;
-    for (int i = threadIdx.x; i < 2 * RSB; i += 256) (&s_hist[0][0])[i] = 0u;
-    __syncthreads();
-    const unsigned himask = LEVEL == 0 ? 0u : (LEVEL == 1 ? 0xFFE00000u : 0xFFFFFC00u);
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < N; i += gridDim.x * 256) {
-        const int lab = label8[i];
-        if (lab < 0 || !(lab == 1 ? sp.drop : sn.drop)) continue;
-        const unsigned k = philox_first(seed, offset, (unsigned)lab, (unsigned)i);
-        if ((k & himask) != (lab == 1 ? sp.prefix : sn.prefix)) continue;
-        const unsigned d = LEVEL == 0 ? (k >> 21) : (LEVEL == 1 ? ((k >> 10) & 2047u) : (k & 1023u));
-        atomicAdd(&s_hist[lab][d], 1u);
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < 2 * RSB; i += 256) {
-        const unsigned v = (&s_hist[0][0])[i];
-        if (v) atomicAdd(&ctl->hist[i / RSB][LEVEL][i % RSB], v);
-    }
-}
-
-__global__ __launch_bounds__(256) void rpn_samp_apply_kernel(const int8_t *__restrict__ label8, int N, unsigned long long seed,
-                                                             unsigned long long offset, const unsigned long long *__restrict__ philox_snap,
-                                                             const RpnSelCtl *__restrict__ ctl,
-                                                             const int32_t *__restrict__ counts, int64_t *__restrict__ out_cls)
-{
-    if (philox_snap) { seed = philox_snap[0]; offset = philox_snap[1]; }
-    __shared__ int s_tmp[8];
-    const RpnSelState sn = rpn_sel_state(ctl, counts, 0, 3, s_tmp);      // prefix = exact threshold key T, want = #(key == T) to keep
-    const RpnSelState sp = rpn_sel_state(ctl, counts, 1, 3, s_tmp);
-    if (!sn.drop && !sp.drop) return;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < N; i += gridDim.x * 256) {
-        const int lab = label8[i];
-        if (lab < 0) continue;
-        const RpnSelState &st = lab == 1 ? sp : sn;
-        if (!st.drop) continue;
-        const unsigned k = philox_first(seed, offset, (unsigned)lab, (unsigned)i);
-        bool kept = k < st.prefix;
-        if (k == st.prefix) {
-            kept = true;
-            if (st.want != st.inbin) {                   // a 32-bit key tie straddles the threshold (p ~ N / 2^32): lowest indices stay
-                int before = 0;
-                for (int j = 0; j < i; ++j)
-                    before += (label8[j] == lab && philox_first(seed, offset, (unsigned)lab, (unsigned)j) == k);
-                kept = before < st.want;
-            }
-        }
-        if (!kept) out_cls[i] = -1;
-    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1068,7 +883,7 @@ __global__ __launch_bounds__(1024) void head_targets_kernel(int variant, const f
 // ------------------------------------------------------------------------------------------------
 // host launchers
 // ------------------------------------------------------------------------------------------------
-struct RpnWs { unsigned long long *colkey, *colkey2, *snap; RpnCtl *ctl; RpnSel2 *sel2; RpnBList *bl; int8_t *label8; int32_t *list; unsigned *keys; RpnSelCtl *sel; size_t total; };
+struct RpnWs { unsigned long long *colkey, *colkey2, *snap; RpnCtl *ctl; RpnSel2 *sel2; RpnBList *bl; int8_t *label8; int32_t *list; unsigned *keys; size_t total; };
 static RpnWs carve_rpn(void *ws, int64_t N, int64_t G)
 {
     RpnWs w; char *p = (char *)ws; size_t o = 0;
@@ -1078,14 +893,13 @@ static RpnWs carve_rpn(void *ws, int64_t N, int64_t G)
     w.ctl = (RpnCtl *)take(sizeof(RpnCtl));
     w.snap = (unsigned long long *)take(16);
     w.colkey = (unsigned long long *)take((size_t)RPN_MAX_G * 8 * 8);
-    w.sel2 = (RpnSel2 *)take(sizeof(RpnSel2));                      // the fused sampler's key histogram + list counters: zero between calls
+    w.sel2 = (RpnSel2 *)take(sizeof(RpnSel2));                      // the sampler's key histogram + list counters: zero between calls
     w.bl = (RpnBList *)take(sizeof(RpnBList));
-    w.colkey2 = (unsigned long long *)take((size_t)G * 8 * 8);      // the staged (three-launch) path's own maxima: cleared per call, so that
+    w.colkey2 = (unsigned long long *)take((size_t)G * 8 * 8);      // the staged paths' own maxima: cleared per call, so that
                                                                     // the fused kernel's colkey keeps its "zero between calls" invariant
     w.label8 = (int8_t *)take((size_t)N);
-    w.list = (int32_t *)take((size_t)N * 4);
-    w.keys = (unsigned *)take((size_t)N * 4);
-    w.sel = (RpnSelCtl *)take(sizeof(RpnSelCtl));
+    w.list = (int32_t *)take((size_t)N * 4);                        // parity mode: the candidates in anchor order
+    w.keys = (unsigned *)take((size_t)N * 4);                       // device-RNG mode: the Philox keys
     w.total = o;
     return w;
 }
@@ -1106,56 +920,53 @@ FRCNN_EXPORT int frcnn_rpn_targets(int variant, const float *anchors, int64_t N,
     RpnWs w = carve_rpn(workspace, N, G);
     if (workspace_bytes < w.total) return frcnn_set_error(FRCNN_ERR_WORKSPACE, "rpn_targets: workspace %zu < %zu bytes", workspace_bytes, w.total);
     hipStream_t s = (hipStream_t)stream;
-    static const bool force_block = [] { const char *e = getenv("FRCNN_RPN_SAMPLE"); return e && !strcmp(e, "block"); }();   // tests: old path
     static const int n_cus = [] {
         int dev = 0, cus = 256;
         if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
         return cus;
     }();
     static const bool no_fuse = [] { const char *e = getenv("FRCNN_RPN_FUSED"); return e && !strcmp(e, "0"); }();
+    const bool device_rng = !perm_pos && !perm_neg;
     const int64_t nb1024 = (N + 1023) / 1024;
-    if (!perm_pos && !perm_neg && !no_fuse && !force_block) {
-        // device-RNG mode: ONE launch for column maxima, labels and (N <= 24 576) sampling, two above; every workgroup must be
-        // resident for the in-kernel barrier: two 1024-thread workgroups per CU (at most 57 KB of LDS each)
+    const int ga = (int)(nb1024 < n_cus ? nb1024 : n_cus);              // rpn_apply_kernel's grid
+    // device-RNG mode: ONE launch for column maxima, labels and (N <= 24 576) sampling, two above; every workgroup must be
+    // resident for the in-kernel barrier: two 1024-thread workgroups per CU (at most 57 KB of LDS each)
+    if (device_rng && !no_fuse && nb1024 <= 2 * n_cus) {
         const bool inl = N <= RS_LDS_MAX;                               // the last workgroup finishes the sampling itself
-        if (nb1024 <= 2 * n_cus) {
-            if (inl)
-                FRCNN_LAUNCH(rpn_match_kernel<true>, dim3((unsigned)nb1024), dim3(1024), 0, s, variant, (const float4 *)anchors, (int)N, (const float4 *)gt, (int)G,
-                             w.colkey, w.ctl, w.sel2, w.bl, (unsigned long long)seed, (unsigned long long)offset, (unsigned long long *)philox_state_dev, out_cls,
-                             (float4 *)out_reg, w.label8, w.keys, out_counts);
-            else
-                FRCNN_LAUNCH(rpn_match_kernel<false>, dim3((unsigned)nb1024), dim3(1024), 0, s, variant, (const float4 *)anchors, (int)N, (const float4 *)gt, (int)G,
-                             w.colkey, w.ctl, w.sel2, w.bl, (unsigned long long)seed, (unsigned long long)offset, (unsigned long long *)philox_state_dev, out_cls,
-                             (float4 *)out_reg, w.label8, w.keys, out_counts);
-            FRCNN_CHECK_LAUNCH("rpn_match_kernel");
-            if (inl) return FRCNN_OK;
-            const int ga = (int)(nb1024 < n_cus ? nb1024 : n_cus);
-            FRCNN_LAUNCH(rpn_apply_kernel, dim3((unsigned)ga), dim3(1024), 0, s, (int)N, w.label8, w.keys, w.ctl, w.sel2, w.bl, out_cls, out_counts);
-            FRCNN_CHECK_LAUNCH("rpn_apply_kernel");
-            return FRCNN_OK;
-        }
+        if (inl)
+            FRCNN_LAUNCH(rpn_match_kernel<true>, dim3((unsigned)nb1024), dim3(1024), 0, s, variant, (const float4 *)anchors, (int)N, (const float4 *)gt, (int)G,
+                         w.colkey, w.ctl, w.sel2, w.bl, (unsigned long long)seed, (unsigned long long)offset, (unsigned long long *)philox_state_dev, out_cls,
+                         (float4 *)out_reg, w.label8, w.keys, out_counts);
+        else
+            FRCNN_LAUNCH(rpn_match_kernel<false>, dim3((unsigned)nb1024), dim3(1024), 0, s, variant, (const float4 *)anchors, (int)N, (const float4 *)gt, (int)G,
+                         w.colkey, w.ctl, w.sel2, w.bl, (unsigned long long)seed, (unsigned long long)offset, (unsigned long long *)philox_state_dev, out_cls,
+                         (float4 *)out_reg, w.label8, w.keys, out_counts);
+        FRCNN_CHECK_LAUNCH("rpn_match_kernel");
+        if (inl) return FRCNN_OK;
+        FRCNN_LAUNCH(rpn_apply_kernel, dim3((unsigned)ga), dim3(1024), 0, s, (int)N, w.label8, w.keys, w.ctl, w.sel2, w.bl, out_cls, out_counts);
+        FRCNN_CHECK_LAUNCH("rpn_apply_kernel");
+        return FRCNN_OK;
     }
+    // the staged form: column maxima and labels as launches of their own, then the mode's sampler
     if (hipMemsetAsync(w.colkey2, 0, (size_t)G * 8 * 8, s) != hipSuccess) return frcnn_set_error(FRCNN_ERR_LAUNCH, "rpn_targets: memset failed");
     const dim3 grid((unsigned)((N + 255) / 256)), block(256);
     FRCNN_LAUNCH(rpn_colmax_kernel, grid, block, 0, s, variant, (const float4 *)anchors, (int)N, (const float4 *)gt,
                  (int)G, w.colkey2, out_counts, (unsigned long long *)philox_state_dev, w.snap);
     FRCNN_CHECK_LAUNCH("rpn_colmax_kernel");
-    const unsigned long long *snap = philox_state_dev ? w.snap : nullptr;
-    FRCNN_LAUNCH(rpn_label_kernel, grid, block, 0, s, variant, (const float4 *)anchors, (int)N, (const float4 *)gt, (int)G,
-                 w.colkey2, out_cls, (float4 *)out_reg, w.label8, out_counts);
-    FRCNN_CHECK_LAUNCH("rpn_label_kernel");
-    if (N > RS_LDS_MAX && !perm_pos && !perm_neg && !force_block) {     // chip-wide device-RNG sampler for FPN-sized N
-        if (hipMemsetAsync(w.sel, 0, sizeof(RpnSelCtl), s) != hipSuccess) return frcnn_set_error(FRCNN_ERR_LAUNCH, "rpn_targets: memset failed");
-        const int gb = (int)((N + 2047) / 2048) < 1024 ? (int)((N + 2047) / 2048) : 1024;
-        FRCNN_LAUNCH(rpn_samp_hist_kernel<0>, dim3(gb), dim3(256), 0, s, w.label8, (int)N, (unsigned long long)seed, (unsigned long long)offset, snap, w.sel, out_counts);
-        FRCNN_LAUNCH(rpn_samp_hist_kernel<1>, dim3(gb), dim3(256), 0, s, w.label8, (int)N, (unsigned long long)seed, (unsigned long long)offset, snap, w.sel, out_counts);
-        FRCNN_LAUNCH(rpn_samp_hist_kernel<2>, dim3(gb), dim3(256), 0, s, w.label8, (int)N, (unsigned long long)seed, (unsigned long long)offset, snap, w.sel, out_counts);
-        FRCNN_LAUNCH(rpn_samp_apply_kernel, dim3(gb), dim3(256), 0, s, w.label8, (int)N, (unsigned long long)seed, (unsigned long long)offset, snap, w.sel, out_counts, out_cls);
-        FRCNN_CHECK_LAUNCH("rpn_samp kernels");
+    if (device_rng) {
+        FRCNN_LAUNCH(rpn_label_kernel<true>, grid, block, 0, s, variant, (const float4 *)anchors, (int)N, (const float4 *)gt, (int)G, w.colkey2,
+                     (unsigned long long)seed, (unsigned long long)offset, philox_state_dev ? w.snap : nullptr, out_cls, (float4 *)out_reg, w.label8, w.keys,
+                     w.sel2, out_counts);
+        FRCNN_CHECK_LAUNCH("rpn_label_kernel");
+        FRCNN_LAUNCH(rpn_apply_kernel, dim3((unsigned)ga), dim3(1024), 0, s, (int)N, w.label8, w.keys, w.ctl, w.sel2, w.bl, out_cls, out_counts);
+        FRCNN_CHECK_LAUNCH("rpn_apply_kernel");
         return FRCNN_OK;
     }
+    FRCNN_LAUNCH(rpn_label_kernel<false>, grid, block, 0, s, variant, (const float4 *)anchors, (int)N, (const float4 *)gt, (int)G, w.colkey2,
+                 0ull, 0ull, nullptr, out_cls, (float4 *)out_reg, w.label8, nullptr, nullptr, out_counts);
+    FRCNN_CHECK_LAUNCH("rpn_label_kernel");
     FRCNN_LAUNCH(rpn_sample_kernel, dim3(1), dim3(1024), 0, s, (int)N, w.label8, out_cls, perm_pos, (int)n_perm_pos, perm_neg,
-                 (int)n_perm_neg, (unsigned long long)seed, (unsigned long long)offset, snap, w.list, w.keys, out_counts);
+                 (int)n_perm_neg, w.list, out_counts);
     FRCNN_CHECK_LAUNCH("rpn_sample_kernel");
     return FRCNN_OK;
 }

@@ -322,7 +322,8 @@ int frcnn_affine_act_bwd_mixed(const void *g, int g_dtype, const void *g2_bf16, 
  * out_counts (int32[4], device): {n_pos, n_neg before sampling, error flag, reserved}.
  * workspace: DEDICATED to this entry point and ZERO before the first call.  In device-RNG mode column maxima, labels and (N <= 24 576)
  * sampling run as ONE launch whose workgroups meet at an in-kernel barrier; its arrival counter, last-workgroup ticket and the
- * per-GT maxima live in the workspace and are left zero by every call (no memset node; HIP-graph replays need no clearing).          */
+ * per-GT maxima live in the workspace and are left zero by every call (no memset node; HIP-graph replays need no clearing).  So are
+ * the sampler's key histogram and list counters, which the staged device-RNG form (grids too large to be co-resident) shares.         */
 int frcnn_rpn_targets(int variant, const float *anchors /*[N,4]*/, int64_t N, const float *gt /*[G,4]*/, int64_t G,
                       const int64_t *perm_pos, int64_t n_perm_pos, const int64_t *perm_neg, int64_t n_perm_neg,
                       uint64_t seed, uint64_t offset, uint64_t *philox_state_dev /*[2] device, or NULL*/,

@@ -581,10 +581,10 @@ def test_rpn_targets_device_sampling_properties(ops):
     assert 0.35 < q.mean() < 0.65
 
 
-def test_rpn_targets_device_sampling_fpn_size_chipwide_equals_single_workgroup(ops):
-    """N = 268 569 (config F) takes the chip-wide radix sampler; it must pick exactly what the single-workgroup sampler picks
-    (same Philox keys, same smallest-keys rule), which a child process with FRCNN_RPN_SAMPLE=block provides."""
-    import os, subprocess, sys, tempfile
+def test_rpn_targets_device_sampling_fpn_size_equals_reference_with_philox_permutations(ops):
+    """N = 268 569 (config F) takes rpn_match + rpn_apply; with only the negatives over quota (G = 8) and with both classes over quota
+    (G = 300) it must pick exactly what the oracle picks when it is fed the Philox permutations (oracle/philox_ref.py)."""
+    from oracle import philox_ref
     rng = np.random.RandomState(12)
     shapes = [(200, 336), (100, 168), (50, 84), (25, 42), (13, 21)]
     anchor = orc.tv_anchor_grid(800, 1344, shapes, normalise=True)
@@ -598,14 +598,8 @@ def test_rpn_targets_device_sampling_fpn_size_chipwide_equals_single_workgroup(o
         npe = min(n_pos, 128)
         assert (a == 1).sum() == npe and (a == 0).sum() == min(n_neg, 256 - npe), tag
         assert ((a == 1) <= (pre == 1)).all() and ((a == 0) <= (pre == 0)).all()
-        with tempfile.TemporaryDirectory() as d:
-            np.save(os.path.join(d, "anchor.npy"), anchor), np.save(os.path.join(d, "gt.npy"), gt)
-            code = ("import numpy as np, torch, sys; from faster_rcnn_pytorch_amd import ops;"
-                    "d=sys.argv[1]; a=torch.from_numpy(np.load(d+'/anchor.npy')).cuda(); g=torch.from_numpy(np.load(d+'/gt.npy')).cuda();"
-                    "np.save(d+'/out.npy', ops.rpn_targets(a, g, variant=1, seed=77, offset=5)[0].cpu().numpy())")
-            env = dict(os.environ, FRCNN_RPN_SAMPLE="block", PYTHONPATH=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-            subprocess.run([sys.executable, "-c", code, d], check=True, env=env, timeout=300)
-            assert np.array_equal(a, np.load(os.path.join(d, "out.npy"))), tag
+        pp = philox_ref.sampling_perm(77, 5, 1, np.nonzero(pre == 1)[0]); pn = philox_ref.sampling_perm(77, 5, 0, np.nonzero(pre == 0)[0])
+        assert np.array_equal(a, orc.rpn_targets(anchor, gt, pp, pn, variant=1)[0]), tag
 
 
 def test_philox_state_on_device_equals_by_value_and_advances(ops):
@@ -719,8 +713,8 @@ def test_rpn_targets_device_sampling_equals_reference_with_philox_permutations(o
 
 
 def test_rpn_targets_staged_chipwide_sampler_equals_reference_with_philox_permutations():
-    """The staged form at FPN size (rpn_colmax -> rpn_label -> three histogram levels -> apply: what the launcher falls back to when the
-    fused grid could not be co-resident) draws the same Philox keys: a child process with FRCNN_RPN_FUSED=0 must reproduce the labels
+    """The staged form at FPN size (rpn_colmax -> rpn_label with keys and key histogram -> rpn_apply: what the launcher falls back to when
+    the fused grid could not be co-resident) draws the same Philox keys: a child process with FRCNN_RPN_FUSED=0 must reproduce the labels
     the oracle gives for the Philox permutations, with a subsampled positive class."""
     import os, subprocess, sys, tempfile
     from oracle import philox_ref
@@ -740,6 +734,45 @@ def test_rpn_targets_staged_chipwide_sampler_equals_reference_with_philox_permut
         env = dict(os.environ, FRCNN_RPN_FUSED="0", PYTHONPATH=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
         subprocess.run([sys.executable, "-c", code, d], check=True, env=env, timeout=300)
         assert np.array_equal(np.load(os.path.join(d, "out.npy")), cls_o)
+
+
+def test_rpn_targets_staged_device_rng_small_shape_equals_reference_and_leaves_workspace_zero():
+    """The staged device-RNG form (FRCNN_RPN_FUSED=0: rpn_colmax -> rpn_label with keys -> rpn_apply) at N = 3285, a ragged tail for its
+    256- and 1024-thread blocks: (a) both classes over quota, (b) only the negatives.  One child process makes three calls per case:
+    (seed, offset) by value = the oracle with the Philox permutations; from a device philox_state = the same labels, offset + 1 left
+    behind (the snapshot hand-off between the launches); by value again = the first call (the shared sampler workspace was left zero)."""
+    import os, subprocess, sys, tempfile
+    from oracle import philox_ref
+    anchor = orc.tv_anchor_grid(96, 136, [(24, 34), (12, 17), (6, 9), (3, 5), (2, 3)], normalise=True)
+    assert anchor.shape[0] == 3285
+    l0 = anchor[:24 * 34 * 3]
+    ins = np.nonzero((l0[:, 0] >= 0) & (l0[:, 1] >= 0) & (l0[:, 2] <= 1) & (l0[:, 3] <= 1))[0]
+    rng = np.random.RandomState(1)
+    gts = [l0[ins[rng.choice(len(ins), 140, replace=False)]], _gt(rng, 3)]          # oracle: (n_pos, n_neg) = (559, 1088) and (8, 2853)
+    seed, offset = 31, 9
+    code = ("import numpy as np, torch, sys; from faster_rcnn_pytorch_amd import ops; d = sys.argv[1];"
+            "L = lambda n: torch.from_numpy(np.load(d + '/' + n + '.npy')).cuda(); a = L('anchor')\n"
+            "for c in '01':\n"
+            "    g = L('gt' + c); st = ops.philox_state(%d, %d, 'cuda')\n"
+            "    r = [ops.rpn_targets(a, g, variant=1, seed=%d, offset=%d), ops.rpn_targets(a, g, variant=1, philox_state=st),"
+            " ops.rpn_targets(a, g, variant=1, seed=%d, offset=%d)]\n"
+            "    np.save(d + '/cls' + c + '.npy', np.stack([x[0].cpu().numpy() for x in r]))\n"
+            "    np.save(d + '/counts' + c + '.npy', np.stack([x[2].cpu().numpy() for x in r])); np.save(d + '/st' + c + '.npy', st.cpu().numpy())\n"
+            % (seed, offset, seed, offset, seed, offset))
+    with tempfile.TemporaryDirectory() as d:
+        np.save(os.path.join(d, "anchor.npy"), anchor), np.save(os.path.join(d, "gt0.npy"), gts[0]), np.save(os.path.join(d, "gt1.npy"), gts[1])
+        env = dict(os.environ, FRCNN_RPN_FUSED="0", PYTHONPATH=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+        subprocess.run([sys.executable, "-c", code, d], check=True, env=env, timeout=300)
+        for c, gt in enumerate(gts):
+            pre, _, (n_pos, n_neg) = orc.rpn_targets(anchor, gt, variant=1)
+            assert n_neg > 256 - min(n_pos, 128) and (n_pos > 128) == (c == 0), (c, n_pos, n_neg)   # the classes meant to be subsampled are
+            pp = philox_ref.sampling_perm(seed, offset, 1, np.nonzero(pre == 1)[0]); pn = philox_ref.sampling_perm(seed, offset, 0, np.nonzero(pre == 0)[0])
+            cls_o = orc.rpn_targets(anchor, gt, pp, pn, variant=1)[0]
+            cls, counts = np.load(os.path.join(d, "cls%d.npy" % c)), np.load(os.path.join(d, "counts%d.npy" % c))
+            for k in range(3):
+                assert np.array_equal(cls[k], cls_o), (c, k)
+                assert counts[k, :3].tolist() == [n_pos, n_neg, 0], (c, k)
+            assert np.load(os.path.join(d, "st%d.npy" % c)).tolist() == [seed, offset + 1]
 
 
 @pytest.mark.parametrize("variant,label_offset,max_pos,total,P", [(0, 1, 32, 128, 2000), (1, 0, 128, 512, 1000), (0, 1, 32, 128, 300)])
