@@ -105,6 +105,9 @@ SIGNATURES = {
     "frcnn_zoom_out": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     "frcnn_resize_crop_workspace": (_sz, [_i, _i, _i, _i, _i, _i]),
     "frcnn_resize_crop": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "frcnn_sgd_table_bytes": (_sz, [_i, _vp]),
+    "frcnn_sgd_table_build_host": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
+    "frcnn_sgd_step": (_i, [_vp, _sz, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "frcnn_diag_occupy": (_i, [_i, _i, _vp]),
     "frcnn_prof_enable": (_i, [_i]),
     "frcnn_prof_collect": (_i, []),

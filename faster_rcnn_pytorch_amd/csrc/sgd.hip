@@ -1,0 +1,234 @@
+// sgd.hip -- the optimizer step of the reference (main.py:58-61: torch.optim.SGD(lr, momentum, weight_decay), stepped at train.py:35-37)
+// as ONE multi-tensor launch whose hyper-parameters are device data, so that a captured graph follows the learning-rate schedule.
+//
+//   table   built on the host (frcnn_sgd_table_build_host), uploaded by the caller:
+//             SgdHeader | SgdRow[n_tensors] {parameter, gradient, momentum, numel, group, vec} | int2 map[n_chunks] {tensor, chunk in tensor}
+//           One workgroup per map entry: SGD_CHUNK elements of one tensor.  No search: the block reads its own entry and its tensor's row.
+//   hyper   float[G][4] = (lr, momentum, weight_decay, unused), read by every block at run time.
+//   born    int32[n_tensors]: 0 until a tensor's momentum has been written once.  The update kernel only READS it; sgd_born_kernel, the
+//           second launch on the same stream, sets the words after every block of the first has finished.
+//   skip    NULL, or a device int32: non-zero turns both launches into no-ops.
+//
+// The rule, operation for operation (torch.optim.SGD, dampening 0, no Nesterov, maximize=False; the fused operations are torch's
+// `add(x, alpha=a)`, one rounding):
+//   d  = wd != 0 ? fma(wd, p, g) : g              no product with a zero weight decay: an infinite p stays infinite
+//   m' = (first update or mu == 0) ? d : round(mu * m) + d
+//   p' = fma(-lr, m', p)
+// With mu == 0 torch keeps no momentum buffer: m is neither read nor written and the born word stays as it is.
+// The library is built with -ffp-contract=off; every fused operation below is written out (__fmaf_rn).
+//
+// Memory: 12 B read + 8 B written per element, nothing reused: a streaming kernel.  16-byte accesses when a tensor's three pointers are
+// 16-byte aligned (SGD_CHUNK is a multiple of 4, so every chunk of such a tensor starts aligned), four independent float4 triples in flight
+// per thread; the gradient is read once and loaded non-temporally.  Any other tensor (a view at an odd storage offset) takes the
+// dword path for its whole length -- its three pointers need not share a misalignment, so there is no common peel.
+#include "frcnn_common.h"
+#include "frcnn_internal.h"
+#include "frcnn_layout.h"
+#include <algorithm>
+#include <vector>
+FRCNN_LAYOUT_STAMP(sgd);
+
+#define SGD_CHUNK 8192                  // elements per workgroup: 256 threads x 8 float4
+#define SGD_THREADS 256
+#define SGD_MAGIC 0x31444753u           // "SGD1"
+#define SGD_MAX_TENSORS 65536
+#define SGD_MAX_GROUPS 1024
+
+typedef float sgd_f4 __attribute__((ext_vector_type(4)));
+struct SgdHeader { uint32_t magic; int32_t n_tensors, n_groups, n_chunks, chunk, pad[3]; uint64_t rows_off, map_off, bytes, pad2; };
+struct SgdRow { float *p; const float *g; float *m; int64_t numel; int32_t group, vec, pad[2]; };
+static_assert(sizeof(SgdHeader) == 64 && sizeof(SgdRow) == 48, "sgd table layout");
+static_assert(SGD_CHUNK % (4 * SGD_THREADS) == 0, "a chunk is a whole number of float4 sweeps");
+
+static size_t sgd_table_bytes(int64_t n_tensors, int64_t n_chunks)
+{
+    return sizeof(SgdHeader) + (size_t)n_tensors * sizeof(SgdRow) + (size_t)n_chunks * sizeof(int2);
+}
+
+__device__ __forceinline__ float sgd_one(float p, float g, float *m, float neg_lr, float mu, float wd, bool use_wd, bool keep, bool first)
+{
+    const float d = use_wd ? __fmaf_rn(wd, p, g) : g;
+    float mn = d;
+    if (keep) {
+        if (!first) mn = __fadd_rn(__fmul_rn(mu, *m), d);
+        *m = mn;
+    }
+    return __fmaf_rn(neg_lr, mn, p);
+}
+
+__global__ __launch_bounds__(SGD_THREADS) void sgd_update_kernel(const SgdRow *__restrict__ rows, const int2 *__restrict__ map, int n_tensors,
+                                                                 const float4 *__restrict__ hyper, int n_groups,
+                                                                 const int32_t *__restrict__ born, const int32_t *__restrict__ skip)
+{
+    if (skip && *skip != 0) return;
+    const int2 c = map[blockIdx.x];
+    if ((unsigned)c.x >= (unsigned)n_tensors || c.y < 0) return;           // a table that is not ours: touch nothing
+    const SgdRow r = rows[c.x];
+    if ((unsigned)r.group >= (unsigned)n_groups) return;
+    const int64_t off = (int64_t)c.y * SGD_CHUNK;
+    if (off >= r.numel) return;
+    const int64_t left = r.numel - off;
+    const int n = left < SGD_CHUNK ? (int)left : SGD_CHUNK;
+    const float4 h = hyper[r.group];
+    const float neg_lr = -h.x, mu = h.y, wd = h.z;
+    const bool use_wd = wd != 0.0f, keep = mu != 0.0f, first = born[c.x] == 0;
+    float *p = r.p + off, *m = r.m + off;
+    const float *g = r.g + off;
+    const int tid = threadIdx.x;
+    int done = 0;
+    if (r.vec) {
+        sgd_f4 *p4 = (sgd_f4 *)p, *m4 = (sgd_f4 *)m;
+        const sgd_f4 *g4 = (const sgd_f4 *)g;
+        const int n4 = n >> 2;
+        for (int base = 0; base < n4; base += 4 * SGD_THREADS) {
+            sgd_f4 vp[4], vg[4], vm[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int i = base + k * SGD_THREADS + tid;
+                if (i < n4) {
+                    vp[k] = p4[i];
+                    vg[k] = __builtin_nontemporal_load(&g4[i]);
+                    if (keep && !first) vm[k] = m4[i];
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int i = base + k * SGD_THREADS + tid;
+                if (i < n4) {
+                    sgd_f4 q, mv = vm[k];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        float me = mv[e];
+                        q[e] = sgd_one(vp[k][e], vg[k][e], &me, neg_lr, mu, wd, use_wd, keep, first);
+                        mv[e] = me;
+                    }
+                    if (keep) m4[i] = mv;
+                    p4[i] = q;
+                }
+            }
+        }
+        done = n4 << 2;
+    }
+    for (int i = done + tid; i < n; i += SGD_THREADS) {                     // the tail of an aligned tensor; all of a misaligned one
+        float mv = 0.0f;
+        if (keep && !first) mv = m[i];
+        const float q = sgd_one(p[i], g[i], &mv, neg_lr, mu, wd, use_wd, keep, first);
+        if (keep) m[i] = mv;
+        p[i] = q;
+    }
+}
+
+// after the update: a tensor whose group keeps momentum has one now
+__global__ __launch_bounds__(SGD_THREADS) void sgd_born_kernel(const SgdRow *__restrict__ rows, int n_tensors, const float4 *__restrict__ hyper, int n_groups,
+                                                               int32_t *__restrict__ born, const int32_t *__restrict__ skip)
+{
+    if (skip && *skip != 0) return;
+    const int t = blockIdx.x * SGD_THREADS + threadIdx.x;
+    if (t >= n_tensors) return;
+    const int grp = rows[t].group;
+    if ((unsigned)grp >= (unsigned)n_groups) return;
+    if (hyper[grp].y != 0.0f) born[t] = 1;
+}
+
+// ---- host ------------------------------------------------------------------------------------------------------------------------
+static int64_t sgd_chunks_of(int64_t numel) { return (numel + SGD_CHUNK - 1) / SGD_CHUNK; }
+
+// main.py:58-61 / train.py:35-37.  Bytes of the table for these tensor sizes; 0 for what the builder refuses.
+FRCNN_EXPORT size_t frcnn_sgd_table_bytes(int n_tensors, const int64_t *numel_host)
+{
+    if (n_tensors < 1 || n_tensors > SGD_MAX_TENSORS || !numel_host) return 0;
+    int64_t chunks = 0;
+    for (int t = 0; t < n_tensors; ++t) {
+        if (numel_host[t] < 0 || numel_host[t] > ((int64_t)1 << 40)) return 0;
+        chunks += sgd_chunks_of(numel_host[t]);
+    }
+    if (chunks > 0x7fffffff) return 0;
+    return sgd_table_bytes(n_tensors, chunks);
+}
+
+// main.py:58-61 / train.py:35-37.  Fills the caller's HOST buffer; the caller uploads table_bytes bytes to 16-byte aligned device memory.
+FRCNN_EXPORT int frcnn_sgd_table_build_host(int n_tensors, const void *const *params_host, const void *const *grads_host, const void *const *moms_host,
+                                            const int64_t *numel_host, const int32_t *group_host, int n_groups, void *table_host, size_t table_bytes,
+                                            int32_t *n_chunks_host)
+{
+    FRCNN_REQUIRE(params_host && grads_host && moms_host && numel_host && group_host && table_host && n_chunks_host, "sgd_table_build: NULL argument");
+    FRCNN_REQUIRE(n_tensors >= 1 && n_tensors <= SGD_MAX_TENSORS, "sgd_table_build: n_tensors %d outside 1 .. %d", n_tensors, SGD_MAX_TENSORS);
+    FRCNN_REQUIRE(n_groups >= 1 && n_groups <= SGD_MAX_GROUPS, "sgd_table_build: n_groups %d outside 1 .. %d", n_groups, SGD_MAX_GROUPS);
+    for (int t = 0; t < n_tensors; ++t) {
+        FRCNN_REQUIRE(numel_host[t] >= 0, "sgd_table_build: tensor %d has a negative size %lld", t, (long long)numel_host[t]);
+        FRCNN_REQUIRE(numel_host[t] <= ((int64_t)1 << 40), "sgd_table_build: tensor %d is too large (%lld elements)", t, (long long)numel_host[t]);
+        FRCNN_REQUIRE(params_host[t] && grads_host[t] && moms_host[t], "sgd_table_build: NULL pointer in row %d", t);
+        FRCNN_REQUIRE(group_host[t] >= 0 && group_host[t] < n_groups, "sgd_table_build: row %d names group %d outside 0 .. %d", t, group_host[t], n_groups - 1);
+        FRCNN_REQUIRE((((uintptr_t)params_host[t] | (uintptr_t)grads_host[t] | (uintptr_t)moms_host[t]) & 3) == 0,
+                      "sgd_table_build: row %d has a pointer that is not 4-byte aligned", t);
+    }
+    const size_t need = frcnn_sgd_table_bytes(n_tensors, numel_host);
+    FRCNN_REQUIRE(need != 0, "sgd_table_build: more than 2^31 - 1 chunks");
+    if (table_bytes < need) return frcnn_set_error(FRCNN_ERR_WORKSPACE, "sgd_table_build: short table, %zu < %zu bytes", table_bytes, need);
+    // nothing that is written may overlap anything else: parameter and momentum ranges pairwise (all rows), a gradient with neither
+    struct Span { uintptr_t lo, hi; int row; char kind; };
+    std::vector<Span> w;
+    w.reserve(2 * (size_t)n_tensors);
+    for (int t = 0; t < n_tensors; ++t) {
+        const size_t b = (size_t)numel_host[t] * 4;
+        if (b == 0) continue;
+        w.push_back({(uintptr_t)params_host[t], (uintptr_t)params_host[t] + b, t, 'p'});
+        w.push_back({(uintptr_t)moms_host[t], (uintptr_t)moms_host[t] + b, t, 'm'});
+    }
+    std::sort(w.begin(), w.end(), [](const Span &a, const Span &b) { return a.lo < b.lo; });
+    for (size_t i = 1; i < w.size(); ++i)
+        FRCNN_REQUIRE(w[i].lo >= w[i - 1].hi, "sgd_table_build: overlapping parameter and momentum (%c of row %d and %c of row %d)",
+                      w[i - 1].kind, w[i - 1].row, w[i].kind, w[i].row);
+    for (int t = 0; t < n_tensors; ++t) {
+        const size_t b = (size_t)numel_host[t] * 4;
+        if (b == 0) continue;
+        const uintptr_t lo = (uintptr_t)grads_host[t], hi = lo + b;
+        auto it = std::upper_bound(w.begin(), w.end(), lo, [](uintptr_t v, const Span &s) { return v < s.lo; });
+        const bool hit = (it != w.end() && it->lo < hi) || (it != w.begin() && (it - 1)->hi > lo);
+        FRCNN_REQUIRE(!hit, "sgd_table_build: the gradient of row %d overlaps a parameter or a momentum", t);
+    }
+    char *base = (char *)table_host;
+    SgdHeader *hd = (SgdHeader *)base;
+    SgdRow *rows = (SgdRow *)(base + sizeof(SgdHeader));
+    int2 *map = (int2 *)(base + sizeof(SgdHeader) + (size_t)n_tensors * sizeof(SgdRow));
+    int64_t c = 0;
+    for (int t = 0; t < n_tensors; ++t) {
+        const uintptr_t all = (uintptr_t)params_host[t] | (uintptr_t)grads_host[t] | (uintptr_t)moms_host[t];
+        rows[t].p = (float *)params_host[t];
+        rows[t].g = (const float *)grads_host[t];
+        rows[t].m = (float *)moms_host[t];
+        rows[t].numel = numel_host[t];
+        rows[t].group = group_host[t];
+        rows[t].vec = (all & 15) == 0;
+        rows[t].pad[0] = rows[t].pad[1] = 0;
+        const int64_t k = sgd_chunks_of(numel_host[t]);
+        for (int64_t j = 0; j < k; ++j) map[c++] = make_int2(t, (int)j);
+    }
+    *hd = SgdHeader{SGD_MAGIC, n_tensors, n_groups, (int32_t)c, SGD_CHUNK, {0, 0, 0}, sizeof(SgdHeader),
+                    sizeof(SgdHeader) + (size_t)n_tensors * sizeof(SgdRow), need, 0};
+    *n_chunks_host = (int32_t)c;
+    return FRCNN_OK;
+}
+
+// train.py:35-37 (optimizer.step()) for the optimizer main.py:58-61 constructs.  Two launches, no host synchronisation, capturable.
+FRCNN_EXPORT int frcnn_sgd_step(const void *table, size_t table_bytes, int n_tensors, int n_chunks, const float *hyper, int n_groups, int32_t *born,
+                                const int32_t *skip, void *stream)
+{
+    FRCNN_REQUIRE(table && hyper && born, "sgd_step: NULL pointer");
+    FRCNN_REQUIRE(n_tensors >= 1 && n_tensors <= SGD_MAX_TENSORS && n_chunks >= 0, "sgd_step: bad counts (%d tensors, %d chunks)", n_tensors, n_chunks);
+    FRCNN_REQUIRE(n_groups >= 1 && n_groups <= SGD_MAX_GROUPS, "sgd_step: n_groups %d outside 1 .. %d", n_groups, SGD_MAX_GROUPS);
+    FRCNN_REQUIRE(((uintptr_t)table & 15) == 0 && ((uintptr_t)hyper & 15) == 0 && ((uintptr_t)born & 3) == 0 && ((uintptr_t)skip & 3) == 0,
+                  "sgd_step: table and hyper must be 16-byte aligned, born and skip 4-byte aligned");
+    const size_t need = sgd_table_bytes(n_tensors, n_chunks);
+    if (table_bytes < need) return frcnn_set_error(FRCNN_ERR_WORKSPACE, "sgd_step: short table, %zu < %zu bytes", table_bytes, need);
+    if (n_chunks == 0) return FRCNN_OK;                                     // every tensor is empty
+    const SgdRow *rows = (const SgdRow *)((const char *)table + sizeof(SgdHeader));
+    const int2 *map = (const int2 *)((const char *)table + sizeof(SgdHeader) + (size_t)n_tensors * sizeof(SgdRow));
+    hipStream_t s = (hipStream_t)stream;
+    FRCNN_LAUNCH(sgd_update_kernel, dim3((unsigned)n_chunks), dim3(SGD_THREADS), 0, s, rows, map, n_tensors, (const float4 *)hyper, n_groups,
+                 (const int32_t *)born, skip);
+    FRCNN_LAUNCH(sgd_born_kernel, dim3((unsigned)((n_tensors + SGD_THREADS - 1) / SGD_THREADS)), dim3(SGD_THREADS), 0, s, rows, n_tensors,
+                 (const float4 *)hyper, n_groups, born, skip);
+    FRCNN_CHECK_LAUNCH("sgd kernels");
+    return FRCNN_OK;
+}

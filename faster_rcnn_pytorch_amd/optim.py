@@ -1,0 +1,225 @@
+"""DeviceSGD: the reference's optimizer (main.py:58-61: torch.optim.SGD(lr, momentum, weight_decay); stepped at train.py:35-37) as ONE
+library launch (csrc/sgd.hip) whose hyper-parameters live in device memory.
+
+Why: a torch optimizer built with a Python-float lr passes the lr to its kernels as a launch constant, so a captured graph
+(parallel.GraphStep, torch.cuda.graph) keeps the lr it was captured with whatever a scheduler does afterwards.  Here the kernel reads
+(lr, momentum, weight_decay) per parameter group from a device block at run time; `param_groups[i]['lr']` stays a Python float that
+any torch scheduler can change, and `push_hyper()` -- a stream-ordered write OUTSIDE the graph -- carries a change to the device.
+
+The update rule is torch.optim.SGD's (dampening 0, no Nesterov, maximize=False), bit for bit against torch on the CPU
+(tests/golden/sgd.npz, docs/PARITY.md).  Momentum tensors are allocated once, at construction, and never move: load_state_dict copies
+INTO them.  Whether a tensor has had its first update is device data too (one int32 "born" word per tensor), so a graph captured before
+any step is right from step 0 on, and a step skipped by the guard word leaves everything as it was.
+
+There is no fallback: anything the kernel does not cover (dampening, Nesterov, maximize, non-fp32, sparse or non-contiguous tensors or
+gradients, a trainable parameter without a gradient, CPU tensors) is refused with an exception."""
+import ctypes as C
+
+import torch
+
+from . import _lib
+
+GROUP_KEYS = ("lr", "momentum", "dampening", "weight_decay", "nesterov", "maximize", "foreach", "differentiable", "fused")
+
+
+def group_defaults(lr=1e-3, momentum=0, weight_decay=0, dampening=0, nesterov=False, maximize=False):
+    """The per-group keys of torch.optim.SGD, in its order (a state dict of one loads into the other)."""
+    return dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov, maximize=maximize,
+                foreach=None, differentiable=False, fused=None)
+
+
+def _check_group(g):
+    if g["dampening"] != 0:
+        raise ValueError("DeviceSGD: dampening != 0 is not supported (the reference uses 0, main.py:58-61)")
+    if g["nesterov"]:
+        raise ValueError("DeviceSGD: nesterov=True is not supported")
+    if g["maximize"]:
+        raise ValueError("DeviceSGD: maximize=True is not supported")
+    if g.get("differentiable"):
+        raise ValueError("DeviceSGD: differentiable=True is not supported")
+    for k in ("lr", "momentum", "weight_decay"):
+        v = g[k]
+        if torch.is_tensor(v):
+            raise ValueError("DeviceSGD: %s must be a Python number (the device block is written by push_hyper()), got a tensor" % k)
+        if not float(v) >= 0.0:
+            raise ValueError("DeviceSGD: invalid %s: %r" % (k, v))
+
+
+def _check_dense(t, what, device=None):
+    if not torch.is_tensor(t) or t.layout != torch.strided or t.is_sparse:
+        raise TypeError("DeviceSGD: %s is not a dense strided tensor" % what)
+    if t.device.type != "cuda":
+        raise RuntimeError("DeviceSGD: %s is on %s: the optimizer runs only on a HIP device (no CPU fallback)" % (what, t.device))
+    if device is not None and t.device != device:
+        raise RuntimeError("DeviceSGD: %s is on %s, the optimizer's tensors are on %s" % (what, t.device, device))
+    if t.dtype != torch.float32:
+        raise TypeError("DeviceSGD: %s is %s: fp32 only" % (what, t.dtype))
+    if not t.is_contiguous():
+        raise TypeError("DeviceSGD: %s is not contiguous (dense tensors only)" % what)
+
+
+class DeviceSGD(torch.optim.Optimizer):
+    """DeviceSGD(params, lr, momentum=0, weight_decay=0, guard=None).  `guard`: a device int32 tensor of one element; while it is
+    non-zero a step changes nothing (parameters, momentum, born words).  Parameters with requires_grad=False take no part."""
+
+    def __init__(self, params, lr=1e-3, momentum=0, weight_decay=0, dampening=0, nesterov=False, maximize=False, guard=None):
+        super().__init__(params, group_defaults(lr, momentum, weight_decay, dampening, nesterov, maximize))
+        self._rows = []                                                   # (parameter, group index), trainable parameters in state-dict order
+        for gi, g in enumerate(self.param_groups):
+            _check_group(g)
+            for p in g["params"]:
+                if p.requires_grad:
+                    self._rows.append((p, gi))
+        if not self._rows:
+            raise ValueError("DeviceSGD: no trainable parameter")
+        self.device = self._rows[0][0].device
+        for k, (p, _) in enumerate(self._rows):
+            _check_dense(p, "parameter %d" % k, self.device if k else None)
+        if guard is not None:
+            if not torch.is_tensor(guard) or guard.dtype != torch.int32 or guard.numel() != 1 or guard.device != self.device:
+                raise TypeError("DeviceSGD: guard must be a one-element int32 tensor on %s" % self.device)
+        self.guard = guard
+        n, G = len(self._rows), len(self.param_groups)
+        with torch.no_grad():
+            for p, _ in self._rows:                                       # allocated once; the kernel and every graph hold these addresses
+                self.state[p]["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            self._born = torch.zeros(n, dtype=torch.int32, device=self.device)
+            self._hyper = torch.zeros(G, 4, dtype=torch.float32, device=self.device)
+        self._pushed = [None] * G                                         # what the device block holds, as Python floats
+        self._numel = (C.c_int64 * n)(*[p.numel() for p, _ in self._rows])
+        self._group = (C.c_int32 * n)(*[gi for _, gi in self._rows])
+        self._table_bytes = int(_lib.lib.frcnn_sgd_table_bytes(n, self._numel))
+        if self._table_bytes == 0:
+            raise _lib.FrcnnError("DeviceSGD: frcnn_sgd_table_bytes refuses %d tensors of these sizes" % n)
+        self._table = torch.empty(self._table_bytes, dtype=torch.uint8, device=self.device)     # one address for good
+        self._n_chunks = 0
+        self._key = None
+
+    # ---- hyper-parameters
+    def push_hyper(self):
+        """Writes the (lr, momentum, weight_decay) that changed since the last call into the device block: one stream-ordered fill per
+        changed value, no host synchronisation.  Never part of a graph: under capture a pending change is an error."""
+        for gi, g in enumerate(self.param_groups):
+            _check_group(g)
+            now = (float(g["lr"]), float(g["momentum"]), float(g["weight_decay"]))
+            old = self._pushed[gi]
+            if old == now:
+                continue
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("DeviceSGD: group %d's hyper-parameters changed and the stream is capturing: the device block is written "
+                                   "outside graphs -- call push_hyper() before the capture and before each replay" % gi)
+            with torch.no_grad():
+                for k in range(3):
+                    if old is None or old[k] != now[k]:
+                        self._hyper[gi, k].fill_(now[k])
+            self._pushed[gi] = now
+
+    # ---- the table
+    def _gradients(self):
+        gs = []
+        for k, (p, _) in enumerate(self._rows):
+            if not p.requires_grad:
+                raise RuntimeError("DeviceSGD: parameter %d was trainable at construction and is frozen now" % k)
+            g = p.grad
+            if g is None:
+                raise RuntimeError("DeviceSGD: trainable parameter %d has no gradient (.grad is None): a captured step cannot skip a tensor" % k)
+            _check_dense(g, "the gradient of parameter %d" % k, self.device)
+            if g.shape != p.shape:
+                raise RuntimeError("DeviceSGD: the gradient of parameter %d has shape %s, the parameter %s" % (k, tuple(g.shape), tuple(p.shape)))
+            gs.append(g)
+        return gs
+
+    def prepare(self):
+        """Builds and uploads the table for the current parameter / gradient addresses (a no-op when they have not moved).  step() calls it;
+        call it yourself before capturing a graph that no eager step preceded."""
+        gs = self._gradients()
+        key = tuple(p.data_ptr() for p, _ in self._rows) + tuple(g.data_ptr() for g in gs)
+        if key == self._key:
+            return
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("DeviceSGD: a parameter or gradient address changed and the stream is capturing: run one eager step (or "
+                               "prepare()) on the final gradient tensors before the capture")
+        n = len(self._rows)
+        vp = C.c_void_p * n
+        host = torch.empty(self._table_bytes, dtype=torch.uint8).pin_memory()                 # a fresh staging block per build: the copy below is asynchronous
+        n_chunks = C.c_int32(0)
+        _lib.check(_lib.lib.frcnn_sgd_table_build_host(
+            n, vp(*[p.data_ptr() for p, _ in self._rows]), vp(*[g.data_ptr() for g in gs]),
+            vp(*[self.state[p]["momentum_buffer"].data_ptr() for p, _ in self._rows]), self._numel, self._group, len(self.param_groups),
+            C.c_void_p(host.data_ptr()), self._table_bytes, C.byref(n_chunks)), "frcnn_sgd_table_build_host")
+        self._table.copy_(host, non_blocking=True)
+        self._n_chunks, self._key = int(n_chunks.value), key
+
+    def launch(self):
+        """The library launch alone (what a graph records): no hyper-parameter write."""
+        self.prepare()
+        _lib.check(_lib.lib.frcnn_sgd_step(
+            C.c_void_p(self._table.data_ptr()), self._table_bytes, len(self._rows), self._n_chunks, C.c_void_p(self._hyper.data_ptr()),
+            len(self.param_groups), C.c_void_p(self._born.data_ptr()), C.c_void_p(self.guard.data_ptr()) if self.guard is not None else None,
+            C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), "frcnn_sgd_step")
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        self.push_hyper()
+        with torch.cuda.device(self.device):
+            self.launch()
+        return loss
+
+    def add_param_group(self, param_group):
+        if getattr(self, "_table", None) is not None:
+            raise RuntimeError("DeviceSGD: parameter groups are fixed at construction (the momentum tensors and the table are allocated there)")
+        super().add_param_group(param_group)
+
+    # ---- checkpoints: torch.optim.SGD's format
+    def born(self):
+        """The born words as a list of 0 / 1, one per trainable parameter (a device read-back: synchronises)."""
+        return [int(v) for v in self._born.cpu().tolist()]
+
+    def state_dict(self):
+        born = dict(zip((id(p) for p, _ in self._rows), self.born()))
+        state, groups, idx = {}, [], 0
+        for g in self.param_groups:
+            packed = {k: v for k, v in g.items() if k != "params"}
+            packed["params"] = list(range(idx, idx + len(g["params"])))
+            for i, p in zip(packed["params"], g["params"]):
+                if born.get(id(p)):
+                    state[i] = {"momentum_buffer": self.state[p]["momentum_buffer"]}
+            idx += len(g["params"])
+            groups.append(packed)
+        return {"state": state, "param_groups": groups}
+
+    @torch.no_grad()
+    def load_state_dict(self, state_dict):
+        saved = state_dict["param_groups"]
+        if len(saved) != len(self.param_groups):
+            raise ValueError("loaded state dict has a different number of parameter groups")
+        if any(len(s["params"]) != len(g["params"]) for s, g in zip(saved, self.param_groups)):
+            raise ValueError("loaded state dict contains a parameter group that doesn't match the size of optimizer's group")
+        for s in saved:
+            merged = group_defaults()
+            merged.update({k: v for k, v in s.items() if k != "params"})
+            _check_group(merged)
+        by_index = {}
+        for s, g in zip(saved, self.param_groups):
+            for i, p in zip(s["params"], g["params"]):
+                by_index[id(p)] = state_dict["state"].get(i, state_dict["state"].get(str(i)))
+        born, copies = [], []
+        for k, (p, _) in enumerate(self._rows):
+            buf = (by_index.get(id(p)) or {}).get("momentum_buffer")
+            if buf is not None:
+                if tuple(buf.shape) != tuple(p.shape):
+                    raise ValueError("DeviceSGD: the momentum of parameter %d has shape %s, the parameter %s" % (k, tuple(buf.shape), tuple(p.shape)))
+                copies.append((self.state[p]["momentum_buffer"], buf))
+            born.append(0 if buf is None else 1)
+        for dst, src in copies:                                           # INTO the tensors allocated at construction: no address changes
+            dst.copy_(src.to(device=self.device, dtype=torch.float32))
+        self._born.copy_(torch.tensor(born, dtype=torch.int32))
+        for s, g in zip(saved, self.param_groups):
+            for k, v in s.items():
+                if k != "params":
+                    g[k] = v
+        self.push_hyper()

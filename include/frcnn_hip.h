@@ -655,6 +655,36 @@ int frcnn_resize_crop(const uint8_t *src_hwc, int h, int w, int H1, int W1, int 
                       float *boxes_out, int64_t *labels_out, float *area_out, int64_t *iscrowd_out, int32_t *count_dev,
                       void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- optimizer: SGD with momentum and weight decay, hyper-parameters in device memory -----------------------------------------------
+ * The three entry points replace torch.optim.SGD as main.py:58-61 constructs it (lr, momentum, weight_decay; dampening 0, no Nesterov,
+ * maximize=False) and train.py:35-37 steps it, for fp32 dense tensors, in place on parameter and momentum:
+ *   d  = wd != 0 ? fma(wd, p, g) : g          (no product with a zero weight decay)
+ *   m' = (the tensor's first update, or mu == 0) ? d : round(mu * m) + d
+ *   p' = fma(-lr, m', p)
+ * every fma rounded once: the bits of torch.optim.SGD on the CPU (tests/golden/sgd.npz).  With mu == 0 the momentum is neither read nor
+ * written and the tensor's born word is left alone (torch keeps no buffer then).
+ *   hyper  float[n_groups][4] = (lr, momentum, weight_decay, unused) in DEVICE memory, 16-byte aligned, read by the kernel at run time: a
+ *          captured graph applies whatever the block holds at each replay.
+ *   born   int32[n_tensors] in DEVICE memory: 0 = the tensor's momentum has never been written (its content is then not read).  Read by
+ *          the update, set by a second small launch behind it.
+ *   skip   NULL, or a device int32: when non-zero the step changes nothing (parameters, momentum, born words).
+ *   table  frcnn_sgd_table_bytes(n_tensors, numel_host) bytes, filled on the HOST by frcnn_sgd_table_build_host from arrays of DEVICE
+ *          pointers (parameter, gradient, momentum), element counts and group indices, then uploaded by the caller to 16-byte aligned
+ *          device memory.  It holds one row per tensor and one entry per 8192-element chunk; *n_chunks_host is the number of entries.
+ *          Pointers need 4-byte alignment only; a tensor whose three pointers are 16-byte aligned is moved with 16-byte accesses.
+ * frcnn_sgd_table_bytes: 0 for counts the builder refuses.  frcnn_sgd_table_build_host, FRCNN_ERR_INVALID_ARG: a NULL array, n_tensors
+ * outside 1 .. 65536, n_groups outside 1 .. 1024, a negative size, a NULL or misaligned pointer in a row, a group index outside
+ * 0 .. n_groups - 1, overlapping parameter and momentum ranges (of one row or of two), a gradient overlapping either;
+ * FRCNN_ERR_WORKSPACE: a short table.  frcnn_sgd_step (main.py:58-61, train.py:35-37): two launches whatever the number and sizes of the
+ * tensors, no host synchronisation, capturable.  FRCNN_ERR_INVALID_ARG before anything is launched: a NULL table / hyper / born, bad
+ * counts, a misaligned pointer; FRCNN_ERR_WORKSPACE: table_bytes below what n_tensors and n_chunks need.  */
+size_t frcnn_sgd_table_bytes(int n_tensors, const int64_t *numel_host);
+int frcnn_sgd_table_build_host(int n_tensors, const void *const *params_host, const void *const *grads_host, const void *const *moms_host,
+                               const int64_t *numel_host, const int32_t *group_host, int n_groups, void *table_host, size_t table_bytes,
+                               int32_t *n_chunks_host);
+int frcnn_sgd_step(const void *table, size_t table_bytes, int n_tensors, int n_chunks, const float *hyper, int n_groups, int32_t *born,
+                   const int32_t *skip, void *stream);
+
 /* ---- in-library kernel timing (HIP events on the launch stream) -------------------------------------- */
 /* When enabled, every kernel launch made by this library is bracketed by two hipEventRecord on the
  * caller's stream.  frcnn_prof_collect() synchronises those events (call it after the stream is idle)
