@@ -108,6 +108,9 @@ SIGNATURES = {
     "frcnn_sgd_table_bytes": (_sz, [_i, _vp]),
     "frcnn_sgd_table_build_host": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
     "frcnn_sgd_step": (_i, [_vp, _sz, _i, _i, _vp, _i, _vp, _vp, _vp]),
+    "frcnn_grad_norm_workspace_bytes": (_sz, [_i]),
+    "frcnn_grad_norm": (_i, [_vp, _sz, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "frcnn_sgd_step_scaled": (_i, [_vp, _sz, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "frcnn_diag_occupy": (_i, [_i, _i, _vp]),
     "frcnn_prof_enable": (_i, [_i]),
     "frcnn_prof_collect": (_i, []),

@@ -5,6 +5,9 @@
 //     prologue's sampling workgroups (boxes.hip) and READ by topk_partition / topk_bucket (topk.hip), each from its own copy of the
 //     header: two objects compiled against two versions of it disagree about where the splitters, counts and barrier words lie and
 //     how large a bucket can get (round 3, 14:49: DESIGN.md section 7);
+//   * SgdHeader / SgdRow + SGD_CHUNK / SGD_THREADS (sgd_dev.h): the optimizer's table, BUILT in sgd.hip and walked by the kernels of sgd.hip
+//     and grad_norm.hip; frcnn_grad_norm_state (include/frcnn_hip.h): written by grad_norm.hip, its coef and skip words read by sgd.hip's
+//     kernels through pointers the caller derives from the same struct;
 //   * the profiling table size and the ABI version.
 // Every object registers its stamp in a static initialiser; frcnn_layout_check() (api.cpp; also run by frcnn_abi_version()) compares
 // them all with api.cpp's own and names the object that disagrees -- the library then refuses to load (FRCNN_ERR_UNSUPPORTED) instead of
@@ -15,6 +18,7 @@
 #include <cstddef>
 #include "frcnn_internal.h"
 #include "topk_dev.h"
+#include "sgd_dev.h"
 
 constexpr uint64_t frcnn_lay_mix(uint64_t h, uint64_t v) { return (h ^ v) * 0x100000001b3ull; }
 
@@ -38,6 +42,12 @@ constexpr uint64_t frcnn_layout_stamp_value()
     LAY(offsetof(SsCtl, pad)); LAY(offsetof(SsCtl, bar)); LAY(offsetof(SsCtl, flag));
     h = frcnn_lay_plan(h, 20646, 12000); h = frcnn_lay_plan(h, 20646, 6000); h = frcnn_lay_plan(h, 268569, 4000);
     h = frcnn_lay_plan(h, 268569, 2000); h = frcnn_lay_plan(h, 65536, 65536); h = frcnn_lay_plan(h, 4096, 300);
+    LAY(SGD_CHUNK); LAY(SGD_THREADS); LAY(sizeof(SgdHeader)); LAY(sizeof(SgdRow)); LAY(offsetof(SgdRow, p)); LAY(offsetof(SgdRow, g));
+    LAY(offsetof(SgdRow, m)); LAY(offsetof(SgdRow, numel)); LAY(offsetof(SgdRow, group)); LAY(offsetof(SgdRow, vec));
+    LAY(sizeof(frcnn_grad_norm_state)); LAY(offsetof(frcnn_grad_norm_state, max_norm)); LAY(offsetof(frcnn_grad_norm_state, flags));
+    LAY(offsetof(frcnn_grad_norm_state, sumsq)); LAY(offsetof(frcnn_grad_norm_state, norm)); LAY(offsetof(frcnn_grad_norm_state, coef));
+    LAY(offsetof(frcnn_grad_norm_state, skip)); LAY(offsetof(frcnn_grad_norm_state, nonfinite)); LAY(offsetof(frcnn_grad_norm_state, steps));
+    LAY(offsetof(frcnn_grad_norm_state, skipped_steps)); LAY(FRCNN_GRAD_NORM_FINISH_THREADS);
 #ifdef FRCNN_LAYOUT_TEST_SKEW          // tests/test_cabi.py builds ONE object with this defined and expects the library to refuse to load
     LAY(FRCNN_LAYOUT_TEST_SKEW);
 #endif
@@ -53,6 +63,11 @@ static_assert(offsetof(SsCtl, bar) % 64 == 0 && offsetof(SsCtl, flag) % 64 == 0,
 static_assert(sizeof(AnchorDesc) == 8 + 4 * 4 * FRCNN_MAX_LEVELS + 8 * FRCNN_MAX_LEVELS + 16 * FRCNN_MAX_LEVELS * FRCNN_MAX_BASE + 8,
               "AnchorDesc: unexpected size (kernarg struct of the prologue / anchor kernels)");
 static_assert(sizeof(AnchorDesc) <= 4096, "AnchorDesc must fit the kernarg segment");
+static_assert(sizeof(frcnn_grad_norm_state) == 64 && offsetof(frcnn_grad_norm_state, sumsq) == 8 && offsetof(frcnn_grad_norm_state, norm) == 16 &&
+                  offsetof(frcnn_grad_norm_state, coef) == 20 && offsetof(frcnn_grad_norm_state, skip) == 24 &&
+                  offsetof(frcnn_grad_norm_state, nonfinite) == 28 && offsetof(frcnn_grad_norm_state, steps) == 32 &&
+                  offsetof(frcnn_grad_norm_state, skipped_steps) == 36,
+              "frcnn_grad_norm_state: the offsets include/frcnn_hip.h documents (optim.py reads the block by them)");
 
 void frcnn_layout_register(const char *object, uint64_t stamp);
 int frcnn_layout_check_impl(void);

@@ -24,26 +24,10 @@
 #include "frcnn_common.h"
 #include "frcnn_internal.h"
 #include "frcnn_layout.h"
+#include "sgd_dev.h"
 #include <algorithm>
 #include <vector>
 FRCNN_LAYOUT_STAMP(sgd);
-
-#define SGD_CHUNK 8192                  // elements per workgroup: 256 threads x 8 float4
-#define SGD_THREADS 256
-#define SGD_MAGIC 0x31444753u           // "SGD1"
-#define SGD_MAX_TENSORS 65536
-#define SGD_MAX_GROUPS 1024
-
-typedef float sgd_f4 __attribute__((ext_vector_type(4)));
-struct SgdHeader { uint32_t magic; int32_t n_tensors, n_groups, n_chunks, chunk, pad[3]; uint64_t rows_off, map_off, bytes, pad2; };
-struct SgdRow { float *p; const float *g; float *m; int64_t numel; int32_t group, vec, pad[2]; };
-static_assert(sizeof(SgdHeader) == 64 && sizeof(SgdRow) == 48, "sgd table layout");
-static_assert(SGD_CHUNK % (4 * SGD_THREADS) == 0, "a chunk is a whole number of float4 sweeps");
-
-static size_t sgd_table_bytes(int64_t n_tensors, int64_t n_chunks)
-{
-    return sizeof(SgdHeader) + (size_t)n_tensors * sizeof(SgdRow) + (size_t)n_chunks * sizeof(int2);
-}
 
 __device__ __forceinline__ float sgd_one(float p, float g, float *m, float neg_lr, float mu, float wd, bool use_wd, bool keep, bool first)
 {
@@ -56,11 +40,18 @@ __device__ __forceinline__ float sgd_one(float p, float g, float *m, float neg_l
     return __fmaf_rn(neg_lr, mn, p);
 }
 
+// SCALE = false: the rule above on the gradient as it is.  SCALE = true: every gradient element is first multiplied by the device float
+// *grad_scale (one rounding, __fmul_rn) -- the bits of torch's in-place g.mul_(coef) followed by torch.optim.SGD; the gradient itself is
+// not written.
+template <bool SCALE>
 __global__ __launch_bounds__(SGD_THREADS) void sgd_update_kernel(const SgdRow *__restrict__ rows, const int2 *__restrict__ map, int n_tensors,
                                                                  const float4 *__restrict__ hyper, int n_groups,
-                                                                 const int32_t *__restrict__ born, const int32_t *__restrict__ skip)
+                                                                 const int32_t *__restrict__ born, const int32_t *__restrict__ skip,
+                                                                 const float *__restrict__ grad_scale)
 {
     if (skip && *skip != 0) return;
+    float gs = 1.0f;
+    if (SCALE) gs = *grad_scale;
     const int2 c = map[blockIdx.x];
     if ((unsigned)c.x >= (unsigned)n_tensors || c.y < 0) return;           // a table that is not ours: touch nothing
     const SgdRow r = rows[c.x];
@@ -99,7 +90,8 @@ __global__ __launch_bounds__(SGD_THREADS) void sgd_update_kernel(const SgdRow *_
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         float me = mv[e];
-                        q[e] = sgd_one(vp[k][e], vg[k][e], &me, neg_lr, mu, wd, use_wd, keep, first);
+                        const float ge = SCALE ? __fmul_rn(vg[k][e], gs) : vg[k][e];
+                        q[e] = sgd_one(vp[k][e], ge, &me, neg_lr, mu, wd, use_wd, keep, first);
                         mv[e] = me;
                     }
                     if (keep) m4[i] = mv;
@@ -112,7 +104,8 @@ __global__ __launch_bounds__(SGD_THREADS) void sgd_update_kernel(const SgdRow *_
     for (int i = done + tid; i < n; i += SGD_THREADS) {                     // the tail of an aligned tensor; all of a misaligned one
         float mv = 0.0f;
         if (keep && !first) mv = m[i];
-        const float q = sgd_one(p[i], g[i], &mv, neg_lr, mu, wd, use_wd, keep, first);
+        const float ge = SCALE ? __fmul_rn(g[i], gs) : g[i];
+        const float q = sgd_one(p[i], ge, &mv, neg_lr, mu, wd, use_wd, keep, first);
         if (keep) m[i] = mv;
         p[i] = q;
     }
@@ -210,25 +203,44 @@ FRCNN_EXPORT int frcnn_sgd_table_build_host(int n_tensors, const void *const *pa
     return FRCNN_OK;
 }
 
-// train.py:35-37 (optimizer.step()) for the optimizer main.py:58-61 constructs.  Two launches, no host synchronisation, capturable.
-FRCNN_EXPORT int frcnn_sgd_step(const void *table, size_t table_bytes, int n_tensors, int n_chunks, const float *hyper, int n_groups, int32_t *born,
-                                const int32_t *skip, void *stream)
+static int sgd_step_launch(const char *who, const void *table, size_t table_bytes, int n_tensors, int n_chunks, const float *hyper, int n_groups, int32_t *born,
+                           const int32_t *skip, const float *grad_scale, bool scaled, void *stream)
 {
-    FRCNN_REQUIRE(table && hyper && born, "sgd_step: NULL pointer");
-    FRCNN_REQUIRE(n_tensors >= 1 && n_tensors <= SGD_MAX_TENSORS && n_chunks >= 0, "sgd_step: bad counts (%d tensors, %d chunks)", n_tensors, n_chunks);
-    FRCNN_REQUIRE(n_groups >= 1 && n_groups <= SGD_MAX_GROUPS, "sgd_step: n_groups %d outside 1 .. %d", n_groups, SGD_MAX_GROUPS);
-    FRCNN_REQUIRE(((uintptr_t)table & 15) == 0 && ((uintptr_t)hyper & 15) == 0 && ((uintptr_t)born & 3) == 0 && ((uintptr_t)skip & 3) == 0,
-                  "sgd_step: table and hyper must be 16-byte aligned, born and skip 4-byte aligned");
+    FRCNN_REQUIRE(table && hyper && born && (!scaled || grad_scale), "%s: NULL pointer", who);
+    FRCNN_REQUIRE(n_tensors >= 1 && n_tensors <= SGD_MAX_TENSORS && n_chunks >= 0, "%s: bad counts (%d tensors, %d chunks)", who, n_tensors, n_chunks);
+    FRCNN_REQUIRE(n_groups >= 1 && n_groups <= SGD_MAX_GROUPS, "%s: n_groups %d outside 1 .. %d", who, n_groups, SGD_MAX_GROUPS);
+    FRCNN_REQUIRE(((uintptr_t)table & 15) == 0 && ((uintptr_t)hyper & 15) == 0 && ((uintptr_t)born & 3) == 0 && ((uintptr_t)skip & 3) == 0 &&
+                      ((uintptr_t)grad_scale & 3) == 0,
+                  "%s: table and hyper must be 16-byte aligned, born, skip and grad_scale 4-byte aligned", who);
     const size_t need = sgd_table_bytes(n_tensors, n_chunks);
-    if (table_bytes < need) return frcnn_set_error(FRCNN_ERR_WORKSPACE, "sgd_step: short table, %zu < %zu bytes", table_bytes, need);
+    if (table_bytes < need) return frcnn_set_error(FRCNN_ERR_WORKSPACE, "%s: short table, %zu < %zu bytes", who, table_bytes, need);
     if (n_chunks == 0) return FRCNN_OK;                                     // every tensor is empty
     const SgdRow *rows = (const SgdRow *)((const char *)table + sizeof(SgdHeader));
     const int2 *map = (const int2 *)((const char *)table + sizeof(SgdHeader) + (size_t)n_tensors * sizeof(SgdRow));
     hipStream_t s = (hipStream_t)stream;
-    FRCNN_LAUNCH(sgd_update_kernel, dim3((unsigned)n_chunks), dim3(SGD_THREADS), 0, s, rows, map, n_tensors, (const float4 *)hyper, n_groups,
-                 (const int32_t *)born, skip);
+    if (scaled)
+        FRCNN_LAUNCH(sgd_update_kernel<true>, dim3((unsigned)n_chunks), dim3(SGD_THREADS), 0, s, rows, map, n_tensors, (const float4 *)hyper, n_groups,
+                     (const int32_t *)born, skip, grad_scale);
+    else
+        FRCNN_LAUNCH(sgd_update_kernel<false>, dim3((unsigned)n_chunks), dim3(SGD_THREADS), 0, s, rows, map, n_tensors, (const float4 *)hyper, n_groups,
+                     (const int32_t *)born, skip, (const float *)nullptr);
     FRCNN_LAUNCH(sgd_born_kernel, dim3((unsigned)((n_tensors + SGD_THREADS - 1) / SGD_THREADS)), dim3(SGD_THREADS), 0, s, rows, n_tensors,
                  (const float4 *)hyper, n_groups, born, skip);
     FRCNN_CHECK_LAUNCH("sgd kernels");
     return FRCNN_OK;
+}
+
+// train.py:35-37 (optimizer.step()) for the optimizer main.py:58-61 constructs.  Two launches, no host synchronisation, capturable.
+FRCNN_EXPORT int frcnn_sgd_step(const void *table, size_t table_bytes, int n_tensors, int n_chunks, const float *hyper, int n_groups, int32_t *born,
+                                const int32_t *skip, void *stream)
+{
+    return sgd_step_launch("sgd_step", table, table_bytes, n_tensors, n_chunks, hyper, n_groups, born, skip, nullptr, false, stream);
+}
+
+// train.py:35-37 with the gradient clipping torch.nn.utils.clip_grad_norm_ would do in front of optimizer.step(): the same two launches,
+// every gradient element multiplied by the device float *grad_scale (frcnn_grad_norm's coef) on its way into the rule.
+FRCNN_EXPORT int frcnn_sgd_step_scaled(const void *table, size_t table_bytes, int n_tensors, int n_chunks, const float *hyper, int n_groups, int32_t *born,
+                                       const int32_t *skip, const float *grad_scale, void *stream)
+{
+    return sgd_step_launch("sgd_step_scaled", table, table_bytes, n_tensors, n_chunks, hyper, n_groups, born, skip, grad_scale, true, stream);
 }

@@ -11,9 +11,19 @@ The update rule is torch.optim.SGD's (dampening 0, no Nesterov, maximize=False),
 INTO them.  Whether a tensor has had its first update is device data too (one int32 "born" word per tensor), so a graph captured before
 any step is right from step 0 on, and a step skipped by the guard word leaves everything as it was.
 
+Gradient clipping and the non-finite skip (csrc/grad_norm.hip) are device data as well.  With `max_grad_norm` and / or `skip_nonfinite`
+two more launches in front of the update measure the global L2 norm of all trainable gradients (a binary64 sum in a fixed, documented
+order: include/frcnn_hip.h) and count their non-finite elements; a clip coefficient -- torch.nn.utils.clip_grad_norm_'s
+max_norm / (norm + 1e-6) clamped to 1 -- and a skip word land in a 64-byte state block, and the update multiplies the coefficient in as
+it reads the gradient: no extra pass over the gradients, `p.grad` is NOT scaled in place, no host synchronisation, capturable, four
+launches whatever the tensors are.  `max_grad_norm` is a Python float that `push_hyper()` carries to the device like the lr.  With both
+options off nothing changes: the same two launches and no further allocation.
+
 There is no fallback: anything the kernel does not cover (dampening, Nesterov, maximize, non-fp32, sparse or non-contiguous tensors or
 gradients, a trainable parameter without a gradient, CPU tensors) is refused with an exception."""
 import ctypes as C
+import math
+import struct
 
 import torch
 
@@ -45,6 +55,20 @@ def _check_group(g):
             raise ValueError("DeviceSGD: invalid %s: %r" % (k, v))
 
 
+def _check_max_grad_norm(v):
+    if torch.is_tensor(v):
+        raise ValueError("DeviceSGD: max_grad_norm must be a Python number (the device block is written by push_hyper()), got a tensor")
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or math.isnan(v) or not v > 0:
+        raise ValueError("DeviceSGD: invalid max_grad_norm: %r (a number > 0)" % (v,))
+    return float(v)
+
+
+# the state block of csrc/grad_norm.hip (frcnn_grad_norm_state, include/frcnn_hip.h): byte offsets, and the whole block for struct.unpack
+GN_STATE_BYTES, GN_OFF_MAX_NORM, GN_OFF_FLAGS, GN_OFF_NORM, GN_OFF_COEF, GN_OFF_SKIP = 64, 0, 4, 16, 20, 24
+GN_STATE_FORMAT = "<fIdffiiii24x"
+GN_CLIP, GN_SKIP_NONFINITE = 1, 2
+
+
 def _check_dense(t, what, device=None):
     if not torch.is_tensor(t) or t.layout != torch.strided or t.is_sparse:
         raise TypeError("DeviceSGD: %s is not a dense strided tensor" % what)
@@ -59,10 +83,25 @@ def _check_dense(t, what, device=None):
 
 
 class DeviceSGD(torch.optim.Optimizer):
-    """DeviceSGD(params, lr, momentum=0, weight_decay=0, guard=None).  `guard`: a device int32 tensor of one element; while it is
-    non-zero a step changes nothing (parameters, momentum, born words).  Parameters with requires_grad=False take no part."""
+    """DeviceSGD(params, lr, momentum=0, weight_decay=0, guard=None, max_grad_norm=None, skip_nonfinite=False).  `guard`: a device int32
+    tensor of one element; while it is non-zero a step changes nothing (parameters, momentum, born words).  Parameters with
+    requires_grad=False take no part.
 
-    def __init__(self, params, lr=1e-3, momentum=0, weight_decay=0, dampening=0, nesterov=False, maximize=False, guard=None):
+    `max_grad_norm`: a Python float > 0; the gradients enter the update multiplied by min(1, max_grad_norm / (norm + 1e-6)), norm the global
+    L2 norm of all trainable gradients (norm_type 2 only).  The attribute may be changed later; push_hyper() (step() calls it) carries the
+    new value to the device, outside graphs.  `skip_nonfinite`: a step whose gradients hold an inf or a NaN changes nothing and is counted.
+    WHETHER the two are on is fixed here, because the launch sequence differs.  grad_stats() reads the last step's norm, coefficient,
+    skip word and the counters back; grad_norm_tensor is the norm as a device scalar.
+
+    The state dict stays torch.optim.SGD's, key for key: max_grad_norm and the counters (steps, skipped_steps) are NOT checkpointed --
+    pass max_grad_norm to the constructor again on resume; the counters restart at zero."""
+
+    def __init__(self, params, lr=1e-3, momentum=0, weight_decay=0, dampening=0, nesterov=False, maximize=False, guard=None,
+                 max_grad_norm=None, skip_nonfinite=False, norm_type=2.0):
+        if torch.is_tensor(norm_type) or isinstance(norm_type, bool) or not isinstance(norm_type, (int, float)) or float(norm_type) != 2.0:
+            raise ValueError("DeviceSGD: norm_type %r is not supported: the L2 norm only" % (norm_type,))
+        self._clip, self._skip_nonfinite = max_grad_norm is not None, bool(skip_nonfinite)
+        self.max_grad_norm = _check_max_grad_norm(max_grad_norm) if self._clip else None
         super().__init__(params, group_defaults(lr, momentum, weight_decay, dampening, nesterov, maximize))
         self._rows = []                                                   # (parameter, group index), trainable parameters in state-dict order
         for gi, g in enumerate(self.param_groups):
@@ -94,11 +133,16 @@ class DeviceSGD(torch.optim.Optimizer):
         self._table = torch.empty(self._table_bytes, dtype=torch.uint8, device=self.device)     # one address for good
         self._n_chunks = 0
         self._key = None
+        self._gn_state = self._gn_work = None                             # allocated by the first prepare() when clipping or skipping is on
+        self._gn_work_bytes = 0
+        self._pushed_max_norm = None
 
     # ---- hyper-parameters
     def push_hyper(self):
         """Writes the (lr, momentum, weight_decay) that changed since the last call into the device block: one stream-ordered fill per
-        changed value, no host synchronisation.  Never part of a graph: under capture a pending change is an error."""
+        changed value, no host synchronisation.  Never part of a graph: under capture a pending change is an error.  max_grad_norm travels
+        the same way (into the state block, once prepare() has allocated it)."""
+        self._push_max_norm()
         for gi, g in enumerate(self.param_groups):
             _check_group(g)
             now = (float(g["lr"]), float(g["momentum"]), float(g["weight_decay"]))
@@ -113,6 +157,24 @@ class DeviceSGD(torch.optim.Optimizer):
                     if old is None or old[k] != now[k]:
                         self._hyper[gi, k].fill_(now[k])
             self._pushed[gi] = now
+
+    def _push_max_norm(self):
+        if not self._clip:
+            if self.max_grad_norm is not None:
+                raise ValueError("DeviceSGD: max_grad_norm was None at construction: whether gradients are clipped is fixed there (the launch "
+                                 "sequence differs)")
+            return
+        if self.max_grad_norm is None:
+            raise ValueError("DeviceSGD: max_grad_norm cannot be switched off after construction (the launch sequence differs)")
+        now = _check_max_grad_norm(self.max_grad_norm)
+        if self._gn_state is None or now == self._pushed_max_norm:
+            return
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("DeviceSGD: max_grad_norm changed and the stream is capturing: the device block is written outside graphs -- "
+                               "call push_hyper() before the capture and before each replay")
+        with torch.no_grad():
+            self._gn_state[GN_OFF_MAX_NORM:GN_OFF_MAX_NORM + 4].view(torch.float32).fill_(now)
+        self._pushed_max_norm = now
 
     # ---- the table
     def _gradients(self):
@@ -140,6 +202,15 @@ class DeviceSGD(torch.optim.Optimizer):
             raise RuntimeError("DeviceSGD: a parameter or gradient address changed and the stream is capturing: run one eager step (or "
                                "prepare()) on the final gradient tensors before the capture")
         n = len(self._rows)
+        if (self._clip or self._skip_nonfinite) and self._gn_state is None:   # once; the kernels and every graph hold these addresses
+            chunks = sum((int(v) + 8191) // 8192 for v in self._numel)
+            self._gn_work_bytes = int(_lib.lib.frcnn_grad_norm_workspace_bytes(chunks))
+            with torch.no_grad():
+                self._gn_work = torch.empty(self._gn_work_bytes, dtype=torch.uint8, device=self.device)
+                self._gn_state = torch.zeros(GN_STATE_BYTES, dtype=torch.uint8, device=self.device)
+                self._gn_state[GN_OFF_FLAGS:GN_OFF_FLAGS + 4].view(torch.int32).fill_((GN_CLIP if self._clip else 0) |
+                                                                                    (GN_SKIP_NONFINITE if self._skip_nonfinite else 0))
+            self._push_max_norm()
         vp = C.c_void_p * n
         host = torch.empty(self._table_bytes, dtype=torch.uint8).pin_memory()                 # a fresh staging block per build: the copy below is asynchronous
         n_chunks = C.c_int32(0)
@@ -153,10 +224,42 @@ class DeviceSGD(torch.optim.Optimizer):
     def launch(self):
         """The library launch alone (what a graph records): no hyper-parameter write."""
         self.prepare()
-        _lib.check(_lib.lib.frcnn_sgd_step(
-            C.c_void_p(self._table.data_ptr()), self._table_bytes, len(self._rows), self._n_chunks, C.c_void_p(self._hyper.data_ptr()),
-            len(self.param_groups), C.c_void_p(self._born.data_ptr()), C.c_void_p(self.guard.data_ptr()) if self.guard is not None else None,
-            C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), "frcnn_sgd_step")
+        guard = C.c_void_p(self.guard.data_ptr()) if self.guard is not None else None
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        head = (C.c_void_p(self._table.data_ptr()), self._table_bytes, len(self._rows), self._n_chunks)
+        tail = (C.c_void_p(self._hyper.data_ptr()), len(self.param_groups), C.c_void_p(self._born.data_ptr()))
+        if not (self._clip or self._skip_nonfinite):
+            _lib.check(_lib.lib.frcnn_sgd_step(*head, *tail, guard, stream), "frcnn_sgd_step")
+            return
+        state = self._gn_state.data_ptr()                                 # the guard goes INTO the state block's skip word
+        _lib.check(_lib.lib.frcnn_grad_norm(*head, C.c_void_p(state), guard, C.c_void_p(self._gn_work.data_ptr()), self._gn_work_bytes, stream),
+                   "frcnn_grad_norm")
+        skip = C.c_void_p(state + GN_OFF_SKIP)
+        if self._clip:
+            _lib.check(_lib.lib.frcnn_sgd_step_scaled(*head, *tail, skip, C.c_void_p(state + GN_OFF_COEF), stream), "frcnn_sgd_step_scaled")
+        else:
+            _lib.check(_lib.lib.frcnn_sgd_step(*head, *tail, skip, stream), "frcnn_sgd_step")
+
+    # ---- the gradient norm of the last step
+    def _need_state(self):
+        if not (self._clip or self._skip_nonfinite):
+            raise RuntimeError("DeviceSGD: no gradient norm is measured: construct with max_grad_norm and / or skip_nonfinite=True")
+        if self._gn_state is None:
+            raise RuntimeError("DeviceSGD: the state block is allocated by the first prepare() / step()")
+
+    @property
+    def grad_norm_tensor(self):
+        """The last measured global gradient norm: a 0-d float32 view of the state block on the device (no copy, no synchronisation) --
+        for logging from inside a capture."""
+        self._need_state()
+        return self._gn_state[GN_OFF_NORM:GN_OFF_NORM + 4].view(torch.float32)[0]
+
+    def grad_stats(self):
+        """The state block after the last step, as a dict: norm, coef, skip, nonfinite, steps, skipped_steps, sumsq (and max_norm as the
+        device holds it).  A device read-back: synchronises."""
+        self._need_state()
+        max_norm, _, sumsq, norm, coef, skip, nonfinite, steps, skipped = struct.unpack(GN_STATE_FORMAT, bytes(self._gn_state.cpu().numpy()))
+        return dict(norm=norm, coef=coef, skip=skip, nonfinite=nonfinite, steps=steps, skipped_steps=skipped, sumsq=sumsq, max_norm=max_norm)
 
     @torch.no_grad()
     def step(self, closure=None):

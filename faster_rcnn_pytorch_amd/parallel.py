@@ -7,6 +7,7 @@ gradient is 548 MB fp32 and xGMI is point-to-point (per-link bound ring), so lar
 DDP's 25 MB default amortise the per-collective latency; classifier.0 (411 MB) finishes its backward
 first, which lets its reduction overlap the whole conv backward.
 """
+import gc
 import os
 
 import torch
@@ -232,6 +233,11 @@ class GraphStep(object):
                     self._eager(f)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
+        # torch.cuda.graph no longer collects garbage before a capture (torch >= 2.9, unless torch.compiler.config.force_cudagraph_gc).  A
+        # dead Python cycle that holds graphs or device memory -- an earlier GraphStep whose forward_loss closure refers back to its owner --
+        # would otherwise be destroyed by whichever automatic collection comes next, possibly in the middle of a capture below, where
+        # destroying a graph is not permitted and aborts the process.  Collect now, while nothing is capturing.
+        gc.collect()
         pool = None
         for f in range(self.n):
             ga = torch.cuda.CUDAGraph()

@@ -685,6 +685,61 @@ int frcnn_sgd_table_build_host(int n_tensors, const void *const *params_host, co
 int frcnn_sgd_step(const void *table, size_t table_bytes, int n_tensors, int n_chunks, const float *hyper, int n_groups, int32_t *born,
                    const int32_t *skip, void *stream);
 
+/* ---- optimizer: global gradient norm, clip coefficient and non-finite skip word, all in device memory ---------------------------------
+ * What torch.nn.utils.clip_grad_norm_(parameters, max_norm) in front of optimizer.step() (train.py:35-37) computes, without its pass
+ * that rewrites the gradients and without a host read: frcnn_grad_norm measures the L2 norm of every gradient of an SGD table (the
+ * table frcnn_sgd_table_build_host made: rows and chunk map are reused as they are) and counts the non-finite elements, and leaves a clip
+ * coefficient and a skip word in a device state block; frcnn_sgd_step_scaled is frcnn_sgd_step with every gradient element multiplied by
+ * a device float (that coefficient) on its way into the rule: round(g * coef), the bits of torch's in-place g.mul_(coef) followed by
+ * torch.optim.SGD.  The gradients are never written.
+ *
+ * The state block: 64 bytes of DEVICE memory, 16-byte aligned.  max_norm and flags are inputs, written by the caller outside any graph;
+ * steps and skipped_steps are running counters the caller zeroes once; everything else is rewritten by every call. */
+typedef struct {
+    float max_norm;          /*  0  in   the clip threshold (read when FRCNN_GRAD_NORM_CLIP is set) */
+    uint32_t flags;          /*  4  in   FRCNN_GRAD_NORM_CLIP | FRCNN_GRAD_NORM_SKIP_NONFINITE */
+    double sumsq;            /*  8  out  the sum of the squares, binary64, in the order below */
+    float norm;              /* 16  out  (float)sqrt(sumsq), both correctly rounded */
+    float coef;              /* 20  out  clip set: c = max_norm / (norm + 1e-6f) in binary32, c > 1 ? 1 : c (a NaN stays NaN); else 1 */
+    int32_t skip;            /* 24  out  1 or 0: (SKIP_NONFINITE set and nonfinite != 0) or (user_guard given and *user_guard != 0) */
+    int32_t nonfinite;       /* 28  out  elements whose exponent field is all ones (inf, NaN), saturating at INT32_MAX */
+    int32_t steps;           /* 32  i/o  += 1 per call */
+    int32_t skipped_steps;   /* 36  i/o  += skip per call */
+    int32_t reserved[6];     /* 40       not touched */
+} frcnn_grad_norm_state;
+#define FRCNN_GRAD_NORM_CLIP 1u
+#define FRCNN_GRAD_NORM_SKIP_NONFINITE 2u
+#define FRCNN_GRAD_NORM_FINISH_THREADS 1024
+/* The summation order is part of the contract: sumsq depends on the gradient VALUES and on each element's position in its tensor only --
+ * never on pointer alignment, on which load path ran, on residency or on timing.  No atomics; no workgroup waits on another.
+ *   element  every element x is widened to binary64 and squared there (exact: 48 significant bits).
+ *   chunk    chunk c of a tensor holds its elements [8192 c, 8192 c + n), n <= 8192, element i of the chunk at position i.  One workgroup
+ *            of 256 threads.  Thread t, t = (i / 4) % 256, owns the elements i with that t; it keeps four binary64 accumulators, one per
+ *            e = i % 4, each starting at +0 and taking its squares in increasing i (j = i / 1024 = 0 .. 7); then a = (a0 + a1) + (a2 + a3).
+ *   wave     the 64 threads of a wave (t / 64) combine by an xor butterfly: for d = 32, 16, 8, 4, 2, 1: a[t] = a[t] + a[t ^ d] (every
+ *            lane ends with the same bits).
+ *   block    partial[c] = ((w0 + w1) + w2) + w3, the four waves in wave order; stored with a plain store, the chunk's int32 count of
+ *            non-finite elements beside it.
+ *   finish   one workgroup of T = FRCNN_GRAD_NORM_FINISH_THREADS threads over the n_chunks partials in map order (tensor by tensor,
+ *            chunk by chunk): thread t starts at +0 and adds partials t, t + T, t + 2T, ... in that order; then the butterfly above
+ *            inside each of the 16 waves; then the waves in wave order, (((w0 + w1) + w2) + ...) + w15.  Counts: the same tree in int64.
+ * Finite gradients cannot overflow the sum (at most 2^56 squares below 2^256 each); a norm above FLT_MAX becomes +inf and coef 0, as torch's
+ * fp32 norm does.  tests/grad_norm_ref.py restates all of it in numpy.
+ *
+ * frcnn_grad_norm_workspace_bytes: bytes for n_chunks partials and counts (at least 16); 0 for a negative count.  The workspace is
+ * 16-byte aligned device memory, fully rewritten by every call.  frcnn_grad_norm (train.py:35-37): two launches whatever the tensors
+ * are, no host synchronisation, capturable; n_chunks == 0 (every tensor empty) still runs the finish (norm 0).  user_guard: NULL, or a
+ * device int32 OR-ed into the skip word.  frcnn_sgd_step_scaled (train.py:35-37): frcnn_sgd_step's arguments and refusals, and
+ * grad_scale, a device float, 4-byte aligned, not NULL -- &state->coef.  Pass &state->skip as `skip` to either step function.
+ * FRCNN_ERR_INVALID_ARG before anything is launched: a NULL table / state / workspace, n_tensors outside 1 .. 65536, a negative
+ * n_chunks, a table, state or workspace that is not 16-byte aligned, a user_guard that is not 4-byte aligned; FRCNN_ERR_WORKSPACE: a
+ * table shorter than n_tensors and n_chunks need, a workspace shorter than frcnn_grad_norm_workspace_bytes(n_chunks). */
+size_t frcnn_grad_norm_workspace_bytes(int n_chunks);
+int frcnn_grad_norm(const void *table, size_t table_bytes, int n_tensors, int n_chunks, frcnn_grad_norm_state *state, const int32_t *user_guard,
+                    void *workspace, size_t workspace_bytes, void *stream);
+int frcnn_sgd_step_scaled(const void *table, size_t table_bytes, int n_tensors, int n_chunks, const float *hyper, int n_groups, int32_t *born,
+                          const int32_t *skip, const float *grad_scale, void *stream);
+
 /* ---- in-library kernel timing (HIP events on the launch stream) -------------------------------------- */
 /* When enabled, every kernel launch made by this library is bracketed by two hipEventRecord on the
  * caller's stream.  frcnn_prof_collect() synchronises those events (call it after the stream is idle)
