@@ -302,6 +302,8 @@ __global__ __launch_bounds__(1024) void rpn_sample_kernel(int N, const int8_t *_
         const int8_t want = (int8_t)cls_id;
         const int64_t *perm = cls_id == 1 ? perm_pos : perm_neg;
         const int n_perm = cls_id == 1 ? n_perm_pos : n_perm_neg;
+        if (n_c == 0 && n_perm == 0) continue;              // nothing to demote (n_pos > 256 makes `n_neg > 256 - n_pos` true for n_neg = 0:
+                                                            // the reference draws randperm(0) there); a zero-length permutation needs no pointer
         if (perm == nullptr || n_perm != n_c) {             // uniform
             if (threadIdx.x == 0) counts[2] = 1;
             continue;
@@ -759,7 +761,8 @@ __global__ __launch_bounds__(1024) void head_targets_kernel(int variant, const f
     const int n_neg = min(total - n_pos, nnc);
     const bool host_mode = (perm_pos != nullptr) || (perm_neg != nullptr);
     if (host_mode) {
-        if (perm_pos == nullptr || perm_neg == nullptr || n_perm_pos != npc || n_perm_neg != nnc) { if (tid == 0) s_err = 1; }
+        // (an EMPTY candidate list goes with a zero-length permutation, the reference's randperm(0): no pointer needed for it)
+        if ((perm_pos == nullptr && npc > 0) || (perm_neg == nullptr && nnc > 0) || n_perm_pos != npc || n_perm_neg != nnc) { if (tid == 0) s_err = 1; }
         else {
             for (int j = tid; j < n_pos + n_neg; j += 1024) {
                 const int64_t p = j < n_pos ? perm_pos[j] : perm_neg[j - n_pos];
