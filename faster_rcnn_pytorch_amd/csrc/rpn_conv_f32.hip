@@ -466,18 +466,21 @@ template <> __device__ __forceinline__ void wn_gt<4>(const float *u, float *w)
 // (the plain one-thread-per-element form read 36-byte pieces 18 KB apart: 15 us at C = 512)
 // both = 1: ONE launch makes the forward's U (blocks [0, n)) and the data gradient's rotated U (blocks [n, 2n), into U2) -- a forward that will be
 // followed by a backward keeps the second for it (frcnn_conv3x3_f32_fwd's u_rotated) and the backward starts one launch shorter
+// One block of it: bid = the block's index in the weight transform's own grid, s = its 16 x (16 * 9 + 1) floats of LDS (the caller's: the launch
+// that also holds the input transform's strips lends its window buffer)
+#define WN_WS (16 * 9 + 1)
+#define WN_W_ROWS 1024                  // grid rows of weight blocks in the shared launch at the most (past that the blocks stride)
 template <int M>
-__global__ __launch_bounds__(256) void rpn_wino_weight_kernel(const float *__restrict__ w, float *__restrict__ U, float *__restrict__ U2, int Cout, int Cin,
-                                                              int tr_only)
+__device__ __forceinline__ void wn_weight_block(float (*s)[WN_WS], const float *__restrict__ w, float *__restrict__ U, float *__restrict__ U2, int Cout, int Cin,
+                                                int tr_only, unsigned bid)
 {
     // w [Cout][Cin][9].  forward: m = co, k = ci;  data gradient (TR): m = ci, k = co
     constexpr int A = Wn<M>::A;
-    __shared__ float s[16][16 * 9 + 1];
     const unsigned nblk = (unsigned)(Cout / 16) * (unsigned)(Cin / 16);
-    const bool TR = tr_only || blockIdx.x >= nblk;                        // uniform per block
-    const unsigned b = blockIdx.x >= nblk ? blockIdx.x - nblk : blockIdx.x;
+    const bool TR = tr_only || bid >= nblk;                               // uniform per block
+    const unsigned b = bid >= nblk ? bid - nblk : bid;
     const int Mo = TR ? Cin : Cout, K = TR ? Cout : Cin;
-    if (blockIdx.x >= nblk) U = U2;
+    if (bid >= nblk) U = U2;
     const unsigned nb = (unsigned)K / 16u, m0 = (b / nb) * 16u, k0 = (b % nb) * 16u, row = (unsigned)Cin * 9u;
 #pragma unroll
     for (unsigned q = 0; q < 9; ++q) {
@@ -506,6 +509,13 @@ __global__ __launch_bounds__(256) void rpn_wino_weight_kernel(const float *__res
 #pragma unroll
         for (int q = 0; q < A; ++q) U[(size_t)(r * A + q) * n + o] = u[q];
     }
+}
+template <int M>
+__global__ __launch_bounds__(256) void rpn_wino_weight_kernel(const float *__restrict__ w, float *__restrict__ U, float *__restrict__ U2, int Cout, int Cin,
+                                                              int tr_only)
+{
+    __shared__ float s[16][WN_WS];
+    wn_weight_block<M>(s, w, U, U2, Cout, Cin, tr_only, blockIdx.x);
 }
 
 // Staging loads of the input-side transforms.  The loads are inline assembly, unconditional, at clamped addresses (the window's zeros are a select
@@ -595,18 +605,18 @@ struct WnStrips { int first[FRCNN_MAX_LEVELS + 1]; int segs[FRCNN_MAX_LEVELS]; i
 // incoming gradient is at the POOLED resolution and the words carry, per 2 x 2 window of the tile, the position of the maximum and whether
 // it was positive (3 bits each): the window staged is the pooled one (half the rows and columns), and a thread rebuilds its full-resolution
 // patch from it -- max_pool2d's and the ReLU's backward without the full-resolution gradient ever existing in memory.
+// bx = the strip (all levels counted through), c = the channel: the block's place in the transform's own (strips x channels) grid
 template <int M, int MODE, bool POOL>
-__global__ __launch_bounds__(256) void rpn_wino_input_kernel(WnArgs a, WnStrips st, float *__restrict__ V)
+__device__ __forceinline__ void wn_input_strip(const WnArgs &a, const WnStrips &st, float *__restrict__ V, const int bx, const int c)
 {
     static_assert(!POOL || M == 4, "pooled gradients: 4 x 4 tiles only");
     constexpr int A = Wn<M>::A, P = Wn<M>::P, WT = Wn<M>::WT, HALO = MODE == 1 ? 0 : 1, IN = MODE == 1 ? M : A;
     constexpr int SM = POOL ? 2 : M, SIN = POOL ? (MODE == 1 ? 2 : 4) : IN;       // staged pixels per tile side; staged patch side
     extern __shared__ __attribute__((aligned(8))) float s[];          // the largest window of the launch's levels (wn_strips): <= Wn<M>::LDS floats
-    const int c = blockIdx.y;
     int l = 0;
 #pragma unroll
-    for (int q = 1; q < FRCNN_MAX_LEVELS; ++q) l += (q < a.n_levels && (int)blockIdx.x >= st.first[q]) ? 1 : 0;
-    const int strip = blockIdx.x - st.first[l], segs = st.segs[l], R = st.rows[l];
+    for (int q = 1; q < FRCNN_MAX_LEVELS; ++q) l += (q < a.n_levels && bx >= st.first[q]) ? 1 : 0;
+    const int strip = bx - st.first[l], segs = st.segs[l], R = st.rows[l];
     const int H = a.lv[l].H, W = a.lv[l].W, tw = a.lv[l].tw, th = (H + M - 1) / M;
     const int ty0 = (strip / segs) * R, tx0 = (strip % segs) * WT, wt = min(WT, tw - tx0), nr = min(R, th - ty0);
     const int Hs = POOL ? H >> 1 : H, Ws = POOL ? W >> 1 : W;              // the staged tensor's size (pooled: floor, like max_pool2d)
@@ -764,7 +774,7 @@ __global__ __launch_bounds__(256) void rpn_wino_input_kernel(WnArgs a, WnStrips 
         for (int h = 32; h > 0; h >>= 1) bsum += __shfl_down(bsum, h, 64);   // wave sums by lane shuffles (fixed tree), then four values through LDS
         if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = bsum;
         __syncthreads();
-        if (threadIdx.x == 0) a.db_part[(size_t)c * st.first[FRCNN_MAX_LEVELS] + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+        if (threadIdx.x == 0) a.db_part[(size_t)c * st.first[FRCNN_MAX_LEVELS] + bx] = (red[0] + red[1]) + (red[2] + red[3]);
     }
     if (a.zero_pad && strip == 0) {                                       // this level's padding columns of channel c, all planes
         const int T = a.lv[l].T, Tp = (T + a.tg - 1) / a.tg * a.tg, np = Tp - T;
@@ -773,6 +783,30 @@ __global__ __launch_bounds__(256) void rpn_wino_input_kernel(WnArgs a, WnStrips 
             (MODE == 2 ? a.out2 : V)[(size_t)xi * plane + col0 + T + q] = 0.0f;
         }
     }
+}
+template <int M, int MODE, bool POOL>
+__global__ __launch_bounds__(256) void rpn_wino_input_kernel(WnArgs a, WnStrips st, float *__restrict__ V)
+{
+    wn_input_strip<M, MODE, POOL>(a, st, V, (int)blockIdx.x, (int)blockIdx.y);
+}
+// The weight transform and the input transform of one call (neither reads what the other writes; both only feed the product) as ONE launch, the
+// disjoint union of their grids: rows [0, w_rows) of the grid are weight blocks -- first, so the latency-bound small launch of the two starts at
+// once and ends inside the other; they stride over the n_wblocks where those are more than w_rows rows hold -- and row w_rows + c is channel c of
+// the input transform.  The LDS is the launch's dynamic buffer, sized for the larger of the two bodies (wn_run).  amdgpu_waves_per_eu: left alone the union
+// took 79 VGPRs at m = 4 (six waves per SIMD) where the input transform has 54 (seven); held to the input transform's occupancy it compiles to 72, no scratch.
+template <int M>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(M == 4 ? 7 : 8))) void rpn_wino_weight_input_kernel(WnArgs a, WnStrips st, float *__restrict__ V, const float *__restrict__ w, float *__restrict__ U,
+                                                                    float *__restrict__ U2, int Cout, int Cin, int tr_only, unsigned n_wblocks, unsigned w_rows)
+{
+    if (blockIdx.y < w_rows) {                                            // uniform per block
+        extern __shared__ __attribute__((aligned(8))) float ws[];
+        for (unsigned b = blockIdx.y * gridDim.x + blockIdx.x; b < n_wblocks; b += w_rows * gridDim.x) {
+            wn_weight_block<M>((float (*)[WN_WS])ws, w, U, U2, Cout, Cin, tr_only, b);
+            __syncthreads();                                              // the next block's tile goes where this one's is still being read
+        }
+        return;
+    }
+    wn_input_strip<M, 0, false>(a, st, V, (int)blockIdx.x, (int)(blockIdx.y - w_rows));
 }
 
 // POOL (m = 4): ReLU + max_pool2d(2, 2) in the same pass -- the tile's four 2 x 2 windows -> the pooled outputs [C][H/2][W/2] (floor) and, per window,
@@ -864,12 +898,13 @@ __device__ __forceinline__ void wn_output_tile(const WnArgs &a, int c, int t, co
     if (a.bits_out) a.bits_out[at] = (unsigned short)word;
 }
 
+// bx, c: the block's place in the transform's own (tiles / 256 x channels) grid
 template <int M, bool POOL>
-__global__ __launch_bounds__(256) void rpn_wino_output_kernel(WnArgs a, const float *__restrict__ Mp)
+__device__ __forceinline__ void wn_output_block(const WnArgs &a, const float *__restrict__ Mp, const int bx, const int c)
 {
     static_assert(!POOL || M == 4, "fused pooling: 4 x 4 tiles only");
     constexpr int A = Wn<M>::A, P = Wn<M>::P;
-    const int t = blockIdx.x * 256 + threadIdx.x, c = blockIdx.y;
+    const int t = bx * 256 + threadIdx.x;
     if (t >= a.Ttot) return;
     const size_t plane = (size_t)a.C * a.Ttot, at = (size_t)c * a.Ttot + t;
     float mv[P];
@@ -885,18 +920,24 @@ __global__ __launch_bounds__(256) void rpn_wino_output_kernel(WnArgs a, const fl
         }
     wn_output_tile<M, POOL>(a, c, t, mv);
 }
+template <int M, bool POOL>
+__global__ __launch_bounds__(256) void rpn_wino_output_kernel(WnArgs a, const float *__restrict__ Mp)
+{
+    wn_output_block<M, POOL>(a, Mp, (int)blockIdx.x, (int)blockIdx.y);
+}
 
 // dW[co][ci] = G^T dU G: (m + 2)^2 -> 3 x 3, thread = (co, ci); n = Cout * Cin
 // blocks past the (co, ci) range: the bias gradient, one block per channel adds the output-gradient transform's strip partials in strip order
+// (bid = the block's index in this transform's own grid)
 template <int M>
-__global__ __launch_bounds__(256) void rpn_wino_dw_kernel(const float *__restrict__ dU, float *__restrict__ dw, unsigned n, float *__restrict__ db,
-                                                          const float *__restrict__ db_part, int n_strips)
+__device__ __forceinline__ void wn_dw_block(const float *__restrict__ dU, float *__restrict__ dw, unsigned n, float *__restrict__ db,
+                                            const float *__restrict__ db_part, int n_strips, const unsigned bid)
 {
     constexpr int A = Wn<M>::A;
     const unsigned dw_blocks = (n + 255u) / 256u;
-    if (blockIdx.x >= dw_blocks) {
+    if (bid >= dw_blocks) {
         __shared__ float red[256];
-        const unsigned c = blockIdx.x - dw_blocks;
+        const unsigned c = bid - dw_blocks;
         float t = 0.0f;
         for (int i = threadIdx.x; i < n_strips; i += 256) t += db_part[(size_t)c * n_strips + i];      // fixed assignment and order: bit-reproducible
         red[threadIdx.x] = t;
@@ -909,7 +950,7 @@ __global__ __launch_bounds__(256) void rpn_wino_dw_kernel(const float *__restric
         if (threadIdx.x == 0) db[c] = red[0];
         return;
     }
-    const unsigned o = blockIdx.x * 256u + threadIdx.x;
+    const unsigned o = bid * 256u + threadIdx.x;
     if (o >= n) return;
     float t[3][A];                                                        // t[i][q] = (G^T u[.][q])_i
 #pragma unroll
@@ -928,6 +969,30 @@ __global__ __launch_bounds__(256) void rpn_wino_dw_kernel(const float *__restric
 #pragma unroll
         for (int j = 0; j < 3; ++j) dw[(size_t)o * 9 + i * 3 + j] = w3[j];
     }
+}
+template <int M>
+__global__ __launch_bounds__(256) void rpn_wino_dw_kernel(const float *__restrict__ dU, float *__restrict__ dw, unsigned n, float *__restrict__ db,
+                                                          const float *__restrict__ db_part, int n_strips)
+{
+    wn_dw_block<M>(dU, dw, n, db, db_part, n_strips, blockIdx.x);
+}
+// The last launches of a layer's two gradients -- the data gradient's output transform and the weight gradient's G^T dU G (with the bias sums) -- as
+// ONE launch, the disjoint union of their grids (frcnn_conv3x3_f32_bwd): rows [0, dw_rows) of the grid hold the n_dw_blocks blocks of the second,
+// striding where they are more than the rows hold; row dw_rows + c is channel c of the first.  (amdgpu_waves_per_eu: 74 VGPRs at m = 4 otherwise, against the
+// output transform's 72 and seven waves per SIMD; 70 with it, no scratch.)
+template <int M>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(M == 4 ? 7 : 8))) void rpn_wino_output_dw_kernel(WnArgs a, const float *__restrict__ Mp, const float *__restrict__ dU, float *__restrict__ dw, unsigned n,
+                                                                 float *__restrict__ db, const float *__restrict__ db_part, int n_strips, unsigned n_dw_blocks,
+                                                                 unsigned dw_rows)
+{
+    if (blockIdx.y < dw_rows) {                                           // uniform per block
+        for (unsigned b = blockIdx.y * gridDim.x + blockIdx.x; b < n_dw_blocks; b += dw_rows * gridDim.x) {
+            wn_dw_block<M>(dU, dw, n, db, db_part, n_strips, b);
+            __syncthreads();                                              // (a bias block's sums in LDS: read before the next block writes there)
+        }
+        return;
+    }
+    wn_output_block<M, false>(a, Mp, (int)blockIdx.x, (int)(blockIdx.y - dw_rows));
 }
 
 #ifdef WN_STAMP                                                      // developer build (tools/dev/wn_stamps.py): wall-clock stamps (100 MHz) of every workgroup of the last launch
@@ -968,8 +1033,10 @@ __device__ __forceinline__ void wn_cut8(const float *v, wn_u32x4 &h, wn_u32x4 &m
         l[p] = __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, qb), __builtin_bit_cast(unsigned, qa), 0x07060302u);
     }
 }
+// One workgroup of the product: bid = its index among the product's own a.G workgroups, smem = 2 x WN_KC x (MT + NW) floats of LDS (16-byte aligned) and
+// s_last a word of LDS, both the calling kernel's -- the launch that holds two products lends both bodies the same bytes
 template <bool NT, int MT, int NW, bool SPLIT>
-__global__ __launch_bounds__(256, CF_WPS) void rpn_wino_gemm_kernel(WgArgs a, float *__restrict__ part, int *__restrict__ cnt)
+__device__ __forceinline__ void wn_gemm_block(const WgArgs &a, float *__restrict__ part, int *__restrict__ cnt, const unsigned bid, float *smem, int &s_last)
 {
     WN_STAMP_AT(0);
     constexpr int MI = MT / 64, NI = NW / 64, NG = MI * NI;          // MFMA tiles per wave
@@ -978,13 +1045,12 @@ __global__ __launch_bounds__(256, CF_WPS) void rpn_wino_gemm_kernel(WgArgs a, fl
     // <true>:  MT (NW) rows x 32 k (k contiguous in memory): row r's eight 16-byte pieces sit at slots p ^ ((r >> 1) & 7) of its 128 LDS bytes -- the
     //          DMA's LDS image is lane-linear, but which global piece a lane fetches is free -- so that the ds_read_b128 of 16 different rows
     //          (one lane group) hit 16 different bank quads
-    __shared__ __attribute__((aligned(16))) float sA[2][WN_KC * MT];
-    __shared__ __attribute__((aligned(16))) float sB[2][WN_KC * NW];
-    __shared__ int s_last;
+    float (*sA)[WN_KC * MT] = (float (*)[WN_KC * MT])smem;
+    float (*sB)[WN_KC * NW] = (float (*)[WN_KC * NW])(smem + 2 * WN_KC * MT);
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1, li = lane & 31, lh = lane >> 5;
     const int G = a.G, U_ = a.n_units, Kc = a.Kc, lda = a.lda, ldb = a.ldb, ldo = a.ldo;
-    const int sigma = (G % 8 == 0) ? (int)(blockIdx.x & 7) * (G >> 3) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+    const int sigma = (G % 8 == 0) ? (int)(bid & 7) * (G >> 3) + (int)(bid >> 3) : (int)bid;
     const int u0 = a.whole ? (int)cf_start(sigma, U_ / Kc, G) * Kc : (int)cf_start(sigma, U_, G);
     const int u1 = a.whole ? (int)cf_start(sigma + 1, U_ / Kc, G) * Kc : (int)cf_start(sigma + 1, U_, G);
     if (u0 >= u1) return;
@@ -1314,6 +1380,26 @@ __global__ __launch_bounds__(256, CF_WPS) void rpn_wino_gemm_kernel(WgArgs a, fl
 #endif
     }
 }
+template <bool NT, int MT, int NW, bool SPLIT>
+__global__ __launch_bounds__(256, CF_WPS) void rpn_wino_gemm_kernel(WgArgs a, float *__restrict__ part, int *__restrict__ cnt)
+{
+    __shared__ __attribute__((aligned(16))) float smem[2 * WN_KC * (MT + NW)];
+    __shared__ int s_last;
+    wn_gemm_block<NT, MT, NW, SPLIT>(a, part, cnt, blockIdx.x, smem, s_last);
+}
+// The two products of a layer's backward -- the data gradient's (K-major form) and the weight gradient's (k-contiguous form), which read the same
+// transformed output gradient and nothing of each other -- as ONE launch, the disjoint union of their grids: workgroups [0, a1.G) run the first with
+// its own ranges, slabs and tickets, the a2.G behind them the second with ITS ranges, slabs and tickets (part2 / cnt2), each exactly as in a launch
+// of its own; the second product's workgroups start where the first one's tail leaves workgroup slots empty.
+template <int MT1, int NW1, int MT2, int NW2, bool SPLIT>
+__global__ __launch_bounds__(256, CF_WPS) void rpn_wino_gemm2_kernel(WgArgs a1, WgArgs a2, float *__restrict__ part1, int *__restrict__ cnt1, float *__restrict__ part2,
+                                                                     int *__restrict__ cnt2)
+{
+    __shared__ __attribute__((aligned(16))) float smem[2 * WN_KC * ((MT1 + NW1) > (MT2 + NW2) ? (MT1 + NW1) : (MT2 + NW2))];
+    __shared__ int s_last;
+    if (blockIdx.x < (unsigned)a1.G) wn_gemm_block<false, MT1, NW1, SPLIT>(a1, part1, cnt1, blockIdx.x, smem, s_last);      // uniform per block
+    else wn_gemm_block<true, MT2, NW2, SPLIT>(a2, part2, cnt2, blockIdx.x - (unsigned)a1.G, smem, s_last);
+}
 
 // ---- the product with the output transform fused in, for 64 output channels and K = 64 (conv1_2 and its data gradient at 600 x 1000) ----
 // There the stage is a byte mover: 0.35 GB of product planes written by the GEMM and read back by the output transform, for 11 GFLOP.  Here a workgroup
@@ -1434,6 +1520,30 @@ static int wn_launch_gemm(bool nt, int MT, int NW, const WgArgs &g, float *part,
     WN_GEMM_CASE(true, 64, 64)
 #undef WN_GEMM_CASE
     return frcnn_set_error(FRCNN_ERR_UNSUPPORTED, "conv3x3_f32: no GEMM for a %d x %d tile", MT, NW);
+}
+
+// The pairs (data gradient's tile | weight gradient's tile) whose layers gain from the shared launch, per layer of the VGG16 600 x 1000 step (one-call backward,
+// us, shared / two launches): conv2_1 246 / 277, conv5_x 107 / 113.  Where both products run 128 x 128 tiles the shared launch LOSES -- conv2_2 395 / 369,
+// conv3_2 355 / 289, conv4_2 358 / 287: the weight gradient's 256 ranges are sized for one workgroup per CU on the whole chip, and behind the other product's
+// 512 workgroups they land two to a CU on the half of the chip that frees up first -- so that pair, and every pair not measured, keeps two launches:
+// *launched = false and the caller launches the products one after the other
+static int wn_launch_gemm2(int MT1, int NW1, const WgArgs &g1, int MT2, int NW2, const WgArgs &g2, float *part1, int *cnt1, float *part2, int *cnt2, hipStream_t s,
+                           bool *launched)
+{
+    const bool split = g_wn_products.load() != 0;
+    *launched = true;
+#define WN_GEMM2_CASE(A1, B1, A2, B2)                                                                                                                      \
+    if (MT1 == A1 && NW1 == B1 && MT2 == A2 && NW2 == B2) {                                                                                                \
+        if (split) FRCNN_LAUNCH((rpn_wino_gemm2_kernel<A1, B1, A2, B2, true>), dim3((unsigned)(g1.G + g2.G)), dim3(256), 0, s, g1, g2, part1, cnt1, part2, cnt2);   \
+        else FRCNN_LAUNCH((rpn_wino_gemm2_kernel<A1, B1, A2, B2, false>), dim3((unsigned)(g1.G + g2.G)), dim3(256), 0, s, g1, g2, part1, cnt1, part2, cnt2); \
+        FRCNN_CHECK_LAUNCH("rpn_wino_gemm2_kernel");                                                                                                       \
+        return FRCNN_OK;                                                                                                                                   \
+    }
+    WN_GEMM2_CASE(64, 128, 128, 64)                                  // 64 -> 128 (VGG16 conv2_1)
+    WN_GEMM2_CASE(128, 64, 128, 128)                                 // multiples of 128 on a map whose tile total is padded to 64 (VGG16 conv5_x at 37 x 62)
+#undef WN_GEMM2_CASE
+    *launched = false;
+    return FRCNN_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- weight gradient
@@ -1639,7 +1749,7 @@ __global__ __launch_bounds__(256, CW_WPS) void rpn_conv3x3_f32_wgrad_kernel(CwAr
 
 // ---------------------------------------------------------------------------------------------------------------- host side
 // workspace (dedicated, ZERO before the first call, left zero by every call): [ticket words | transposed weights | slabs]
-struct CfWs { int *cnt; float *wt, *part, *U, *V, *M; size_t total; };
+struct CfWs { int *cnt, *cnt2; float *wt, *part, *part2, *U, *V, *M; size_t total; };      // cnt2 / part2: the second product of a launch that holds two
 static int cf_ranges()
 {
     static int per_dev[64];                                          // 0 = not asked yet; per device: one process may drive several
@@ -1661,11 +1771,13 @@ static CfWs cf_carve(void *ws, int C, size_t u_floats = 0, size_t vm_floats = 0)
     CfWs w; char *p = (char *)ws; size_t o = 0;
     auto take = [&](size_t b) { void *r = p ? p + o : nullptr; o += align_up(b, 256); return r; };
     w.cnt = (int *)take(CF_MAX_TILES * sizeof(int));
+    w.cnt2 = (int *)take(CF_MAX_TILES * sizeof(int));              // (at a fixed offset like cnt: every layer's calls leave the same words zero)
     w.wt = (float *)take((size_t)C * C * 9 * sizeof(float));
     const size_t fwd = (size_t)cf_ranges() * 2 * CF_SLAB * sizeof(float);
     const size_t wg_tiles = (size_t)(C / 32) * (C / 32);           // weight gradient: tiles x workgroups per tile <= max(tiles, CUs) slabs of one tile
     const size_t wg = std::max<size_t>(wg_tiles, (size_t)cf_ranges() / CF_WPS * CW_WPS) * (32 * 32 * 9) * sizeof(float);
     w.part = (float *)take(fwd > wg ? fwd : wg);
+    w.part2 = (float *)take(fwd / CF_WPS);                          // the k-contiguous product's ranges (wn_ranges_nt), two slabs each
     w.U = u_floats ? (float *)take(u_floats * sizeof(float)) : nullptr;
     w.V = vm_floats ? (float *)take(vm_floats * sizeof(float)) : nullptr;
     w.M = vm_floats ? (float *)take(vm_floats * sizeof(float)) : nullptr;
@@ -1804,10 +1916,13 @@ static int wn_strips(WnStrips *st, const WnArgs &a, const int *H, int n_levels, 
 // forward (transposed = false) or data gradient (true) of the convolution with w [Cout][Cin][3][3] through the Winograd domain: four
 // launches for all levels.  forward: K = Cin, M = Cout (+ bias, ReLU in the output transform);  data gradient: K = Cout, M = Cin, the
 // incoming gradient optionally masked by the forward's ReLU output
+// later != NULL (frcnn_conv3x3_f32_bwd): the output transform is not launched but described there -- the caller launches it with the weight gradient's last kernel
+// (and, with `products` set by the caller, the product too: gemm_pending -- the caller launches it with the weight gradient's product)
+struct WnOutLater { WnArgs a; const float *Mp; int Mo; bool pending; bool products; bool gemm_pending; WgArgs g; int MT, NW; };
 template <int M>
 static int wn_run(const float *const *in, float *const *out, const unsigned short *bits_in, const int *H, const int *W, int n_levels, int Cin, int Cout,
                   const float *w, bool transposed, const float *bias, int relu, unsigned short *bits_out, float *xt, void *workspace, hipStream_t s,
-                  bool pooled = false, const float *u_rot = nullptr, float *dm_out = nullptr, bool want_bias = false)
+                  bool pooled = false, const float *u_rot = nullptr, float *dm_out = nullptr, bool want_bias = false, WnOutLater *later = nullptr)
 {
     // relu (forward): 0 none, 1 ReLU, 2 ReLU + max_pool2d(2, 2);  pooled (data gradient): `in` is at the pooled resolution, bits_in are pool words
     constexpr int P = Wn<M>::P;
@@ -1823,8 +1938,11 @@ static int wn_run(const float *const *in, float *const *out, const unsigned shor
     FRCNN_REQUIRE(n_tiles <= CF_MAX_TILES && units < (1ll << 31), "conv3x3_f32: %lld tiles above the limit %d", n_tiles, CF_MAX_TILES);
     const unsigned wb = (unsigned)((Mo / 16) * (K / 16));
     const float *Uuse = ws.U;
+    // the weight transform rides in the input transform's launch (rpn_wino_weight_input_kernel) where that is the plain one (MODE 0, not pooled).
+    // Under the profiler brackets the two stay launches of their own: a bracket times ONE kernel name (the values are the same bits either way)
+    const bool w_in_input = !(transposed && u_rot) && !dm_out && !pooled && !frcnn_prof_on();
     if (transposed && u_rot) Uuse = u_rot;                           // the forward already made the rotated transform
-    else {
+    else if (!w_in_input) {
         FRCNN_LAUNCH(rpn_wino_weight_kernel<M>, dim3(!transposed && u_rot ? 2 * wb : wb), dim3(256), 0, s, w, ws.U, (float *)u_rot, Cout, Cin, transposed ? 1 : 0);
         FRCNN_CHECK_LAUNCH("rpn_wino_weight_kernel");
     }
@@ -1847,6 +1965,11 @@ static int wn_run(const float *const *in, float *const *out, const unsigned shor
         } else FRCNN_LAUNCH((rpn_wino_input_kernel<M, 2, false>), dim3((unsigned)n_strips, (unsigned)K), dim3(256), lds, s, a, st, Vb);
     } else if (pooled) {
         if constexpr (M == 4) FRCNN_LAUNCH((rpn_wino_input_kernel<4, 0, true>), dim3((unsigned)n_strips, (unsigned)K), dim3(256), lds, s, a, st, Vb);
+    } else if (w_in_input) {
+        // weight blocks: as many grid rows as hold them all, WN_W_ROWS at the most (a 512 -> 512 layer on a one-strip map has 2048 of them)
+        const unsigned n_wb = !transposed && u_rot ? 2 * wb : wb, w_rows = std::min<unsigned>((n_wb + (unsigned)n_strips - 1) / (unsigned)n_strips, WN_W_ROWS);
+        FRCNN_LAUNCH(rpn_wino_weight_input_kernel<M>, dim3((unsigned)n_strips, (unsigned)K + w_rows), dim3(256), std::max(lds, sizeof(float) * 16 * WN_WS), s, a, st, Vb,
+                     w, ws.U, (float *)u_rot, Cout, Cin, transposed ? 1 : 0, n_wb, w_rows);
     } else FRCNN_LAUNCH((rpn_wino_input_kernel<M, 0, false>), dim3((unsigned)n_strips, (unsigned)K), dim3(256), lds, s, a, st, Vb);
     FRCNN_CHECK_LAUNCH("rpn_wino_input_kernel");
     if constexpr (M == 4) {
@@ -1875,8 +1998,11 @@ static int wn_run(const float *const *in, float *const *out, const unsigned shor
         // with two partial segments, their slabs and a reduction per tile
         else if (n_tiles <= g.G && n_tiles * WN_ONE_TILE_DEN >= (long long)g.G * WN_ONE_TILE_NUM) { g.G = (int)n_tiles; g.whole = 1; }
     }
-    { const int rc = wn_launch_gemm(false, MT, a.tg, g, ws.part, ws.cnt, s); if (rc) return rc; }
+    // (not where this product reads the workspace's U, which the weight gradient's product overwrites: only with the forward's rotated transform at hand)
+    if (later && later->products && relu != 2 && Uuse != ws.U) { later->g = g; later->MT = MT; later->NW = a.tg; later->gemm_pending = true; }
+    else { const int rc = wn_launch_gemm(false, MT, a.tg, g, ws.part, ws.cnt, s); if (rc) return rc; }
     a.C = Mo; a.bias = bias; a.relu = relu; a.bits_out = bits_out;
+    if (later && relu != 2) { later->a = a; later->Mp = ws.M; later->Mo = Mo; later->pending = true; return FRCNN_OK; }
     if (relu == 2) {
         if constexpr (M == 4) FRCNN_LAUNCH((rpn_wino_output_kernel<4, true>), dim3((unsigned)((Ttot + 255) / 256), (unsigned)Mo), dim3(256), 0, s, a, ws.M);
     } else FRCNN_LAUNCH((rpn_wino_output_kernel<M, false>), dim3((unsigned)((Ttot + 255) / 256), (unsigned)Mo), dim3(256), 0, s, a, ws.M);
@@ -1988,7 +2114,8 @@ FRCNN_EXPORT int frcnn_conv3x3_f32_bwd_data(const float *const *dy_dev, const un
 // bias gradient)
 template <int M>
 static int wn_wgrad(const float *const *feats, const float *const *d_outs, const unsigned short *bits, const int *H, const int *W, int n_levels, int Cin, int Cout,
-                    float *dw, float *dbias, const float *xt, void *workspace, hipStream_t s, bool pooled = false, const float *dm_in = nullptr)
+                    float *dw, float *dbias, const float *xt, void *workspace, hipStream_t s, bool pooled = false, const float *dm_in = nullptr,
+                    const WnOutLater *later = nullptr)
 {
     constexpr int P = Wn<M>::P;
     WnArgs a;
@@ -2026,9 +2153,29 @@ static int wn_wgrad(const float *const *feats, const float *const *d_outs, const
     FRCNN_CHECK_LAUNCH("rpn_wino_input_kernel");
     WgArgs g = {dm_in ? dm_in : ws.M, xt ? xt : ws.V, ws.U, Ttot * Cout, Ttot * Cin, (long long)Cout * Cin, (int)Ttot, (int)Ttot, Cin, mt, nt, (int)Kc, (int)units,
                 (int)std::min<long long>(wn_ranges_nt(), units), 0};
-    { const int rc = wn_launch_gemm(true, MT, NW, g, ws.part, ws.cnt, s); if (rc) return rc; }
-    const unsigned n = (unsigned)Cout * (unsigned)Cin;
-    FRCNN_LAUNCH(rpn_wino_dw_kernel<M>, dim3((n + 255u) / 256u + (dbias ? (unsigned)Cout : 0u)), dim3(256), 0, s, ws.U, dw, n, dbias, ws.wt, n_strips_dy);
+    bool both = false;
+    if (later && later->gemm_pending) {
+        // the data gradient's product, which that call left to this one: one launch for both where the pair of tile shapes is built, else its own launch first
+        const int rc = wn_launch_gemm2(later->MT, later->NW, later->g, MT, NW, g, ws.part, ws.cnt, ws.part2, ws.cnt2, s, &both);
+        if (rc) return rc;
+        if (!both) { const int rc1 = wn_launch_gemm(false, later->MT, later->NW, later->g, ws.part, ws.cnt, s); if (rc1) return rc1; }
+    }
+    if (!both) { const int rc = wn_launch_gemm(true, MT, NW, g, ws.part, ws.cnt, s); if (rc) return rc; }
+    const unsigned n = (unsigned)Cout * (unsigned)Cin, n_dw_blocks = (n + 255u) / 256u + (dbias ? (unsigned)Cout : 0u);
+    if (later && later->pending) {
+        // the data gradient's output transform, which that call left to this one: neither of the two kernels reads what the other writes
+        const unsigned gx = (unsigned)((later->a.Ttot + 255) / 256);
+        if (!frcnn_prof_on()) {                                      // (the profiler brackets time ONE kernel name each: separate launches there)
+            const unsigned dw_rows = std::min<unsigned>((n_dw_blocks + gx - 1) / gx, WN_W_ROWS);
+            FRCNN_LAUNCH(rpn_wino_output_dw_kernel<M>, dim3(gx, (unsigned)later->Mo + dw_rows), dim3(256), 0, s, later->a, later->Mp, ws.U, dw, n, dbias, ws.wt,
+                         n_strips_dy, n_dw_blocks, dw_rows);
+            FRCNN_CHECK_LAUNCH("rpn_wino_output_dw_kernel");
+            return FRCNN_OK;
+        }
+        FRCNN_LAUNCH((rpn_wino_output_kernel<M, false>), dim3(gx, (unsigned)later->Mo), dim3(256), 0, s, later->a, later->Mp);
+        FRCNN_CHECK_LAUNCH("rpn_wino_output_kernel");
+    }
+    FRCNN_LAUNCH(rpn_wino_dw_kernel<M>, dim3(n_dw_blocks), dim3(256), 0, s, ws.U, dw, n, dbias, ws.wt, n_strips_dy);
     FRCNN_CHECK_LAUNCH("rpn_wino_dw_kernel");
     return FRCNN_OK;
 }
@@ -2046,6 +2193,41 @@ FRCNN_EXPORT int frcnn_conv3x3_f32_wgrad(const float *const *x_dev, const float 
     if (pooled) return frcnn_set_error(FRCNN_ERR_UNSUPPORTED, "conv3x3_f32_wgrad: a pooled gradient needs the forward's words and the 4 x 4 tile");
     return wn_wgrad<2>(x_dev, dy_dev, relu_bits_dev, H_host, W_host, n_levels, Cin, Cout, dw_dev, dbias_dev, x_transformed_dev, workspace, (hipStream_t)stream, false,
                        dy_transformed_dev);
+}
+
+// Both gradients of a layer whose forward kept the transformed activations, in one call: what frcnn_conv3x3_f32_bwd_data (with dy_transformed_dev) followed by
+// frcnn_conv3x3_f32_wgrad (with both cached transforms) computes, bit for bit, with the data gradient's output transform and the weight gradient's last kernel
+// as ONE launch (rpn_wino_output_dw_kernel) and, on the tile-shape pairs of wn_launch_gemm2, the two products as one (rpn_wino_gemm2_kernel): three or four
+// launches where the two calls make five.  A 64 -> 64 layer on the 4 x 4 tile, whose product and output transform are one kernel already, runs exactly the two
+// calls' launches.
+template <int M>
+static int wn_bwd(const float *const *dy, const unsigned short *bits, float *const *dx, const int *H, const int *W, int n_levels, int Cin, int Cout, const float *w,
+                  const float *u_rot, bool pooled, const float *xt, float *dyt, float *dw, float *dbias, void *workspace, hipStream_t s)
+{
+    // development A/B: FRCNN_CONV_F32_BWD_PRODUCTS=2 launches the two products of the call one after the other
+    static const bool two = [] { const char *e = getenv("FRCNN_CONV_F32_BWD_PRODUCTS"); return e && atoi(e) == 2; }();
+    WnOutLater later;
+    later.pending = later.gemm_pending = false;
+    later.products = !two && !frcnn_prof_on();                       // (under the profiler brackets every kernel name keeps launches of its own)
+    int rc = wn_run<M>(dy, dx, bits, H, W, n_levels, Cin, Cout, w, true, nullptr, 0, nullptr, nullptr, workspace, s, pooled, u_rot, dyt, dbias != nullptr, &later);
+    if (rc) return rc;
+    return wn_wgrad<M>(dy, dy, bits, H, W, n_levels, Cin, Cout, dw, dbias, xt, workspace, s, pooled, dyt, &later);
+}
+FRCNN_EXPORT int frcnn_conv3x3_f32_bwd(const float *const *dy_dev, const unsigned short *relu_bits_dev, float *const *dx_dev, const int *H_host, const int *W_host,
+                                       int n_levels, int Cin, int Cout, const float *w_dev, const float *u_rotated_dev, int pooled, const float *x_transformed_dev,
+                                       float *dy_transformed_dev, float *dw_dev, float *dbias_dev, void *workspace, size_t workspace_bytes, void *stream)
+{
+    int rc = cf_check((const void *const *)dy_dev, (const void *const *)dx_dev, H_host, W_host, n_levels, Cin, Cout, 64, 64, w_dev, workspace, workspace_bytes,
+                      "conv3x3_f32_bwd");
+    if (rc) return rc;
+    FRCNN_REQUIRE(x_transformed_dev && dy_transformed_dev && dw_dev, "conv3x3_f32_bwd: NULL pointer (both cached transforms and dw are required)");
+    if (pooled && (!relu_bits_dev || wn_pick_m(H_host, W_host, n_levels) != 4))
+        return frcnn_set_error(FRCNN_ERR_UNSUPPORTED, "conv3x3_f32_bwd: a pooled gradient needs the forward's words and the 4 x 4 tile");
+    if (wn_pick_m(H_host, W_host, n_levels) == 4)
+        return wn_bwd<4>(dy_dev, relu_bits_dev, dx_dev, H_host, W_host, n_levels, Cin, Cout, w_dev, u_rotated_dev, pooled != 0, x_transformed_dev, dy_transformed_dev, dw_dev,
+                         dbias_dev, workspace, (hipStream_t)stream);
+    return wn_bwd<2>(dy_dev, relu_bits_dev, dx_dev, H_host, W_host, n_levels, Cin, Cout, w_dev, u_rotated_dev, false, x_transformed_dev, dy_transformed_dev, dw_dev, dbias_dev,
+                     workspace, (hipStream_t)stream);
 }
 
 // ---- the stage's k-contiguous GEMM on its own: O[m][n] = sum_k A[m][k] B[n][k] (fp32, fixed summation order).  The weight gradient of a 1 x 1 convolution

@@ -964,8 +964,9 @@ def rpn_conv3x3(feats, w3):
 
 
 # ---- the same stage for the backbone's 3x3 convolutions (Cin != Cout, bias + ReLU in the output transform, ReLU's backward in the input transforms)
-def _conv3x3_call(fn, what, H, W, n, Cin, Cout, dev, args_of, mask=False, bias=False, cached=False, relu_bits=False, pooled=False, urot=False):
-    _conv_trace(what, Cin, Cout, H, W, mask, bias, cached, relu_bits, pooled, urot)
+def _conv3x3_call(fn, what, H, W, n, Cin, Cout, dev, args_of, mask=False, bias=False, cached=False, relu_bits=False, pooled=False, urot=False, trace=True):
+    if trace:
+        _conv_trace(what, Cin, Cout, H, W, mask, bias, cached, relu_bits, pooled, urot)
     Hh, Wh = _host_i32(H), _host_i32(W)
     nb = int(lib.frcnn_conv3x3_f32_workspace(_np_ptr(Hh), _np_ptr(Wh), n, Cin, Cout))
     if nb == 0:
@@ -1095,7 +1096,34 @@ def conv3x3_wgrad(xs, dys, relu_bits=None, want_bias=False, x_transformed=None, 
     return dw, db
 
 
-CONV3X3_MIN_WORK = 1 << 26         # Cin * Cout * positions: below this the stage's fixed costs (four launches per direction, partial-tile reduction) lose to
+def conv3x3_bwd(dys, w, x_transformed, relu_bits=None, pooled_from=None, u_rotated=None, want_bias=False):
+    """(dxs, dw, dbias | None) of conv3x3_fwd in ONE call (frcnn_conv3x3_f32_bwd): bit for bit conv3x3_bwd_data(..., dy_transformed=) followed by
+    conv3x3_wgrad(..., x_transformed=, dy_transformed=), one launch shorter.  x_transformed: what conv3x3_fwd(..., keep_transformed=True) returned."""
+    w = _req(w, name="w")
+    Cout, Cin = int(w.shape[0]), int(w.shape[1])
+    dys = _conv3x3_levels(dys, Cout, "d_out")
+    hw = _conv3x3_full_sizes(dys, pooled_from)
+    relu_bits = _conv3x3_bits(relu_bits, hw, Cout)
+    dev = dys[0].device
+    H, W = [h for h, _ in hw], [w_ for _, w_ in hw]
+    x_transformed = _req(x_transformed, torch.float32, "x_transformed")
+    if x_transformed.numel() != int(lib.frcnn_conv3x3_f32_xt_floats(_np_ptr(_host_i32(H)), _np_ptr(_host_i32(W)), len(hw), Cin)):
+        raise ValueError("conv3x3_bwd: x_transformed does not belong to these shapes")
+    dxs = [torch.empty((1, Cin, h, w_), dtype=torch.float32, device=dev) for h, w_ in hw]
+    dyt = conv3x3_dy_buffer(hw, Cout, dev)
+    dw = torch.empty((Cout, Cin, 3, 3), dtype=torch.float32, device=dev)
+    db = torch.empty((Cout,), dtype=torch.float32, device=dev) if want_bias else None
+    gp, xp = _ptr_list(dys), _ptr_list(dxs)
+    # the trace keeps the two calls this one stands for (bench.py prices the stage's work from them)
+    _conv_trace("conv3x3_f32_bwd_data", Cin, Cout, H, W, relu_bits is not None, False, True, False, bool(pooled_from), u_rotated is not None)
+    _conv3x3_call(lib.frcnn_conv3x3_f32_bwd, "conv3x3_f32_bwd", H, W, len(dys), Cin, Cout, dev,
+                  lambda Hp, Wp, ws, nws, st: (gp, _ptr(relu_bits), xp, Hp, Wp, len(dys), Cin, Cout, _ptr(w), _ptr(u_rotated), 1 if pooled_from else 0, _ptr(x_transformed),
+                                               _ptr(dyt), _ptr(dw), _ptr(db), ws, nws, st), trace=False)
+    _conv_trace("conv3x3_f32_wgrad", Cin, Cout, H, W, relu_bits is not None, want_bias, True, False, bool(pooled_from), True)
+    return dxs, dw, db
+
+
+CONV3X3_MIN_WORK = 1 << 26        # Cin * Cout * positions: below this the stage's fixed costs (four launches per direction, partial-tile reduction) lose to
                                    # the vendor kernel (tools/dev/conv_layers_time.py: since the tile totals are padded to 64 where that pays, 256 -> 256 on 25 x 42
                                    # wins too -- 38.7 against 41.8 us forward, 92 against 108 with the gradients; smaller maps were not measured and stay)
 
@@ -1141,6 +1169,10 @@ class _Conv3x3F32Fn(torch.autograd.Function):
         g = g.contiguous()
         want_w = ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2])
         want_b = bool(ctx.has_bias and ctx.needs_input_grad[2])
+        if ctx.needs_input_grad[3] and want_w and xt is not None:
+            # both gradients and the forward's transformed activations at hand: one call, whose last launch serves both gradients
+            dxs, dw, db = conv3x3_bwd([g], w, xt, mask, [tuple(x.shape[2:])] if ctx.pool else None, u_rotated=urot, want_bias=want_b)
+            return None, (dw if ctx.needs_input_grad[1] else None), db, dxs[0]
         # both gradients: the data gradient's call stages dy once and leaves its weight-gradient transform (and the bias partials) for the call behind it
         dyt = conv3x3_dy_buffer([tuple(x.shape[2:])], int(w.shape[0]), g.device) if (ctx.needs_input_grad[3] and want_w) else None
         dx = None

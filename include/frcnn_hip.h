@@ -273,6 +273,15 @@ int frcnn_conv3x3_f32_bwd_data(const float *const *dy_levels, const unsigned sho
 int frcnn_conv3x3_f32_wgrad(const float *const *x_levels, const float *const *dy_levels, const unsigned short *relu_bits, const int *H_host, const int *W_host,
                             int n_levels, int Cin, int Cout, float *dw, float *dbias, const float *x_transformed, int pooled, const float *dy_transformed,
                             void *workspace, size_t workspace_bytes, void *stream);
+/* Both gradients of a layer whose forward kept x_transformed, in ONE call: bit for bit what _bwd_data (given dy_transformed, want_bias_partials = dbias != NULL)
+ * followed by _wgrad (given x_transformed and that dy_transformed) leave in dx_levels, dy_transformed, dw and dbias, in fewer launches -- the data gradient's
+ * output transform and the weight gradient's last kernel, which do not depend on each other, share one, and so do the two products on the tile shapes where
+ * that was measured to gain (given u_rotated; each product keeps its ranges and its order of summation).  x_transformed, dy_transformed (scratch of
+ * frcnn_conv3x3_f32_xt_floats(H, W, n_levels, Cout) floats) and dw are required; relu_bits, u_rotated and dbias are optional as in the two calls; Cin and
+ * Cout multiples of 64.  A caller that wants one gradient only, or has no cached transform, makes the two calls above. */
+int frcnn_conv3x3_f32_bwd(const float *const *dy_levels, const unsigned short *relu_bits, float *const *dx_levels, const int *H_host, const int *W_host,
+                          int n_levels, int Cin, int Cout, const float *w, const float *u_rotated, int pooled, const float *x_transformed,
+                          float *dy_transformed, float *dw, float *dbias, void *workspace, size_t workspace_bytes, void *stream);
 
 /* O[m][n] = sum_k A[m][k] * B[n][k], fp32, both operands with k contiguous (the conv stage's weight-gradient GEMM on its own; fixed summation order).  The
  * weight gradient of a 1 x 1 convolution is this product on the NCHW planes as they are: dW [Cout, Cin] = dY [Cout, H*W] . X [Cin, H*W]^T -- the bottlenecks'
