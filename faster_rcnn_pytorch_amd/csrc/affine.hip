@@ -4,7 +4,7 @@
 // 800 x 1344 training step.  One pass each way:
 //   affine_act_fwd_kernel   y = act((x * scale[c] + shift[c]) [+ res]),  act = ReLU or identity; the SAME operations in the SAME order as the torch
 //                           form (separate multiply and add, no contraction): bit-identical results
-//   affine_act_bwd_kernel   gm = g where y > 0 (ReLU) or g;  dx = gm * scale[c];  dres = gm (when the forward had a residual and a ReLU)
+//   affine_act_bwd_kernel   gm = 0 where y <= 0 (ReLU), else g (also at a NaN y, as torch);  dx = gm * scale[c];  dres = gm (when the forward had a residual and a ReLU)
 // x, y, res, g: [C][HW] fp32 planes (NCHW, batch 1); scale, shift: [C].  Pure HBM movers: thread = four elements 256 apart, grid (pieces, C).
 //
 // Mixed precision (round 5; BASELINE configs[4], bf16 autocast): the same two passes with bf16 on either side of the fp32 arithmetic
@@ -64,7 +64,7 @@ __global__ __launch_bounds__(256) void affine_act_bwd_kernel(const float *__rest
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int i = blockIdx.x * 1024 + j * 256 + threadIdx.x;
-        const float gm = m[j] > 0.0f ? v[j] : 0.0f;
+        const float gm = m[j] <= 0.0f ? 0.0f : v[j];                     // a NaN output passes its gradient, as torch's threshold_backward (y > 0 ? g : 0 would drop it)
         if (i < HW) {
             dx[base + i] = gm * s;
             if (DRES) dres[base + i] = gm;
@@ -128,7 +128,7 @@ __global__ __launch_bounds__(256) void affine_act_bwd_mixed_kernel(const GT *__r
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int i = blockIdx.x * 1024 + j * 256 + threadIdx.x;
-        const float gm = m[j] > 0.0f ? v[j] : 0.0f;
+        const float gm = m[j] <= 0.0f ? 0.0f : v[j];                     // NaN output: the gradient passes (see affine_act_bwd_kernel)
         if (i < HW) {
             af_st<DXT>(dx, base + i, gm * s);
             if (DRES) dres[base + i] = gm;

@@ -305,7 +305,8 @@ int frcnn_conv3x3_c3_wgrad(const float *x, const float *dy, int H, int W, int Co
 
 /* FrozenBatchNorm2d (+ residual add) (+ ReLU) of torchvision's ResNet bottleneck behind models/new_model.py:372, one pass each way (csrc/affine.hip):
  *   _fwd : y = act((x * scale[c] + shift[c]) [+ res]), the torch form's operations in its order (bit-identical); res may be NULL; act = ReLU when relu != 0.
- *   _bwd : gm = g where y > 0 (relu != 0; y = the forward's output) or g;  dx = gm * scale[c];  dres = gm (NULL: not wanted).
+ *   _bwd : gm = 0 where y <= 0, else g -- also at a NaN y, as torch's threshold_backward -- (relu != 0; y = the forward's output) or g;  dx = gm * scale[c];
+ *          dres = gm (NULL: not wanted).
  * x, y, res, g, dx, dres: [C, HW] fp32 (NCHW, batch 1); scale, shift: [C] (the frozen statistics folded as torchvision does). */
 int frcnn_affine_act_fwd(const float *x, const float *res, float *y, const float *scale, const float *shift, int C, int HW, int relu, void *stream);
 int frcnn_affine_act_bwd(const float *g, const float *y, const float *scale, float *dx, float *dres, int C, int HW, int relu, void *stream);
@@ -375,7 +376,8 @@ int frcnn_roi_pool_bwd(const float *grad_out, const int32_t *argmax, int64_t R, 
 int frcnn_roi_pool_fwd_a16(const float *feat, int C, int H, int W, const float *rois, int64_t R, float spatial_scale,
                            float *out /*[R,C,7,7]*/, uint16_t *argmax16 /*[R,C,7,7]*/, void *stream);
 /* `rois` / `spatial_scale`: the boxes the forward pooled (may be NULL).  With them the backward adds without LDS atomics for every RoI of at
- * least 7 x 7 feature cells; without them, and for smaller RoIs, with ds_add_f32.  Either way the result is bit-reproducible run to run. */
+ * least 7 x 7 feature cells; without them, and for smaller RoIs, with ds_add_f32.  For an even C the result is bit-reproducible run to run;
+ * an odd C takes the shared-plane kernel, whose LDS atomics add in arrival order (last-bit differences between runs). */
 int frcnn_roi_pool_bwd_a16(const float *grad_out, const uint16_t *argmax16, const float *rois /*[R,4] or NULL*/, float spatial_scale,
                            int64_t R, int C, int H, int W, float *grad_feat, void *stream);
 
