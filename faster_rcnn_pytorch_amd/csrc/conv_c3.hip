@@ -12,6 +12,7 @@
 //                            partials [block of rows][co][28] (one DPP reduction per wave and block; rows per block chosen per call);  conv3x3_c3_wgrad_finalize_kernel adds them in order (bit-reproducible).
 // The input gradient is never needed (the input is the image).
 #include "frcnn_common.h"
+#include "frcnn_dev.h"
 #include "frcnn_internal.h"
 #include "frcnn_layout.h"
 FRCNN_LAYOUT_STAMP(conv_c3);
@@ -76,20 +77,6 @@ __global__ __launch_bounds__(256) void conv3x3_c3_fwd_kernel(const float *__rest
             }
         }
     }
-}
-
-// sum over the wave's 64 lanes on DPP row shifts / broadcasts (plain VALU adds, no LDS crossbar), result in lane 63; fixed order
-__device__ __forceinline__ float c3_wave_sum(float v)
-{
-#define C3_DPP_ADD(ctrl, rmask) v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), ctrl, rmask, 0xf, false))
-    C3_DPP_ADD(0x111, 0xf);    // row_shr:1
-    C3_DPP_ADD(0x112, 0xf);    // row_shr:2
-    C3_DPP_ADD(0x114, 0xf);    // row_shr:4
-    C3_DPP_ADD(0x118, 0xf);    // row_shr:8   -> lane 15 of every row holds the row's sum
-    C3_DPP_ADD(0x142, 0xa);    // row_bcast:15 into rows 1 and 3
-    C3_DPP_ADD(0x143, 0xc);    // row_bcast:31 into rows 2 and 3 -> lane 63 holds the wave's sum
-#undef C3_DPP_ADD
-    return v;
 }
 
 #define C3_WAVES 8                     // waves per block: 32 output channels.  The image rows per block are chosen per call (frcnn_conv3x3_c3_wgrad) so that the launch is ONE round of
@@ -194,7 +181,7 @@ __global__ __launch_bounds__(64 * C3_WAVES) void conv3x3_c3_wgrad_kernel(const f
     for (int j = 0; j < C3_CPW; ++j)
 #pragma unroll
         for (int k = 0; k < 28; ++k) {
-            const float t = c3_wave_sum(acc[j][k >> 1][k & 1]);
+            const float t = wave_sum_dpp(acc[j][k >> 1][k & 1]);
             if (lane == 63) part[((size_t)blockIdx.x * Cout + co0 + j) * 28 + k] = t;
         }
 }

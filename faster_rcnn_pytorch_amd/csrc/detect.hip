@@ -15,6 +15,7 @@
 //  detect_emit_kernel   : one workgroup per class: its output offset (the sum of the counts of the classes before it) and the copy of
 //      its kept boxes / scores / labels; the last class writes the total (-1 when the proposal stage reported an aborted scan).
 #include "frcnn_common.h"
+#include "frcnn_dev.h"
 #include "frcnn_layout.h"
 #include "nms_dev.h"
 FRCNN_LAYOUT_STAMP(detect);
@@ -190,7 +191,7 @@ __global__ __launch_bounds__(DET_THREADS) void detect_emit_kernel(const float4 *
     if (tid < 64) {                                               // class-major concatenation (model.py:396-402): offset = earlier counts
         int a = 0;
         for (int i = tid; i < cls; i += 64) a += ws_cnt[i];
-        for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
+        a = wave_sum_xor(a);
         if (tid == 0) s_off = a;
     }
     __syncthreads();

@@ -25,6 +25,7 @@
 // The limits (EVAL_MAX_*, EVAL_THREADS, eval_supported), the error bits of a frame, eval_lower_bound and the (tp, fp) scan are those of
 // eval_dev.h, shared with coco_eval.hip.
 #include "frcnn_common.h"
+#include "frcnn_dev.h"
 #include "frcnn_layout.h"
 #include "eval_dev.h"
 FRCNN_LAYOUT_STAMP(eval);
@@ -133,7 +134,7 @@ __global__ __launch_bounds__(EVAL_THREADS) void eval_update_kernel(
     if (!s_last) return;
     __threadfence();
     if (tid == 0) {
-        __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);        // ready for the next call
+        agent_st(ticket, 0);        // ready for the next call
         s_base = n > 0 ? atomicAdd(cursor, (u64)n) : 0ull;                                // a full store keeps counting: summarize() reports the loss
     }
     __syncthreads();
@@ -141,8 +142,8 @@ __global__ __launch_bounds__(EVAL_THREADS) void eval_update_kernel(
     const u64 base = s_base;
     const int image_id = frame[2];
     for (int i = tid; i < n; i += EVAL_THREADS) {
-        const int match = __hip_atomic_load(&ws_match[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const uint32_t reach = __hip_atomic_load(&ws_reach[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int match = agent_ld(&ws_match[i]);
+        const uint32_t reach = agent_ld(&ws_reach[i]);
         const float sc = scores[i];
         const u64 bid = ((u64)eval_orderable(sc) << 32) | (uint32_t)~(uint32_t)i;
         const bool difficult = match >= 0 && gt_difficult[match];
@@ -151,7 +152,7 @@ __global__ __launch_bounds__(EVAL_THREADS) void eval_update_kernel(
             uint32_t f = FRCNN_EVAL_FP;                                                   // below the threshold, or no same-class ground truth
             if (reach >> t & 1u) {
                 if (difficult) f = FRCNN_EVAL_IGNORED;
-                else if (__hip_atomic_load(&win[(size_t)t * G + match], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == bid) f = FRCNN_EVAL_TP;
+                else if (agent_ld(&win[(size_t)t * G + match]) == bid) f = FRCNN_EVAL_TP;
             }
             flags |= f << (2 * t);
         }

@@ -4,6 +4,7 @@
 // block-wide scan of the packed (tp, fp) counts.  A change to the error word, the limits or the scan is made here, once.
 #pragma once
 #include "frcnn_common.h"
+#include "frcnn_dev.h"
 
 // device error word (evaluation.py reports them)
 #define EVAL_ERR_UPSTREAM_ABORT 1      // count < 0: an aborted proposal scan upstream
@@ -65,11 +66,7 @@ __device__ __forceinline__ long long eval_lower_bound(const int32_t *__restrict_
 __device__ __forceinline__ u64 eval_scan_step(uint32_t code, u64 *s_wave, const u64 *s_carry)
 {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    u64 v = code == FRCNN_EVAL_TP ? 1ull : (code == FRCNN_EVAL_FP ? 1ull << 32 : 0ull);
-    for (int o = 1; o < 64; o <<= 1) {
-        const u64 u = __shfl_up(v, o);
-        if (lane >= o) v += u;
-    }
+    const u64 v = wave_incl_scan(code == FRCNN_EVAL_TP ? 1ull : (code == FRCNN_EVAL_FP ? 1ull << 32 : 0ull));
     if (lane == 63) s_wave[wv] = v;
     __syncthreads();
     u64 pre = *s_carry;

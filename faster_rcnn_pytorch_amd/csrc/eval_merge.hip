@@ -27,6 +27,7 @@
 //      Records of kept occurrences land in (shard, slot) order, all five columns bit for bit.  Row ranges are read from device memory and
 //      clipped to the shard's live records before they index anything.
 #include "frcnn_common.h"
+#include "frcnn_dev.h"
 #include "frcnn_layout.h"
 #include "eval_dev.h"
 FRCNN_LAYOUT_STAMP(eval_merge);
@@ -156,10 +157,7 @@ __device__ __forceinline__ void merge_range(const long long *__restrict__ rng, l
 __device__ __forceinline__ u64 merge_block_scan(u64 v, u64 *s_wave, u64 *total)
 {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    for (int o = 1; o < 64; o <<= 1) {
-        const u64 u = __shfl_up(v, o);
-        if (lane >= o) v += u;
-    }
+    v = wave_incl_scan(v);
     __syncthreads();                                            // s_wave of an earlier scan has been read
     if (lane == 63) s_wave[wv] = v;
     __syncthreads();
@@ -190,7 +188,7 @@ __global__ __launch_bounds__(MERGE_THREADS) void merge_insert_kernel(MergeSrc s,
     const u64 mask = (u64)TS - 1;
     u64 h = (u64)id & mask;
     for (long long probe = 0; probe < TS; ++probe) {            // the table is at most half full: an empty or the id's own slot is met
-        u64 cur = __hip_atomic_load(&table[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        u64 cur = agent_ld(&table[h]);
         if (cur == MERGE_EMPTY) {
             cur = atomicCAS(&table[h], MERGE_EMPTY, key);
             if (cur == MERGE_EMPTY) return;                     // claimed

@@ -15,6 +15,7 @@
 // Loads: 16-byte when the chunk's GRADIENT pointer is 16-byte aligned (decided from g alone -- SgdRow.vec also covers p and m), dword
 // loads otherwise, with the same element-to-thread assignment.  Default cache policy: the update reads the same bytes next.
 #include "frcnn_common.h"
+#include "frcnn_dev.h"
 #include "frcnn_internal.h"
 #include "frcnn_layout.h"
 #include "sgd_dev.h"
@@ -29,13 +30,6 @@ __device__ __forceinline__ void gn_take(float x, double &acc, int &bad)
     const double d = (double)x;
     acc = __fma_rn(d, d, acc);
     bad += ((__float_as_uint(x) >> 23) & 0xffu) == 0xffu;
-}
-
-__device__ __forceinline__ double gn_wave_sum(double v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = __dadd_rn(v, __shfl_xor(v, d, WAVE));
-    return v;
 }
 
 __global__ __launch_bounds__(SGD_THREADS) void grad_norm_partial_kernel(const SgdRow *__restrict__ rows, const int2 *__restrict__ map, int n_tensors,
@@ -98,7 +92,7 @@ __global__ __launch_bounds__(SGD_THREADS) void grad_norm_partial_kernel(const Sg
     }
     if (tid == (n4 & (SGD_THREADS - 1)))                                    // the n % 4 elements of the last, partial group of four: its owner's last
         for (int e = 0; e < (n & 3); ++e) gn_take(g[4 * n4 + e], a[e], bad);
-    double s = gn_wave_sum(__dadd_rn(__dadd_rn(a[0], a[1]), __dadd_rn(a[2], a[3])));
+    double s = wave_sum_xor(__dadd_rn(__dadd_rn(a[0], a[1]), __dadd_rn(a[2], a[3])));
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) bad += __shfl_xor(bad, d, WAVE);
     __shared__ double ws[SGD_THREADS / WAVE];
@@ -124,7 +118,7 @@ __global__ __launch_bounds__(GN_FINISH_THREADS) void grad_norm_finish_kernel(con
         s = __dadd_rn(s, partial[i]);
         bad += bad_in[i];
     }
-    s = gn_wave_sum(s);
+    s = wave_sum_xor(s);
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) bad += __shfl_xor(bad, d, WAVE);
     __shared__ double ws[GN_FINISH_THREADS / WAVE];

@@ -8,31 +8,18 @@
 // many per backward.  Here one pass over the predictions produces the four sums AND the un-normalised gradients
 // (softmax - onehot, SmoothL1'), so backward is four scalar multiplies.  RPN rows: one lane per anchor, grid-stride over at
 // most 256 workgroups; head rows: one WAVE per RoI (lanes over the classes, coalesced row reads, shuffle max / sum).  Every
-// workgroup writes its partial sums to its own slot; the workgroup that finishes LAST (an agent-scope ticket, acq_rel) adds the slots in
+// workgroup writes its partial sums to its own slot; the workgroup that finishes LAST (an agent-scope ticket, relaxed: frcnn_dev.h) adds the slots in
 // index order: no float atomics (1051 same-line atomics x 5 cost 50 us at FPN size), a loss that is bit-reproducible run to run, and no
 // second launch (round 2 ran the sum as its own one-wave kernel: a launch at the ~5 us floor for 2 KB of data).  The ticket word is the
 // first int32 of the workspace: it must be ZERO before the first call and the last workgroup leaves it zero (frcnn_hip.h).
 #include "frcnn_common.h"
+#include "frcnn_dev.h"
 #include "frcnn_internal.h"
 #include "frcnn_layout.h"
 FRCNN_LAYOUT_STAMP(loss);
 
 struct LossAcc { float rpn_ce, rpn_sl1, head_ce, head_sl1; int rpn_valid; int pad[3]; };      // one 32-byte slot per workgroup
 #define LOSS_MAX_BLOCKS 256                                                                    // per part (RPN rows, head rows)
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-__device__ __forceinline__ float wave_max(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
 
 __device__ __forceinline__ float sl1(float p, float t, float beta, float *grad)
 {
@@ -86,10 +73,10 @@ __global__ __launch_bounds__(256) void det_loss_kernel(const float2 *__restrict_
             const int t = (t64 >= 0 && t64 < NC) ? (int)t64 : -1;
             float m = -__builtin_inff();
             for (int c = lane; c < NC; c += 64) m = fmaxf(m, row[c]);
-            m = wave_max(m);
+            m = wave_max_xor(m);
             float s = 0.f;
             for (int c = lane; c < NC; c += 64) s += expf(row[c] - m);
-            s = wave_sum(s);
+            s = wave_sum_xor(s);
             float *g = g_head_cls + (size_t)r * NC;
             for (int c = lane; c < NC; c += 64) g[c] = expf(row[c] - m) / s - (c == t ? 1.f : 0.f);
             if (lane == 0) {
@@ -105,40 +92,36 @@ __global__ __launch_bounds__(256) void det_loss_kernel(const float2 *__restrict_
             }
         }
     }
-    ce = wave_sum(ce); sl = wave_sum(sl); hce = wave_sum(hce); hsl = wave_sum(hsl);
-    int vc = valid;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) vc += __shfl_xor(vc, o);
+    ce = wave_sum_xor(ce); sl = wave_sum_xor(sl); hce = wave_sum_xor(hce); hsl = wave_sum_xor(hsl);
+    const int vc = wave_sum_xor(valid);
     if (lane == 0) { s_part[w][0] = ce; s_part[w][1] = sl; s_part[w][2] = hce; s_part[w][3] = hsl; s_cnt[w] = vc; }
     __syncthreads();
     // my slot: write-through stores (the adder may sit on another XCD), then the ticket
     if (threadIdx.x < 4)
-        __hip_atomic_store(&(&slots[blockIdx.x].rpn_ce)[threadIdx.x], s_part[0][threadIdx.x] + s_part[1][threadIdx.x] + s_part[2][threadIdx.x] + s_part[3][threadIdx.x],
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (threadIdx.x == 4) __hip_atomic_store(&slots[blockIdx.x].rpn_valid, s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    // the slot is written through and read with agent-scope loads: an acknowledged store behind the ticket is all the hand-off needs (an
-    // acq_rel ticket writes this XCD's dirty gradient lines back and invalidates its L2 in EVERY workgroup: 20.0 -> 16.6 us at FPN size, HIP events)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        agent_st(&(&slots[blockIdx.x].rpn_ce)[threadIdx.x], s_part[0][threadIdx.x] + s_part[1][threadIdx.x] + s_part[2][threadIdx.x] + s_part[3][threadIdx.x]);
+    if (threadIdx.x == 4) agent_st(&slots[blockIdx.x].rpn_valid, s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3]);
+    // the slot is written through and read with agent-scope loads: the relaxed hand-off of frcnn_dev.h (last_arriver, which says why the
+    // ticket carries no order), written out
+    vm_wait<0>();
     __syncthreads();
-    if (threadIdx.x == 0) s_last = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1;
+    if (threadIdx.x == 0) s_last = agent_add(ticket, 1) == (int)gridDim.x - 1;
     __syncthreads();
     if (!s_last || threadIdx.x >= 64) return;
     // ---- the last workgroup: out[0..4] = total, rpn_cls, rpn_reg, head_cls, head_reg ; out[5] = 1/n_valid, out[6] = 1/R (gradient scales)
-    if (threadIdx.x == 0) __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // ready for the next call
+    if (threadIdx.x == 0) ticket_reset(ticket);      // ready for the next call
     const int n_slots = (int)gridDim.x;
     float a[4] = {0.f, 0.f, 0.f, 0.f};
     int nvi = 0;
     for (int b = threadIdx.x; b < n_slots; b += 64) {                  // fixed assignment + fixed shuffle tree: deterministic
-        a[0] += __hip_atomic_load(&slots[b].rpn_ce, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        a[1] += __hip_atomic_load(&slots[b].rpn_sl1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        a[2] += __hip_atomic_load(&slots[b].head_ce, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        a[3] += __hip_atomic_load(&slots[b].head_sl1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        nvi += __hip_atomic_load(&slots[b].rpn_valid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        a[0] += agent_ld(&slots[b].rpn_ce);
+        a[1] += agent_ld(&slots[b].rpn_sl1);
+        a[2] += agent_ld(&slots[b].head_ce);
+        a[3] += agent_ld(&slots[b].head_sl1);
+        nvi += agent_ld(&slots[b].rpn_valid);
     }
 #pragma unroll
-    for (int q = 0; q < 4; ++q) a[q] = wave_sum(a[q]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) nvi += __shfl_xor(nvi, o);
+    for (int q = 0; q < 4; ++q) a[q] = wave_sum_xor(a[q]);
+    nvi = wave_sum_xor(nvi);
     if (threadIdx.x != 0) return;
     const float nv = (float)nvi, fr = (float)R;
     const float l1 = a[0] / nv, l2 = a[1] / nv, l3 = a[2] / fr, l4 = a[3] / fr;

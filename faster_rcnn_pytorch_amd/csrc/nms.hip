@@ -34,6 +34,7 @@
 //      (cascade and generic layout; a dense single level writes them itself).
 // K <= NMS_CASCADE_MIN boxes (both proposal stages, predict's per-image lists) run one level directly.
 #include "frcnn_common.h"
+#include "frcnn_dev.h"
 #include "frcnn_internal.h"
 #include "frcnn_layout.h"
 #include "nms_dev.h"
@@ -157,9 +158,6 @@ __device__ __forceinline__ unsigned sup_half_pos(float4 a, float ta, const float
     return word;
 }
 
-__device__ __forceinline__ u64 agent_ld64(const u64 *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void agent_or64(u64 *p, u64 v) { (void)__hip_atomic_fetch_or(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void agent_st64(u64 *p, u64 v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // One wave = one 64 x 64 tile (cb = my block, the lower-scored side; rb <= cb = suppressor block, staged in LDS).  The words are
 // published for the resolver workgroups that run in the SAME launch on other CUs (see nms_kernel): write-through (sc1) stores (and
@@ -216,15 +214,15 @@ __device__ __forceinline__ void nms_sup_tile(int cb, int rb, int wave, int lane,
     const int tile = cb * (cb + 1) / 2 + rb;
     int flag = 1;
     if (dense) {                                                // one coalesced 512 B store per non-empty tile (see nms_resolve_block_dense)
-        if (__ballot(bits != 0ull) != 0ull) { agent_st64(&sup[(size_t)tile * 64 + lane], bits); flag = 2; }
+        if (__ballot(bits != 0ull) != 0ull) { agent_st(&sup[(size_t)tile * 64 + lane], bits); flag = 2; }
     } else if (bits != 0ull) {                                  // me < n <= K is implied by a set bit
-        agent_st64(&sup[(size_t)me * nblk + rb], bits);
-        agent_or64(&nz[(size_t)(rb >> 6) * K + me], 1ull << (rb & 63));   // group-major: the resolver reads it coalesced
+        agent_st(&sup[(size_t)me * nblk + rb], bits);
+        agent_or(&nz[(size_t)(rb >> 6) * K + me], 1ull << (rb & 63));   // group-major: the resolver reads it coalesced
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // my stores and ORs have reached the coherence point ...
+    vm_wait<0>();            // my stores and ORs have reached the coherence point ...
     // ... before my tile's flag goes up.  One flag WORD per tile, a plain write-through store: a shared per-row counter (cb + 1
     // agent-scope adds to one address) doubled the kernel's time, 43 -> 83 us.
-    if (lane == 0) __hip_atomic_store(&done[tile], flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (lane == 0) agent_st(&done[tile], flag);
 #ifdef NMS_TRACE
     if (lane == 0) atomicMax(&g_nms_trace[4096 + cb][1], (u64)__builtin_amdgcn_s_memrealtime());
 #endif
@@ -259,13 +257,13 @@ __device__ __forceinline__ void nms_resolve_wave(int wg, int n, int K, int nblk,
         int spins = 0;
         for (;;) {
             bool up = true;
-            for (int k = lane; k <= b; k += 64) up = up && __hip_atomic_load(&fl[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
+            for (int k = lane; k <= b; k += 64) up = up && agent_ld(&fl[k]) != 0;
             if (__ballot(!up) == 0ull) break;
             __builtin_amdgcn_s_sleep(8);
             if (++spins > NMS_ROW_WAIT_SPINS) { if (lane == 0) atomicOr(abort_flag, 1); return; }
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");          // nothing older than the counter value is served to the loads below
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        vm_wait<0>();
     }
     // which 64-word groups of my bitmap are non-empty; cur = the unvisited words of the current group
     u64 later = 0ull;                                              // one bit per 64-word group: nzw <= NMS_MAX_BLOCKS / 64 = 64 groups
@@ -273,7 +271,7 @@ __device__ __forceinline__ void nms_resolve_wave(int wg, int n, int K, int nblk,
     int g = 0;
     if (live) {
         for (int q = nzw - 1; q >= 0; --q) {
-            const u64 a = agent_ld64(&nz[(size_t)q * K + i]);
+            const u64 a = agent_ld(&nz[(size_t)q * K + i]);
             if (a != 0ull) { later |= 1ull << q; cur = a; g = q; }
         }
         later &= later - 1ull;                                      // the lowest non-empty group is the current one
@@ -289,13 +287,13 @@ __device__ __forceinline__ void nms_resolve_wave(int wg, int n, int K, int nblk,
     for (int it = 0;; ++it) {
         // publish this iteration's decisions: one agent-scope atomic per wave and bitmap
         const u64 km = __ballot(k_new), rm = __ballot(r_new);
-        if (lane == 0) { if (km) agent_or64(&kept[b], km); if (rm) agent_or64(&rem[b], rm); }
+        if (lane == 0) { if (km) agent_or(&kept[b], km); if (rm) agent_or(&rem[b], rm); }
         k_new = r_new = false;
         if (__ballot(!decided) == 0ull) break;
         bool progressed = (km | rm) != 0ull;
         if (!decided) {
             if (w >= 0) {                                           // poll my current word
-                const u64 kw = agent_ld64(&kept[w]), rw = agent_ld64(&rem[w]);
+                const u64 kw = agent_ld(&kept[w]), rw = agent_ld(&rem[w]);
                 if ((S & kw) != 0ull) { r_new = true; decided = true; }
                 else if ((S & ~rw) == 0ull) w = -1;                 // exhausted: walk on below
             }
@@ -303,7 +301,7 @@ __device__ __forceinline__ void nms_resolve_wave(int wg, int n, int K, int nblk,
                 if (cur == 0ull && later != 0ull) {                 // next non-empty group
                     g = __builtin_ctzll(later);
                     later &= later - 1ull;
-                    cur = agent_ld64(&nz[(size_t)g * K + i]);
+                    cur = agent_ld(&nz[(size_t)g * K + i]);
                 }
                 if (cur == 0ull) { k_new = true; decided = true; }  // every suppressor is removed
                 else {
@@ -316,7 +314,7 @@ __device__ __forceinline__ void nms_resolve_wave(int wg, int n, int K, int nblk,
                         wi[t] = take ? (g << 6) + __builtin_ctzll(cc) : -1;
                         if (take) cc &= cc - 1ull;
                         sv[t] = 0ull; kv[t] = 0ull; rv[t] = 0ull;
-                        if (take) { sv[t] = agent_ld64(&row[wi[t]]); kv[t] = agent_ld64(&kept[wi[t]]); rv[t] = agent_ld64(&rem[wi[t]]); }
+                        if (take) { sv[t] = agent_ld(&row[wi[t]]); kv[t] = agent_ld(&kept[wi[t]]); rv[t] = agent_ld(&rem[wi[t]]); }
                     }
                     bool settled = false;
                     // a kept suppressor ANYWHERE in the batch removes me, also behind a word that still has an undecided one
@@ -398,26 +396,26 @@ __device__ __forceinline__ void nms_resolve_block_dense(int b, int n, int nblk, 
         const bool mine = my_rb < b;
         int spins = 0, f;
         for (;;) {
-            f = __hip_atomic_load(&fl[mine ? my_rb : b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            f = agent_ld(&fl[mine ? my_rb : b]);
             if (__ballot(f == 0) == 0ull) break;
             __builtin_amdgcn_s_sleep(2);
             if (++spins > NMS_ROW_WAIT_SPINS) { if (lane == 0) atomicOr(abort_flag, 1); break; }   // the sweep loop sees the flag and ends
         }
         // (no acquire fence: every word read below was written through and is read with an agent-scope load; the fence's cache
         // invalidate would also throw out the box lines the tile waves of this XCD keep re-reading)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        vm_wait<0>();
         act = __ballot(mine && f == 2);
-        fd = __hip_atomic_load(&fl[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        fd = agent_ld(&fl[b]);
     }
     NMS_T(b * 4 + v, 1);
-    const u64 wdiag = fd == 2 ? agent_ld64(rowp + (size_t)b * 64) : 0ull;
+    const u64 wdiag = fd == 2 ? agent_ld(rowp + (size_t)b * 64) : 0ull;
     u64 dec = ~live_m, acc_k = 0ull, acc_r = 0ull;
     const int max_iter = 4 * n + 65536;
     for (int it = 0;; ++it) {
         NMS_TSWEEP(b, it);
         const int tc = min((int)threadIdx.x, nblk - 1);
-        const u64 sk = agent_ld64(&kept[tc]), sr = agent_ld64(&rem[tc]);
-        const int ab = threadIdx.x == 0 ? __hip_atomic_load(abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
+        const u64 sk = agent_ld(&kept[tc]), sr = agent_ld(&rem[tc]);
+        const int ab = threadIdx.x == 0 ? agent_ld(abort_flag) : 0;
         u64 hit = 0ull, und = 0ull, rest = act;
         bool first = true;
         do {
@@ -427,7 +425,7 @@ __device__ __forceinline__ void nms_resolve_block_dense(int b, int n, int nblk, 
             for (int t = 0; t < NMS_DENSE_BATCH; ++t) {
                 rbs[t] = rest != 0ull ? 4 * (int)__builtin_ctzll(rest) + v : -1;
                 rest &= rest - 1ull;                                // 0 stays 0
-                w[t] = agent_ld64(rowp + (size_t)max(rbs[t], 0) * 64);
+                w[t] = agent_ld(rowp + (size_t)max(rbs[t], 0) * 64);
             }
             if (first) {
                 L->stk[tc] = sk; L->str[tc] = sr;
@@ -458,7 +456,7 @@ __device__ __forceinline__ void nms_resolve_block_dense(int b, int n, int nblk, 
             if ((nr | nk) == 0ull) break;
             acc_k |= nk; acc_r |= nr; dec |= nk | nr;
         }
-        if (threadIdx.x == 0 && dec != dec0) { agent_st64(&kept[b], acc_k); agent_st64(&rem[b], acc_r); }
+        if (threadIdx.x == 0 && dec != dec0) { agent_st(&kept[b], acc_k); agent_st(&rem[b], acc_r); }
         if (dec == ~0ull) { NMS_T(b * 4 + v, 3); NMS_TV(b * 4 + v, 4, it + 1); break; }
         if (aborted) break;
         if (dec == dec0) __builtin_amdgcn_s_sleep(1);
@@ -472,8 +470,8 @@ __device__ __forceinline__ void nms_resolve_block_dense(int b, int n, int nblk, 
     // with sc1 loads.
     __syncthreads();
     if (threadIdx.x == 0) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        L->abort = __hip_atomic_fetch_add(ea.ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        vm_wait<0>();
+        L->abort = agent_add(ea.ticket, 1);
     }
     __syncthreads();
     const int nb = (n + 63) >> 6;
@@ -481,15 +479,12 @@ __device__ __forceinline__ void nms_resolve_block_dense(int b, int n, int nblk, 
     NMS_T(8100, 0);
     __syncthreads();
     const int tc = min((int)threadIdx.x, nb - 1);
-    u64 kw = agent_ld64(&kept[tc]);
+    u64 kw = agent_ld(&kept[tc]);
     if ((int)threadIdx.x >= nb) kw = 0ull;
     if ((int)threadIdx.x == nb - 1 && (n & 63)) kw &= (1ull << (n & 63)) - 1ull;
-    const bool aborted = __hip_atomic_load(abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
+    const bool aborted = agent_ld(abort_flag) != 0;
     // exclusive scan of the blocks' kept counts over the 256 threads
-    int inc = __builtin_popcountll(kw);
-    const int own = inc;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(inc, o); if (lane >= o) inc += u; }
+    const int own = __builtin_popcountll(kw), inc = wave_incl_scan(own);
     int *s_w = (int *)L->hitm;
     if (lane == 63) s_w[v] = inc;
     __syncthreads();
@@ -541,7 +536,7 @@ __device__ __forceinline__ void nms_resolve_block_dense(int b, int n, int nblk, 
         }
     }
 #ifdef NMS_TRACE
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    vm_wait<0>();
 #endif
     NMS_T(8100, 3);
 }
@@ -628,10 +623,7 @@ __global__ __launch_bounds__(64 * NMS_FILTER_WAVES) void nms_filter_kernel(const
     const int nw0 = (n0 + 63) >> 6;
     if (tid < 64) {
         const u64 w = tid < nw0 ? kept0[tid] : 0ull;
-        int inc = __builtin_popcountll(w);
-        const int mine = inc;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(inc, o); if (lane >= o) inc += u; }
+        const int mine = __builtin_popcountll(w), inc = wave_incl_scan(mine);
         if (tid < NMS_T_MAX / 64) { s_kw[tid] = w; s_pref[tid] = inc - mine; }
         if (tid == NMS_T_MAX / 64 - 1) s_pref[NMS_T_MAX / 64] = inc;
     }
@@ -715,12 +707,12 @@ __global__ __launch_bounds__(64 * NMS_FILTER_WAVES) void nms_filter_kernel(const
     for (int q = 0; q < NW; ++q) sup_any |= s_any[q];
     const u64 alive = live_mask & ~sup_any;
     const int cnt = __builtin_popcountll(alive);
-    if (lane == 0) __hip_atomic_store(&look[b], (cnt << 1) | 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (lane == 0) agent_st(&look[b], (cnt << 1) | 1);
     // look back over the earlier blocks (<= NMS_MAX_BLOCKS of them: a few per lane)
     int base = 0;
     for (int k = lane; k < b; k += 64) {
         int v, spins = 0;
-        while (((v = __hip_atomic_load(&look[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) & 1) == 0) {
+        while (((v = __hip_atomic_load(&look[k], FRCNN_RLX_AGENT)) & 1) == 0) {      // (written out: see FRCNN_RLX_AGENT)
             __builtin_amdgcn_s_sleep(2);
             if (++spins > NMS_LOOK_SPINS) { atomicOr(&ctl[0], 1); v = 1; break; }
         }
@@ -758,8 +750,7 @@ __global__ __launch_bounds__(256) void nms_emit_kernel(const float4 *__restrict_
     if (b > nb) return;                                              // wave nb only writes the count
     int part = 0;
     for (int w = lane; w < min(b, nb); w += 64) part += __builtin_popcountll(w < nb0 ? kept0[w] : kept1[w - nb0]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
+    part = wave_sum_xor(part);
     if (b == nb) {
         if (lane == 0) *out_count = aborted ? -1 : (part < post_k ? part : post_k);
         return;

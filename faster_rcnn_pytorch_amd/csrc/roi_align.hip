@@ -19,6 +19,7 @@
 // Any other bin/sampling shape takes the generic one-lane-per-output kernels below (memset + fp32 atomics in backward;
 // order-nondeterministic, tolerance 1e-4).
 #include "frcnn_common.h"
+#include "frcnn_dev.h"
 #include "frcnn_internal.h"
 #include "frcnn_layout.h"
 FRCNN_LAYOUT_STAMP(roi_align);
@@ -507,14 +508,14 @@ __global__ __launch_bounds__(256) void roi_align_bwd_lists_kernel(MsLevels L, Ti
     }
     if (t < n_cg) tix[tile * n_cg + t] = 0;                // the tile kernel's last-segment tickets of this tile (consumed by the NEXT launch)
     if (t == 0) {
-        __hip_atomic_store(&cnt[tile], base, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);       // written through: the planning workgroup reads it in THIS launch
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                         // ... and acknowledged before the ticket announces it
-        s_last = (__hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == tiles - 1) ? 1 : 0;
+        agent_st(&cnt[tile], base);       // written through: the planning workgroup reads it in THIS launch
+        vm_wait<0>();                                         // ... and acknowledged before the ticket announces it
+        s_last = (agent_add(ticket, 1) == tiles - 1) ? 1 : 0;
     }
     __syncthreads();
     if (!s_last) return;
     // the last lists workgroup: every list length is in memory; leave the ticket zero for the next launch and plan
-    if (t == 0) __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (t == 0) ticket_reset(ticket);
     ra_plan_block(tiles, cap_items, cnt, tbase, tnseg, items, slot);
 }
 
@@ -528,7 +529,6 @@ __global__ __launch_bounds__(256) void roi_align_bwd_lists_kernel(MsLevels L, Ti
 // fresh RPN whose long lists sit on the fine level, at the END of the tile order).  slot[item number] = record position, which
 // is also where a segment's partial tile goes (the combine kernel looks it up); unused records carry tile = -1.
 __device__ __forceinline__ int ra_items(int n, int split) { return n == 0 ? 0 : ra_nseg(n, split); }
-__device__ __forceinline__ int ra_cnt(const int32_t *cnt, int q) { return __hip_atomic_load(&cnt[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }   // written by other workgroups of this launch
 // (Round 5: no launch of its own any more -- the lists workgroup that finishes LAST runs it, 256 threads, reading the list lengths the others wrote
 // through with agent-scope loads.)
 __device__ void ra_plan_block(int tiles, int cap_items, const int32_t *__restrict__ cnt, int32_t *__restrict__ tbase, int32_t *__restrict__ tnseg,
@@ -547,12 +547,12 @@ __device__ void ra_plan_block(int tiles, int cap_items, const int32_t *__restric
     constexpr int PC = 4;
     int cn[PC];
 #pragma unroll
-    for (int k = 0; k < PC; ++k) cn[k] = q0 + k < q1 ? ra_cnt(cnt, q0 + k) : 0;
+    for (int k = 0; k < PC; ++k) cn[k] = q0 + k < q1 ? agent_ld(&cnt[q0 + k]) : 0;
     auto each_tile = [&](auto &&f) {
 #pragma unroll
         for (int k = 0; k < PC; ++k)
             if (q0 + k < q1) f(q0 + k, cn[k]);
-        for (int q = q0 + PC; q < q1; ++q) f(q, ra_cnt(cnt, q));
+        for (int q = q0 + PC; q < q1; ++q) f(q, agent_ld(&cnt[q]));
     };
     // segment sgm of ns over a list of n: entries [n sgm / ns, n (sgm + 1) / ns)  (n <= R < 2^27 -- the launcher checks -- and sgm + 1 <= ns <= RS_NSEG = 32: the products fit 32 bits)
     auto cut = [](int n, int sgm, int ns) { return (int)((unsigned)n * (unsigned)sgm / (unsigned)ns); };
@@ -580,10 +580,7 @@ __device__ void ra_plan_block(int tiles, int cap_items, const int32_t *__restric
     __syncthreads();
     if (wave == 0) {                                       // exclusive scan of the 64 buckets by one wave
         const int v = s_hist[lane];
-        int in = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(in, o); if (lane >= o) in += u; }
-        s_hist[lane] = in - v;
+        s_hist[lane] = wave_incl_scan(v) - v;
     }
     __syncthreads();
     int base = base0;
@@ -609,21 +606,7 @@ __device__ int g_ra_plan_ticket[64];
 #define RF_CH 4                          // channels per fill workgroup
 struct FillLevels { int fill0[FRCNN_MAX_LEVELS + 1]; };   // first fill workgroup of level l: (row blocks of l) x (C / RF_CH) each
 
-// 16 bytes per lane, global -> LDS at lds + lane * 16, as INLINE ASSEMBLY: behind the builtin the compiler tracks the transfer and puts
-// s_waitcnt vmcnt(0) in front of the next LDS read that might alias it (every read of the other ring buffers) and into __syncthreads() --
-// each RoI step then paid the full L2 round trip (1 us a step with no arithmetic at all).  The waits are counted by hand (ra_vm_wait).
-__device__ __forceinline__ void ra_dma16(const float *g, const float *lds)
-{
-    const unsigned l = (unsigned)(size_t)(const __attribute__((address_space(3))) float *)lds;
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(__builtin_amdgcn_readfirstlane(l)), "v"(g) : "memory");   // (m0 is a reserved register the compiler sets right in front of the few instructions that read it; no other one here does)
-}
-template <int N> __device__ __forceinline__ void ra_vm_wait() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-__device__ __forceinline__ void ra_barrier()               // workgroup barrier that leaves the LDS-DMA in flight
-{
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
+// The feature tiles and weight records arrive by LDS-DMA (dma16_to_lds, frcnn_dev.h); the waits are counted by hand (vm_wait, barrier_keep_vm_pinned).
 #ifdef RT_TRACE      // developer build (tools/dev/ra_trace.py): per workgroup {start, first barrier, end, steps, XCC/CU id, kind} in 10 ns ticks
 __device__ unsigned long long g_rt_trace[32768][6];
 extern "C" __attribute__((visibility("default"))) void frcnn_ra_trace_read(void *dst) { hipDeviceSynchronize(); hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_rt_trace), sizeof(g_rt_trace)); }
@@ -711,15 +694,15 @@ __global__ __launch_bounds__(256) RT_ATTR void roi_align_bwd_tile_kernel(MsLevel
     const int wv4 = __builtin_amdgcn_readfirstlane(t >> 6), ln = t & 63;
     auto stage_dma = [&](int r, int buf) {
         const float *src = grad_out + ((size_t)r * C + c0) * 49 + ln * 4;
-        ra_dma16(src + wv4 * 256, &s_g[buf][wv4 * 256]);
-        if (wv4 < 2) ra_dma16(src + (wv4 + 4) * 256, &s_g[buf][(wv4 + 4) * 256]);
-        if (wv4 == 2 && ln < 8) ra_dma16(src + 6 * 256, &s_g[buf][6 * 256]);
+        dma16_to_lds(src + wv4 * 256, &s_g[buf][wv4 * 256]);
+        if (wv4 < 2) dma16_to_lds(src + (wv4 + 4) * 256, &s_g[buf][(wv4 + 4) * 256]);
+        if (wv4 == 2 && ln < 8) dma16_to_lds(src + 6 * 256, &s_g[buf][6 * 256]);
     };
     // wave 3 brings the RoI's weight-table record: one global_load_lds_dwordx4 from the pool, or built here when the RoI has none
     auto stage_rec = [&](const RoiEnt &e, int buf) {
         if (wv4 != 3) return;
         const int rec = __builtin_amdgcn_readfirstlane(e.rec);
-        if (rec >= 0) ra_dma16(pool + (size_t)rec * RA_REC + ln * 4, &s_rec[buf][0]);
+        if (rec >= 0) dma16_to_lds(pool + (size_t)rec * RA_REC + ln * 4, &s_rec[buf][0]);
         else
             ra_tables_wave(H, W, ty0, tx0, e.sh, e.sw, e.bh, e.bw, &s_rec[buf][0]);
     };
@@ -758,11 +741,11 @@ __global__ __launch_bounds__(256) RT_ATTR void roi_align_bwd_tile_kernel(MsLevel
             // and the record -- one if that RoI's tables are built here).  The register path waits for everything.
             {
                 const int later = RT_RING == 2 || !dma || i + 1 >= m ? 0 : wv4 != 3 ? 2 : 1 + (__builtin_amdgcn_readfirstlane(s_list[min(i + 1, m - 1)].rec) >= 0 ? 1 : 0);
-                if (later == 2) ra_vm_wait<2>();
-                else if (later == 1) ra_vm_wait<1>();
-                else ra_vm_wait<0>();
+                if (later == 2) vm_wait<2>();
+                else if (later == 1) vm_wait<1>();
+                else vm_wait<0>();
             }
-            ra_barrier();
+            barrier_keep_vm_pinned();
 #ifdef RT_TRACE
             if (cb == lo && i == 0) RT_T(1);
 #endif
@@ -798,7 +781,7 @@ __global__ __launch_bounds__(256) RT_ATTR void roi_align_bwd_tile_kernel(MsLevel
                 for (int q = 0; q < 4; ++q)
                     if (q < 3 || hs == 0) tp[q * 8] = T[q];
             }
-            ra_barrier();
+            barrier_keep_vm_pinned();
             // B2: lane (column, rows 4 rg .. 4 rg + 3 with rg = my wave, channel pairs cq and cq + 8): acc[row][pair] += sum over the bin rows
             // that reach ANY of my four rows of Wy[row][bin] * T[pair][bin][column].  Four adjacent rows hear from three bins where
             // each alone hears from two: 3 x 16 bytes of T per lane where one row per lane read 2 x 64.  The bin range is the wave's
@@ -847,8 +830,8 @@ __global__ __launch_bounds__(256) RT_ATTR void roi_align_bwd_tile_kernel(MsLevel
                          "s_waitcnt vmcnt(0)"
                          :: "v"(dst), "v"(dst + 1024), "v"(dst + 2048), "v"(dst + 3072), "v"(v0), "v"(v1), "v"(v2), "v"(v3) : "memory");
         }
-        __syncthreads();
-        if (t == 0) s_last_seg = (__hip_atomic_fetch_add(&tix[tile * n_cg + cg], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == nseg - 1) ? 1 : 0;
+        __syncthreads();                                       // the hand-off of frcnn_dev.h (last_arriver), its wait in the statement above
+        if (t == 0) s_last_seg = (agent_add(&tix[tile * n_cg + cg], 1) == nseg - 1) ? 1 : 0;
         __syncthreads();
         if (!s_last_seg) { RT_T(2); return; }
         const int32_t *sl = slot + tbase[tile];                // record position of segment s = where its partial tile lies

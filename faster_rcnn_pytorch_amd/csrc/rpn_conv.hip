@@ -21,6 +21,7 @@
 //   is a permutation of a K = 16 slice; the head weights are pre-packed with the same permutation.  The two channel halves are
 //   added through LDS, the biases are added and cls / reg are written.
 #include "frcnn_common.h"
+#include "frcnn_dev.h"
 #include "frcnn_internal.h"
 #include "frcnn_layout.h"
 FRCNN_LAYOUT_STAMP(rpn_conv);
@@ -51,23 +52,7 @@ struct ConvLevels {
     int pos0[FRCNN_MAX_LEVELS];                    // first output row of level l in the concatenated cls / reg tensors
 };
 
-__device__ __forceinline__ unsigned short f2bf(float f)
-{
-    unsigned u = __float_as_uint(f);
-    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (unsigned short)((u >> 16) | 0x40);
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return (unsigned short)(u >> 16);
-}
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));      // (HIP's uint4 is a struct around a union: arrays of it end up in scratch)
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-// (lo, hi) -> two bf16 in one dword, round to nearest even, NaN stays NaN: one v_cvt_pk_bf16_f32 on gfx950
-__device__ __forceinline__ unsigned cvt_pk_bf16(float lo, float hi)
-{
-    const bf16x2_t r = __builtin_convertvector((f32x2_t){lo, hi}, bf16x2_t);
-    return *(const unsigned *)&r;
-}
-__device__ __forceinline__ float bf2f(unsigned short b) { return __uint_as_float((unsigned)b << 16); }
 
 // Position of W3p element (chunk, tap, row m, channel k of the chunk): [chunk 16][tap 9][row block 8][half g 2][row-in-block 32][8], i.e.
 // inside a (tap, 32-row block) the 64 x 16-byte pieces lie in LANE order of the A fragment read (lane = 32 g + row: "8 consecutive
@@ -86,7 +71,7 @@ __global__ __launch_bounds__(256) void rpn_conv_pack_kernel(const float *__restr
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < 16 * 9 * 256 * 16) {
         const int k = i & 15, m = (i >> 4) & 255, tap = (i >> 12) % 9, chunk = (i >> 12) / 9;
-        w3p[rc3_wpos(chunk, tap, m, k)] = f2bf(w3[((size_t)m * RC3_C + chunk * 16 + k) * 9 + tap]);
+        w3p[rc3_wpos(chunk, tap, m, k)] = bf16_rne(w3[((size_t)m * RC3_C + chunk * 16 + k) * 9 + tap]);
     }
     if (i < 8 * 2 * 32 * 2 * 8) {
         const int e = i & 7, g = (i >> 3) & 1, j = (i >> 4) & 31, s = (i >> 9) & 1, ct = i >> 10;
@@ -94,7 +79,7 @@ __global__ __launch_bounds__(256) void rpn_conv_pack_kernel(const float *__restr
         float v = 0.0f;
         if (j < n_cls) v = w_cls[(size_t)j * RC3_C + c];
         else if (j < n_cls + n_reg) v = w_reg[(size_t)(j - n_cls) * RC3_C + c];
-        whp[i] = f2bf(v);
+        whp[i] = bf16_rne(v);
     }
 }
 
@@ -106,7 +91,7 @@ __global__ __launch_bounds__(256) void rpn_conv_pack_bwd_kernel(const float *__r
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < 16 * 9 * 256 * 16) {
         const int k = i & 15, m = (i >> 4) & 255, tap = (i >> 12) % 9, chunk = (i >> 12) / 9;
-        w3p[rc3_wpos(chunk, tap, m, k)] = f2bf(w3[((size_t)(chunk * 16 + k) * RC3_C + m) * 9 + (8 - tap)]);
+        w3p[rc3_wpos(chunk, tap, m, k)] = bf16_rne(w3[((size_t)(chunk * 16 + k) * RC3_C + m) * 9 + (8 - tap)]);
     }
 }
 
@@ -123,13 +108,7 @@ extern "C" __attribute__((visibility("default"))) void frcnn_wg_blocks_read(void
 #define WG_BLK(slot, v) do {} while (0)
 #define RC3_ACC(slot, a, b) do {} while (0)
 #endif
-// hand-placed vector-memory waits / loads (see the schedule in rpn_conv3x3_head_tile)
-template <int N> __device__ __forceinline__ void vm_wait() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-__device__ __forceinline__ void lds_barrier()                   // workgroup barrier that leaves vector-memory operations in flight (__syncthreads() would drain an LDS-DMA)
-{
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-}
+// hand-placed vector-memory loads; the counted waits are vm_wait / barrier_keep_vm of frcnn_dev.h (see the schedule in rpn_conv3x3_head_tile)
 __device__ __forceinline__ unsigned ld_dword(const unsigned short *p)
 {
     unsigned v;
@@ -326,7 +305,7 @@ __device__ __forceinline__ void rpn_conv3x3_head_tile(int lvl, int tile, int ysu
     load_x(1, xv, 0, XI);
     issue_w(1, 1);
     issue_w_part(2, 2, 0, 2);
-    lds_barrier();
+    barrier_keep_vm();
     load_frags(I0{}, 0, 0, 0);
     auto mfma_group = [&](auto S_, int ct) {
         constexpr int p = decltype(S_)::value;
@@ -370,7 +349,7 @@ __device__ __forceinline__ void rpn_conv3x3_head_tile(int lvl, int tile, int ysu
         RC3_STAMP(t3);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         RC3_STAMP(t4);
-        lds_barrier();
+        barrier_keep_vm();
         RC3_STAMP(t5);
         RC3_STAMP(t6);
 #pragma unroll
@@ -402,7 +381,7 @@ __device__ __forceinline__ void rpn_conv3x3_head_tile(int lvl, int tile, int ysu
 #endif
     vm_wait<0>();                                           // the stray DMA pieces and pixel loads of the last steps are done ...
     tie_x(xv);
-    lds_barrier();                                          // ... in every wave before the epilogue reuses LDS
+    barrier_keep_vm();                                          // ... in every wave before the epilogue reuses LDS
 
     // ---- epilogue: raw (bf16), h = relu(raw + b3) as the B operand of the heads' product.
     // Accumulator register r of a lane is channel cb + (r & 3) + 8 (r >> 2) + 4 g at pixel (yy, x0 + li): registers (r, r + 1) are

@@ -37,6 +37,7 @@
 //   tiles = one workgroup per CU, one strip per wave) there are NO global partials; at FPN size (64 tiles) four workgroups share a
 //   tile through slabs + ticket + fixed-order sum like above.
 #include "frcnn_common.h"
+#include "frcnn_dev.h"
 #include "frcnn_internal.h"
 #include "frcnn_layout.h"
 #include <algorithm>
@@ -200,11 +201,7 @@ __global__ __launch_bounds__(256, CF_WPS) void rpn_conv3x3_f32_kernel(CfArgs a, 
                 for (int r = 0; r < 16; ++r)
                     asm volatile("global_store_dword %0, %1, off offset:%2 sc1" :: "v"(dst), "v"(acc[mi][ni][r]), "n"(r * 256) : "memory");
             }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // the slab has been performed before the ticket announces it
-        __syncthreads();
-        if (tid == 0) s_last = (__hip_atomic_fetch_add(&cnt[T.tile], n_chunks, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + n_chunks == Kc) ? 1 : 0;
-        __syncthreads();
-        if (!s_last) return;
+        if (!last_arriver(&cnt[T.tile], n_chunks, Kc, s_last)) return;      // the slab has been performed before the ticket announces it
         // this workgroup completed the tile: add every range's slab in range order (its own included: the order never depends on who is last)
         const long long lo = (long long)T.tile * Kc, hi = lo + Kc - 1;
         int s_first = (int)((lo * G) / U), s_end = (int)((hi * G) / U);
@@ -245,7 +242,7 @@ __global__ __launch_bounds__(256, CF_WPS) void rpn_conv3x3_f32_kernel(CfArgs a, 
             for (int r = 0; r < 16; ++r) acc[1][1][r] += t[3][r];
         }
         store_tile(T);
-        if (tid == 0) __hip_atomic_store(&cnt[T.tile], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // ready for the next call
+        if (tid == 0) ticket_reset(&cnt[T.tile]);      // ready for the next call
     };
 
     int tile = u0 / Kc, chunk = u0 - tile * Kc;
@@ -1081,7 +1078,7 @@ __device__ __forceinline__ void wn_gemm_block(const WgArgs &a, float *__restrict
         if constexpr (NT && MT == 64 && NW == 64)
             asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt" ::"s"(__builtin_amdgcn_readfirstlane(l)), "v"(g) : "memory");
         else
-            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(__builtin_amdgcn_readfirstlane(l)), "v"(g) : "memory");
+            dma16_to_lds(g, lds);
     };
     // one wave transfer of a chunk's staging: piece q < (TA + TB) / 4 of this wave (the first TA / 4 belong to the A tile)
     auto issue_piece = [&](const Tl &T, int chunk, int buf, int q) {
@@ -1170,9 +1167,9 @@ __device__ __forceinline__ void wn_gemm_block(const WgArgs &a, float *__restrict
                 asm volatile("global_store_dwordx4 %0, %1, off offset:%2 sc1" :: "v"(dst), "v"(v), "n"(q * 1024) : "memory");
             }
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (tid == 0) s_last = (__hip_atomic_fetch_add(&cnt[T.tile], n_chunks, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + n_chunks == Kc) ? 1 : 0;
+        vm_wait<0>();                                              // last_arriver (frcnn_dev.h) written out: behind the call the tile's
+        __syncthreads();                                           // address is formed in front of the barrier and the kernel comes out differently
+        if (tid == 0) s_last = (agent_add(&cnt[T.tile], n_chunks) + n_chunks == Kc) ? 1 : 0;
         __syncthreads();
         if (!s_last) return;
         const long long lo = (long long)T.tile * Kc, hi = lo + Kc - 1;
@@ -1215,14 +1212,14 @@ __device__ __forceinline__ void wn_gemm_block(const WgArgs &a, float *__restrict
             }
         }
         store_tile(T);
-        if (tid == 0) __hip_atomic_store(&cnt[T.tile], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (tid == 0) ticket_reset(&cnt[T.tile]);
     };
 
     int tile = u0 / Kc, chunk = u0 - tile * Kc;
     Tl T = tile_of(tile);
     int seg_first = chunk;
     issue_dma(T, chunk, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    vm_wait<0>();
     __syncthreads();
     WN_STAMP_AT(1);
     for (int u = u0; u < u1; ++u) {
@@ -1374,7 +1371,7 @@ __device__ __forceinline__ void wn_gemm_block(const WgArgs &a, float *__restrict
             if (more) T = Tn;
         }
         tile = ntile; chunk = nchunk;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // the next chunk's transfers have landed (this wave's; the barrier covers the others')
+        vm_wait<0>();           // the next chunk's transfers have landed (this wave's; the barrier covers the others')
 #if !(defined(WN_ABL) && (WN_ABL & 8))                             // developer ablation 8: no barrier between chunks
         __syncthreads();
 #endif
@@ -1417,11 +1414,6 @@ __global__ __launch_bounds__(256, CF_WPS) void rpn_wino_gemm2_kernel(WgArgs a1, 
 typedef float wn_f32x4 __attribute__((ext_vector_type(4)));
 #define WO_TB 32
 #define WO_NB 4
-__device__ __forceinline__ void wn_dma16(const float *g, const float *lds)
-{
-    const unsigned l = (unsigned)(size_t)(const __attribute__((address_space(3))) float *)lds;
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(__builtin_amdgcn_readfirstlane(l)), "v"(g) : "memory");
-}
 template <int K, bool POOL>
 __global__ __launch_bounds__(256, 1) void rpn_wino_gemm_out64_kernel(WnArgs a, const float *__restrict__ U, const float *__restrict__ V)
 {
@@ -1437,12 +1429,12 @@ __global__ __launch_bounds__(256, 1) void rpn_wino_gemm_out64_kernel(WnArgs a, c
 #pragma unroll
         for (int q = 0; q < K / 16; ++q) {                                // U: 1-KB transfer d = k rows 4 d .. 4 d + 3; LDS float p of row r holds column (p - 16 r) mod 64
             const int d = wave + 4 * q, r = lane >> 4, c = ((lane & 15) * 4 - 16 * r) & 63;
-            wn_dma16(u + (size_t)(4 * d + r) * MO + c, sA + d * 256);
+            dma16_to_lds(u + (size_t)(4 * d + r) * MO + c, sA + d * 256);
         }
 #pragma unroll
         for (int q = 0; q < K / 32; ++q) {                                // V: transfer d = k rows 8 d .. 8 d + 7 of 32 tiles; row r holds column (p - 16 ((r & 3) >> 1)) mod 32
             const int d = wave + 4 * q, r = lane >> 3, c = ((lane & 7) * 4 - 16 * ((r & 3) >> 1)) & 31;
-            wn_dma16(v + (size_t)(8 * d + r) * a.Ttot + c, sB + d * 256);
+            dma16_to_lds(v + (size_t)(8 * d + r) * a.Ttot + c, sB + d * 256);
         }
     };
     wn_f32x4 acc[P][2];
@@ -1457,9 +1449,9 @@ __global__ __launch_bounds__(256, 1) void rpn_wino_gemm_out64_kernel(WnArgs a, c
         {
             const int fl = (P - 1 - xi) < (NB - 2) ? (P - 1 - xi) : (NB - 2);      // planes issued after xi so far (compile-time: the loop is unrolled)
             static_assert(NB - 2 <= 2, "counted waits below");
-            if (fl == 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * TPW) : "memory");
-            else if (fl == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(TPW) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if (fl == 2) vm_wait<2 * TPW>();
+            else if (fl == 1) vm_wait<TPW>();
+            else vm_wait<0>();
         }
         __syncthreads();
 #if !(defined(WO_ABL) && (WO_ABL & 1))                             // developer ablation 1: no transfers behind the first planes
@@ -1723,7 +1715,7 @@ __global__ __launch_bounds__(256, CW_WPS) void rpn_conv3x3_f32_wgrad_kernel(CwAr
             const float v = ((s_all[e] + s_all[3072 + e]) + s_all[2 * 3072 + e]) + s_all[3 * 3072 + e];
             const int tt = e / 1024, r = (e >> 6) & 15, l = e & 63;
             const int co = (r & 3) + 8 * (r >> 2) + 4 * (l >> 5), ci = l & 31, t = g * 3 + tt;
-            if (dst) __hip_atomic_store(&dst[(co * 32 + ci) * 9 + t], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (dst) agent_st(&dst[(co * 32 + ci) * 9 + t], v);
 #ifndef CW_NO_STORE
             else dw[((size_t)(co0 + co) * C + ci0 + ci) * 9 + t] = v;
 #else
@@ -1733,18 +1725,18 @@ __global__ __launch_bounds__(256, CW_WPS) void rpn_conv3x3_f32_wgrad_kernel(CwAr
         __syncthreads();
     }
     if (a.S == 1) return;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    vm_wait<0>();                                                  // the hand-off of frcnn_dev.h (last_arriver), written out
     __syncthreads();
-    if (tid == 0) s_last = (__hip_atomic_fetch_add(&cnt[tile], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == a.S - 1) ? 1 : 0;
+    if (tid == 0) s_last = (agent_add(&cnt[tile], 1) == a.S - 1) ? 1 : 0;
     __syncthreads();
     if (!s_last) return;
     for (int e = tid; e < 32 * 32 * 9; e += 256) {
         float v = 0.0f;
-        for (int s = 0; s < a.S; ++s) v += __hip_atomic_load(&part[((size_t)tile * a.S + s) * (32 * 32 * 9) + e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        for (int s = 0; s < a.S; ++s) v += agent_ld(&part[((size_t)tile * a.S + s) * (32 * 32 * 9) + e]);
         const int co = e / 288, rem = e - co * 288;
         dw[((size_t)(co0 + co) * C + ci0) * 9 + rem] = v;
     }
-    if (tid == 0) __hip_atomic_store(&cnt[tile], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tid == 0) ticket_reset(&cnt[tile]);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host side

@@ -15,6 +15,7 @@
 // [sum P_l * A, 2|4] tensors), and the mixed-precision configuration (bf16 conv output, bf16 MFMA operands, fp32
 // accumulate / bias / outputs so that box regression stays fp32) is a template instance of the same kernel.
 #include "frcnn_common.h"
+#include "frcnn_dev.h"
 #include "frcnn_internal.h"
 #include "frcnn_layout.h"
 FRCNN_LAYOUT_STAMP(rpn_head);
@@ -31,15 +32,7 @@ struct HeadLevels {
 };
 
 __device__ __forceinline__ float load_raw(const float *p, size_t i) { return p[i]; }
-__device__ __forceinline__ float load_raw(const unsigned short *p, size_t i) { return __uint_as_float((unsigned)p[i] << 16); }
-
-__device__ __forceinline__ short to_bf16_rne(float f)
-{
-    unsigned u = __float_as_uint(f);
-    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (short)((u >> 16) | 0x40);       // NaN stays NaN
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return (short)(u >> 16);
-}
+__device__ __forceinline__ float load_raw(const unsigned short *p, size_t i) { return bf16_to_f32(p[i]); }
 
 // TIN: element type of the 3x3 output (float, or unsigned short = bf16 bits).  NT: number of 32-wide output tiles (1 when
 // n_cls + n_reg <= 32, the FPN head with A = 3).  BF16MM: contract on v_mfma_f32_32x32x16_bf16 (operands rounded to bf16,
@@ -113,11 +106,11 @@ __global__ __launch_bounds__(64 * WAVES) void rpn_head_tail_kernel(HeadLevels L,
             for (int t = 0; t < NT; ++t) {
                 const float4 *wp = (const float4 *)(wrow[t] ? wrow[t] + k0 + 8 * lk : nullptr);
                 const float4 q0 = wp ? wp[0] : make_float4(0.f, 0.f, 0.f, 0.f), q1 = wp ? wp[1] : make_float4(0.f, 0.f, 0.f, 0.f);
-                bv[t][0] = to_bf16_rne(q0.x); bv[t][1] = to_bf16_rne(q0.y); bv[t][2] = to_bf16_rne(q0.z); bv[t][3] = to_bf16_rne(q0.w);
-                bv[t][4] = to_bf16_rne(q1.x); bv[t][5] = to_bf16_rne(q1.y); bv[t][6] = to_bf16_rne(q1.z); bv[t][7] = to_bf16_rne(q1.w);
+                bv[t][0] = bf16_rne(q0.x); bv[t][1] = bf16_rne(q0.y); bv[t][2] = bf16_rne(q0.z); bv[t][3] = bf16_rne(q0.w);
+                bv[t][4] = bf16_rne(q1.x); bv[t][5] = bf16_rne(q1.y); bv[t][6] = bf16_rne(q1.z); bv[t][7] = bf16_rne(q1.w);
             }
 #pragma unroll
-            for (int u = 0; u < 8; ++u) av[u] = to_bf16_rne(a[u] <= 0.0f ? 0.0f : a[u]);      // (NaN-keeping ReLU)
+            for (int u = 0; u < 8; ++u) av[u] = bf16_rne(a[u] <= 0.0f ? 0.0f : a[u]);      // (NaN-keeping ReLU)
 #pragma unroll
             for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv[t], acc[t], 0, 0, 0);
         }
@@ -239,15 +232,8 @@ struct HeadBwdLevels {
     int pos0[FRCNN_MAX_LEVELS];
 };
 
-typedef __bf16 hb_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float hb_f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned hb_cvt_pk_bf16(float lo, float hi)      // one v_cvt_pk_bf16_f32: round to nearest even
-{
-    const hb_bf16x2 r = __builtin_convertvector((hb_f32x2){lo, hi}, hb_bf16x2);
-    return *(const unsigned *)&r;
-}
 __device__ __forceinline__ void store_raw(float *p, size_t i, float v) { p[i] = v; }
-__device__ __forceinline__ void store_raw(unsigned short *p, size_t i, float v) { p[i] = (unsigned short)to_bf16_rne(v); }
+__device__ __forceinline__ void store_raw(unsigned short *p, size_t i, float v) { p[i] = bf16_rne(v); }
 
 template <typename TIN, int NJ, int CT>
 #ifndef HB_NW
@@ -390,7 +376,7 @@ __global__ __launch_bounds__(64 * HB_NW) void rpn_head_tail_bwd_kernel(HeadBwdLe
                 for (int k = 0; k < 8; ++k) {
                     const int r = 2 * k;
                     const float d0 = zr[ct][r] > 0.0f ? acc[r] : 0.0f, d1 = zr[ct][r + 1] > 0.0f ? acc[r + 1] : 0.0f;
-                    const unsigned own = hb_cvt_pk_bf16(d0, d1);
+                    const unsigned own = cvt_pk_bf16(d0, d1);
                     const unsigned nb = (unsigned)__builtin_amdgcn_mov_dpp((int)own, 0xB1, 0xF, 0xF, true);
                     const unsigned d = __builtin_amdgcn_perm(nb, own, sel);
                     const int cl = ((r + (odd ? 1 : 0)) & 3) + 8 * (r >> 2) + 4 * lk;

@@ -16,6 +16,7 @@
 // Sampling semantics in device-RNG mode: keep the candidates with the smallest (Philox4x32-10 key, position) pairs = the reference's
 // randperm sampling run with perm = argsort of the keys (oracle/philox_ref.py; tests compare bit for bit).
 #include "frcnn_common.h"
+#include "frcnn_dev.h"
 #include <cstdlib>
 #include <cstring>
 #include <type_traits>
@@ -35,19 +36,6 @@ __device__ __forceinline__ float iou_variant(int variant, float4 b, float4 g)
 __device__ __forceinline__ bool anchor_inside(float4 a) { return a.x >= 0.0f && a.y >= 0.0f && a.z <= 1.0f && a.w <= 1.0f; }
 
 // ------------------------------------------------------------------------------------------------
-// wave-wide max of a 64-bit key (6 xor-shuffle steps on both halves)
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long k)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)k, o);
-        const unsigned hi = (unsigned)__shfl_xor((int)(unsigned)(k >> 32), o);
-        const unsigned long long other = ((unsigned long long)hi << 32) | lo;
-        k = other > k ? other : k;
-    }
-    return k;
-}
-
 // colkey[g * CK_STRIDE]: one 64-byte line per GT box, so the per-box atomics of different boxes go to different
 // L2 channels instead of serialising on one line (1944 same-line atomics cost ~23 us; this form ~2 us)
 #define CK_STRIDE 8
@@ -81,7 +69,7 @@ __global__ __launch_bounds__(256) void rpn_colmax_kernel(int variant, const floa
             if (v >= 0.0f)                              // NaN never wins
                 key = ((unsigned long long)__float_as_uint(v) << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)i);
         }
-        key = wave_max_u64(key);
+        key = wave_max_xor(key);
         if ((threadIdx.x & 63) == 0) s_k[threadIdx.x >> 6] = key;
         __syncthreads();
         if (threadIdx.x == 0) {
@@ -90,7 +78,7 @@ __global__ __launch_bounds__(256) void rpn_colmax_kernel(int variant, const floa
             m = s_k[2] > m ? s_k[2] : m;
             m = s_k[3] > m ? s_k[3] : m;
             // monotone target: a (possibly stale) plain read that already beats m makes the atomic unnecessary
-            if (m != 0ull && m > __hip_atomic_load(&colkey[(size_t)g * CK_STRIDE], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+            if (m != 0ull && m > agent_ld(&colkey[(size_t)g * CK_STRIDE]))
                 atomicMax(&colkey[(size_t)g * CK_STRIDE], m);
         }
         __syncthreads();
@@ -112,7 +100,7 @@ __device__ __forceinline__ int rpn_label_anchor(int variant, float4 a, int i, co
         const float v = iou_variant(variant, a, gt[g]);
         if (v > best) { best = v; arg = g; }
         const unsigned long long *p = &colkey[(size_t)g * CK_STRIDE];
-        const unsigned long long ck = AGENT ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *p;
+        const unsigned long long ck = AGENT ? __hip_atomic_load(p, FRCNN_RLX_AGENT) : *p;     // (written out: see FRCNN_RLX_AGENT)
         if (variant == 1) match |= (v == __uint_as_float((unsigned)(ck >> 32))) && ck != 0ull;
         else match |= (0xFFFFFFFFu - (unsigned)ck) == (unsigned)i && ck != 0ull;
     }
@@ -189,12 +177,7 @@ __global__ __launch_bounds__(256) void rpn_label_kernel(int variant, const float
 __device__ __forceinline__ int block_excl_scan_1024(int v, int *s_w, int *total)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(inc, o);
-        if (lane >= o) inc += t;
-    }
+    const int inc = wave_incl_scan(v);
     __syncthreads();                       // protect s_w reuse
     if (lane == 63) s_w[wave] = inc;
     __syncthreads();
@@ -354,17 +337,17 @@ struct RpnCtl { int32_t n_pos, n_neg, ticket2, pad0; unsigned long long snap[2];
 // true in exactly one caller: the last of `nb` workgroups to arrive (one thread per workgroup calls it)
 __device__ __forceinline__ bool rpn_arrive_last(RpnArrive *a, int nb)
 {
-    if (nb <= 32) return __hip_atomic_fetch_add(&a->top[0], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == nb - 1;   // few arrivals: one level, one round trip
+    if (nb <= 32) return agent_add(&a->top[0], 1) == nb - 1;   // few arrivals: one level, one round trip
     const int x = (int)blockIdx.x & 7;
     const int n_x = (nb - x + 7) / 8;                              // workgroups with my residue
-    if (__hip_atomic_fetch_add(&a->sub[x][0], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != n_x - 1) return false;
-    return __hip_atomic_fetch_add(&a->top[0], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 8 - 1;
+    if (agent_add(&a->sub[x][0], 1) != n_x - 1) return false;
+    return agent_add(&a->top[0], 1) == 8 - 1;
 }
 // threads 0 .. 8 of one workgroup put the counters back to zero (after everybody has arrived)
 __device__ __forceinline__ void rpn_arrive_reset(RpnArrive *a, int t)
 {
-    if (t < 8) __hip_atomic_store(&a->sub[t][0], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else if (t == 8) __hip_atomic_store(&a->top[0], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (t < 8) agent_st(&a->sub[t][0], 0);
+    else if (t == 8) agent_st(&a->top[0], 0);
 }
 #ifdef RPN_TRACE                        // developer build: phase stamps of rpn_match_kernel (tools/dev/rpn_trace.py)
 __device__ unsigned long long g_rpn_trace[16];
@@ -387,16 +370,11 @@ __device__ __forceinline__ void find_bin_2048(const unsigned *hist, int want, in
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
         const int b = 8 * t + q;
-        c[q] = b < RSB ? (GLOBAL ? __hip_atomic_load(&hist[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : hist[b]) : 0u;     // (!GLOBAL: a histogram in LDS)
+        c[q] = b < RSB ? (GLOBAL ? agent_ld(&hist[b]) : hist[b]) : 0u;     // (!GLOBAL: a histogram in LDS)
         local += (int)c[q];
     }
     const int lane = t & 63, wave = t >> 6;
-    int inc = local;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int v = __shfl_up(inc, o);
-        if (lane >= o) inc += v;
-    }
+    const int inc = wave_incl_scan(local);
     __syncthreads();
     if (lane == 63 && wave < 4) s_tmp[wave] = inc;
     if (t == 0) { s_tmp[4] = 0; s_tmp[5] = 0; s_tmp[6] = 0; s_tmp[7] = 0; }
@@ -447,8 +425,8 @@ __device__ __forceinline__ void rpn_apply_sweep(int i0, int i1, const int8_t *__
         for (int u = 0; u < U; ++u) {
             const int i = min(base + u * bs + (int)threadIdx.x, i1 - 1);
             if (SAME_LAUNCH) {                                   // written by other workgroups of this launch: agent-scope loads
-                lab[u] = __hip_atomic_load(&label8[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                k[u] = __hip_atomic_load(&keys[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                lab[u] = agent_ld(&label8[i]);
+                k[u] = agent_ld(&keys[i]);
             } else { lab[u] = label8[i]; k[u] = keys[i]; }
         }
 #pragma unroll
@@ -461,7 +439,7 @@ __device__ __forceinline__ void rpn_apply_sweep(int i0, int i1, const int8_t *__
             if (bin > c.bin) out_cls[i] = -1;
             else if (bin == c.bin) {
                 const unsigned slot = atomicAdd(&sel->nb[lab[u]], 1u);
-                if (slot < RPN_BL_CAP) __hip_atomic_store(&bl->e[lab[u]][slot], ((unsigned long long)k[u] << 32) | (unsigned)i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (slot < RPN_BL_CAP) agent_st(&bl->e[lab[u]][slot], ((unsigned long long)k[u] << 32) | (unsigned)i);
             }
         }
     }
@@ -474,11 +452,11 @@ __device__ __forceinline__ void rpn_apply_resolve(RpnCut cn, RpnCut cp, RpnSel2 
     for (int c = 0; c < 2; ++c) {
         const RpnCut &ct = c == 1 ? cp : cn;
         if (!ct.drop) continue;                                      // uniform
-        const int m_raw = (int)__hip_atomic_load(&sel->nb[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int m_raw = (int)agent_ld(&sel->nb[c]);
         const int m = min(m_raw, RPN_BL_CAP);
         if (m_raw > RPN_BL_CAP && threadIdx.x == 0) counts[2] = 8;   // cannot happen below ~8 M anchors (the entry point's limit)
         __syncthreads();
-        for (int q = threadIdx.x; q < m; q += blockDim.x) s_e[q] = __hip_atomic_load(&bl->e[c][q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        for (int q = threadIdx.x; q < m; q += blockDim.x) s_e[q] = agent_ld(&bl->e[c][q]);
         __syncthreads();
         for (int q = threadIdx.x; q < m; q += blockDim.x) {
             const unsigned long long me = s_e[q];
@@ -490,22 +468,6 @@ __device__ __forceinline__ void rpn_apply_resolve(RpnCut cn, RpnCut cp, RpnSel2 
     __syncthreads();
     for (int b = threadIdx.x; b < 2 * RSB; b += blockDim.x) (&sel->hist[0][0])[b] = 0u;
     if (threadIdx.x < 2) sel->nb[threadIdx.x] = 0u;
-}
-
-// wave-wide maximum of a float on DPP row shifts / broadcasts (no LDS crossbar): every lane of the wave must be active
-__device__ __forceinline__ float wave_max_f32_dpp(float v)
-{
-    const float ninf = -__builtin_inff();
-#define DPP_MAX(ctrl, rmask)                                                                                                       \
-    v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, ninf), __builtin_bit_cast(int, v), ctrl, rmask, 0xf, false)))
-    DPP_MAX(0x111, 0xf);    // row_shr:1
-    DPP_MAX(0x112, 0xf);    // row_shr:2
-    DPP_MAX(0x114, 0xf);    // row_shr:4
-    DPP_MAX(0x118, 0xf);    // row_shr:8   -> lane 15 of every row holds the row's maximum
-    DPP_MAX(0x142, 0xa);    // row_bcast:15 into rows 1 and 3
-    DPP_MAX(0x143, 0xc);    // row_bcast:31 into rows 2 and 3 -> lane 63 holds the wave's maximum
-#undef DPP_MAX
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
 
 template <bool INLINE>
@@ -528,8 +490,8 @@ __global__ __launch_bounds__(1024) void rpn_match_kernel(int variant, const floa
     RPN_T(blockIdx.x == 0 && tid == 0, 0);
     if (philox_state && blockIdx.x == 0 && tid == 0) {              // this call's (seed, offset); the stream moves on (frcnn_hip.h)
         const unsigned long long sd = philox_state[0], of = philox_state[1];
-        __hip_atomic_store(&ctl->snap[0], sd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&ctl->snap[1], of, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        agent_st(&ctl->snap[0], sd);
+        agent_st(&ctl->snap[1], of);
         philox_state[1] = of + 1ull;
     }
     for (int b = tid; b < 2 * RSB; b += 1024) (&s_hist[0][0])[b] = 0u;
@@ -546,7 +508,7 @@ __global__ __launch_bounds__(1024) void rpn_match_kernel(int variant, const floa
                 // are anchors in ascending order) -- 7 DPP steps and a ballot instead of twelve ds_bpermute for the 64-bit key
                 float v = -1.0f;
                 if (live) { const float t = iou_variant(variant, a, gt[g0 + g]); if (t >= 0.0f) v = t; }   // NaN never wins
-                const float m = wave_max_f32_dpp(v);
+                const float m = wave_max_dpp_all(v);
                 const unsigned long long who = __ballot(v == m);
                 if (lane == 0)
                     s_k[wave][g] = m >= 0.0f ? ((unsigned long long)__float_as_uint(m) << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)(i + __builtin_ctzll(who))) : 0ull;
@@ -557,8 +519,8 @@ __global__ __launch_bounds__(1024) void rpn_match_kernel(int variant, const floa
 #pragma unroll
                 for (int q = 1; q < 16; ++q) m = s_k[q][tid] > m ? s_k[q][tid] : m;
                 unsigned long long *ck = &colkey[(size_t)(g0 + tid) * CK_STRIDE];
-                if (m != 0ull && m > __hip_atomic_load(ck, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(ck, m);
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // performed before my workgroup arrives at the barrier
+                if (m != 0ull && m > agent_ld(ck)) atomicMax(ck, m);
+                vm_wait<0>();     // performed before my workgroup arrives at the barrier
             }
             __syncthreads();
         }
@@ -568,10 +530,10 @@ __global__ __launch_bounds__(1024) void rpn_match_kernel(int variant, const floa
     // (everything the other side of the barrier reads -- colkey, the Philox snapshot -- was written with agent-scope atomics that have
     // been performed, and is read with agent-scope loads: no cache write-back / invalidate needed)
     if (tid == 0) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (rpn_arrive_last(&ctl->bar, nb)) __hip_atomic_store(&ctl->flag[0], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        vm_wait<0>();
+        if (rpn_arrive_last(&ctl->bar, nb)) agent_st(&ctl->flag[0], 1);
         int spins = 0, ok = 1;
-        while (__hip_atomic_load(&ctl->flag[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) {
+        while (agent_ld(&ctl->flag[0]) == 0) {
             __builtin_amdgcn_s_sleep(4);
             if (++spins > RPN_BAR_SPINS) { ok = 0; break; }
         }
@@ -582,8 +544,8 @@ __global__ __launch_bounds__(1024) void rpn_match_kernel(int variant, const floa
     // ---- (2) labels, keys, key histogram
     RPN_T(blockIdx.x == 0 && tid == 0, 2);
     if (philox_state) {
-        seed = __hip_atomic_load(&ctl->snap[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        offset = __hip_atomic_load(&ctl->snap[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        seed = agent_ld(&ctl->snap[0]);
+        offset = agent_ld(&ctl->snap[1]);
     }
     int lab = -1;
     if (i < N) {
@@ -595,12 +557,12 @@ __global__ __launch_bounds__(1024) void rpn_match_kernel(int variant, const floa
         }
         // what the sampling workgroup reads back (or overwrites) in the SAME launch goes out write-through: with an acknowledged store
         // behind every ticket no L2 write-back / invalidate pair is needed around it (that pair cost ~3 us of the INLINE launch)
-        __hip_atomic_store(&out_cls[i], (int64_t)lab, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        agent_st(&out_cls[i], (int64_t)lab);
         out_reg[i] = reg;
-        __hip_atomic_store(&label8[i], (int8_t)lab, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        agent_st(&label8[i], (int8_t)lab);
         if (lab >= 0) {
             const unsigned k = philox_first(seed, offset, (unsigned)lab, (unsigned)i);
-            __hip_atomic_store(&keys[i], k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            agent_st(&keys[i], k);
             atomicAdd(&s_hist[lab][k >> 21], 1u);
         }
     }
@@ -622,20 +584,20 @@ __global__ __launch_bounds__(1024) void rpn_match_kernel(int variant, const floa
     RPN_T(blockIdx.x == 0 && tid == 0, 3);
     __syncthreads();
     // (labels, keys, classes, counters: all written through and acknowledged before the ticket)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    vm_wait<0>();
     __syncthreads();
     if (tid == 0) s_flag = rpn_arrive_last(&ctl->ticket, nb);
     __syncthreads();
     if (!s_flag) return;
     RPN_T(tid == 0, 4);
     for (int g = tid; g < G; g += 1024) colkey[(size_t)g * CK_STRIDE] = 0ull;
-    const int n_pos = __hip_atomic_load(&ctl->n_pos, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const int n_neg = __hip_atomic_load(&ctl->n_neg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int n_pos = agent_ld(&ctl->n_pos);
+    const int n_neg = agent_ld(&ctl->n_neg);
     __syncthreads();
     if (tid == 0) {
         counts[0] = n_pos; counts[1] = n_neg; counts[2] = 0; counts[3] = 0;
-        __hip_atomic_store(&ctl->n_pos, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); __hip_atomic_store(&ctl->n_neg, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&ctl->flag[0], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        agent_st(&ctl->n_pos, 0); agent_st(&ctl->n_neg, 0);
+        agent_st(&ctl->flag[0], 0);
     }
     if (tid >= 64 && tid < 64 + 9) rpn_arrive_reset(&ctl->bar, tid - 64);
     if (tid >= 128 && tid < 128 + 9) rpn_arrive_reset(&ctl->ticket, tid - 128);
@@ -643,7 +605,7 @@ __global__ __launch_bounds__(1024) void rpn_match_kernel(int variant, const floa
     if constexpr (INLINE) {
         const RpnCut cn = rpn_cut(sel, n_pos, n_neg, 0, s_tmp), cp = rpn_cut(sel, n_pos, n_neg, 1, s_tmp);
         if (cn.drop || cp.drop) rpn_apply_sweep<RS_LDS_MAX / 1024, true>(0, N, label8, keys, cn, cp, sel, bl, out_cls);   // one round: N <= RS_LDS_MAX
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // the list's entries and counters are in memory before anybody reads them back
+        vm_wait<0>();            // the list's entries and counters are in memory before anybody reads them back
         __syncthreads();
         rpn_apply_resolve(cn, cp, sel, bl, out_cls, counts, s_big);
     }
@@ -668,12 +630,12 @@ __global__ __launch_bounds__(1024) void rpn_apply_kernel(int N, const int8_t *__
     const int per = (N + (int)gridDim.x - 1) / (int)gridDim.x;
     const int i0 = (int)blockIdx.x * per;
     rpn_apply_sweep<2, false>(i0, min(N, i0 + per), label8, keys, cn, cp, sel, bl, out_cls);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    vm_wait<0>();
     __syncthreads();
-    if (threadIdx.x == 0) s_flag = __hip_atomic_fetch_add(&ctl->ticket2, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1;   // (list entries and counters are written through and acknowledged)
+    if (threadIdx.x == 0) s_flag = agent_add(&ctl->ticket2, 1) == (int)gridDim.x - 1;   // (list entries and counters are written through and acknowledged)
     __syncthreads();
     if (!s_flag) return;
-    if (threadIdx.x == 0) __hip_atomic_store(&ctl->ticket2, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (threadIdx.x == 0) ticket_reset(&ctl->ticket2);
     rpn_apply_resolve(cn, cp, sel, bl, out_cls, counts, s_e);
 }
 

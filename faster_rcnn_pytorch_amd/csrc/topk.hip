@@ -14,6 +14,7 @@
 //   (optionally) the box to position rank(i) if rank(i) < K: the gather at model.py:48 is fused.
 // Work: N^2 pair compares -- used for N < 4096 only; larger N take the sample sort further down.
 #include "frcnn_common.h"
+#include "frcnn_dev.h"
 #include "frcnn_internal.h"
 #include "topk_dev.h"
 #include "frcnn_layout.h"
@@ -159,8 +160,7 @@ __global__ __launch_bounds__(256) void topk_count_kernel(const float *__restrict
         valid += (!proposal_mode || sc >= 0.0f) ? 1 : 0;
         atomicAdd(&s_cnt[ss_bucket(s_split, ss_key(sc, i))], 1);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) valid += __shfl_xor(valid, o);
+    valid = wave_sum_xor(valid);
     if ((threadIdx.x & 63) == 0 && valid) atomicAdd(&s_valid, valid);
     __syncthreads();
     if (s_cnt[threadIdx.x]) atomicAdd(&ctl->cnt[threadIdx.x], s_cnt[threadIdx.x]);
@@ -171,9 +171,7 @@ __global__ __launch_bounds__(256) void topk_count_kernel(const float *__restrict
 __device__ __forceinline__ int ss_scan256(int v, int *s_w /*[4]*/)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(inc, o); if (lane >= o) inc += u; }
+    const int inc = wave_incl_scan(v);
     if (lane == 63) s_w[wave] = inc;
     __syncthreads();
     int base = 0;
@@ -228,18 +226,18 @@ __global__ __launch_bounds__(256) void topk_place_kernel(const float *__restrict
 // grid barrier of the partition launch: two-level arrival counters, the waiters poll the flag of generation `gen` (1, 2)
 __device__ __forceinline__ void ss_grid_barrier(SsCtl *__restrict__ ctl, int gen)
 {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                // what I wrote through / added has been performed before my workgroup arrives
+    vm_wait<0>();                // what I wrote through / added has been performed before my workgroup arrives
     __syncthreads();
     if (threadIdx.x == 0) {
         const int nb = (int)gridDim.x, x = (int)blockIdx.x & 7;
         int (*bar)[16] = ctl->bar + 9 * (gen - 1);
         bool last;
-        if (nb <= 32) last = __hip_atomic_fetch_add(&bar[8][0], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == nb - 1;
-        else last = __hip_atomic_fetch_add(&bar[x][0], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (nb - x + 7) / 8 - 1 &&
-                    __hip_atomic_fetch_add(&bar[8][0], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 8 - 1;
-        if (last) __hip_atomic_store(&ctl->flag[0], gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (nb <= 32) last = agent_add(&bar[8][0], 1) == nb - 1;
+        else last = agent_add(&bar[x][0], 1) == (nb - x + 7) / 8 - 1 &&
+                    agent_add(&bar[8][0], 1) == 8 - 1;
+        if (last) agent_st(&ctl->flag[0], gen);
         int spins = 0;
-        while (__hip_atomic_load(&ctl->flag[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < gen && ++spins < SS_BARRIER_SPINS)
+        while (agent_ld(&ctl->flag[0]) < gen && ++spins < SS_BARRIER_SPINS)
             __builtin_amdgcn_s_sleep(4);
     }
     __syncthreads();
@@ -286,7 +284,7 @@ __global__ __launch_bounds__(256) void topk_partition_kernel(const float *__rest
     if (c) atomicAdd(&ctl->cnt[threadIdx.x], c);
     if (threadIdx.x == 0 && s_valid) atomicAdd(&ctl->n_valid, s_valid);
     ss_grid_barrier(ctl, 1);
-    const int total = __hip_atomic_load(&ctl->cnt[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int total = agent_ld(&ctl->cnt[threadIdx.x]);
     const int excl = ss_scan256(total, s_w);
     s_base[threadIdx.x] = excl;
     __syncthreads();
@@ -297,15 +295,15 @@ __global__ __launch_bounds__(256) void topk_partition_kernel(const float *__rest
         if (bk[e] >= 0) {
             const int pos = s_base[bk[e]] + slot[e];
             if (!ss_in_range(pos, 1, N)) ss_mark_bad(ctl);         // counts / cursors not reset by this build's sampling workgroup: no wild store
-            else if (BUCKETS) __hip_atomic_store(&sorted[pos], k[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            else if (BUCKETS) agent_st(&sorted[pos], k[e]);
             else sorted[pos] = k[e];
         }
     if constexpr (BUCKETS) {
         ss_grid_barrier(ctl, 2);
         s_base[threadIdx.x] = excl;                                 // the buckets' first ranks
         s_cnt[threadIdx.x] = total;
-        const int n_valid = __hip_atomic_load(&ctl->n_valid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const bool bad = __hip_atomic_load(&ctl->pad[SS_PAD_BAD], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0 || n_valid < 0 || n_valid > N;
+        const int n_valid = __hip_atomic_load(&ctl->n_valid, FRCNN_RLX_AGENT);                   // (written out: see FRCNN_RLX_AGENT)
+        const bool bad = agent_ld(&ctl->pad[SS_PAD_BAD]) != 0 || n_valid < 0 || n_valid > N;
         const int n_out = bad ? -1 : (n_valid < K ? n_valid : K);
         if (blockIdx.x == 0 && threadIdx.x == 0) *out_count = n_out;
         __syncthreads();
@@ -333,7 +331,7 @@ __global__ __launch_bounds__(256) void topk_partition_kernel(const float *__rest
             };
             if (m <= 1024) {
                 __syncthreads();
-                for (int t = threadIdx.x; t < m; t += 256) s_k[t] = __hip_atomic_load(&seg[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                for (int t = threadIdx.x; t < m; t += 256) s_k[t] = agent_ld(&seg[t]);
                 __syncthreads();
                 for (int e = e0 + threadIdx.x; e < e1; e += 256) {
                     const u64 kk = s_k[e];
@@ -346,12 +344,12 @@ __global__ __launch_bounds__(256) void topk_partition_kernel(const float *__rest
             }
             for (int r0 = e0; r0 < e1; r0 += 256) {                 // an unlucky sample: row groups x 1024-key chunks
                 const int e = r0 + threadIdx.x;
-                const u64 kk = e < e1 ? __hip_atomic_load(&seg[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
+                const u64 kk = e < e1 ? agent_ld(&seg[e]) : 0ull;
                 int r = 0;
                 for (int c0 = 0; c0 < m; c0 += 1024) {
                     const int cn = min(1024, m - c0);
                     __syncthreads();
-                    for (int t = threadIdx.x; t < cn; t += 256) s_k[t] = __hip_atomic_load(&seg[c0 + t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    for (int t = threadIdx.x; t < cn; t += 256) s_k[t] = agent_ld(&seg[c0 + t]);
                     __syncthreads();
 #pragma unroll 8
                     for (int j = 0; j < cn; ++j) r += s_k[j] > kk;

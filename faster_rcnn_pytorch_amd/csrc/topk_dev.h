@@ -3,6 +3,7 @@
 // per-anchor function and rank them while the other workgroups decode the anchors -- one launch fewer on the proposal path.
 #pragma once
 #include "frcnn_common.h"
+#include "frcnn_dev.h"
 
 #define SS_BUCKETS 256
 #define SS_MIN_N 4096
@@ -22,7 +23,7 @@ struct SsCtl { ss_u64 split[SS_BUCKETS]; int cnt[SS_BUCKETS]; int cursor[SS_BUCK
 // object, a caller's uninitialised workspace) then yields a count of -1 downstream (NMS sees no live box, head_targets raises
 // FRCNN_HT_ERR_SHORT, the loss is NaN, check_device_status() reports) -- not a wild store.
 __device__ __forceinline__ bool ss_in_range(int base, int len, int N) { return base >= 0 && len >= 0 && (unsigned)base + (unsigned)len <= (unsigned)N; }
-__device__ __forceinline__ void ss_mark_bad(SsCtl *ctl) { __hip_atomic_store(&ctl->pad[SS_PAD_BAD], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void ss_mark_bad(SsCtl *ctl) { agent_st(&ctl->pad[SS_PAD_BAD], 1); }
 
 // order-preserving map float -> uint32 (total order; -0 < +0)
 __device__ __forceinline__ uint32_t f2key(float f)
