@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("FRCNN_HIP_LIB") or os.path.join(_HERE, "lib", "libfrc
 OK = 0
 ABI_VERSION = 7
 HT_ERR_PERM_LENGTH, HT_ERR_PERM_RANGE, HT_ERR_UPSTREAM_ABORT, HT_ERR_SHORT = 1, 2, 4, 8
+HT_ERR_GT_COUNT = RPN_ERR_GT_COUNT = 16                     # the device count of ground-truth boxes lay outside [1, capacity]
 OP_TOPK, OP_NMS, OP_REGION_PROPOSAL, OP_RPN_TARGETS, OP_HEAD_TARGETS, OP_PREPROCESS, OP_HEAD_BWD, OP_RPN_CONV, OP_RPN_CONV_WGRAD, OP_RPN_CONV_F32 = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
 OP_DETECT = 11
 OP_EVAL = 12
@@ -77,6 +78,9 @@ SIGNATURES = {
     "frcnn_rpn_targets": (_i, [_i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "frcnn_head_targets": (_i, [_i, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _u64, _u64, _vp,
                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "frcnn_rpn_targets_n": (_i, [_i, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "frcnn_head_targets_n": (_i, [_i, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _u64, _u64, _vp,
+                                  _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "frcnn_roi_pool_fwd": (_i, [_vp, _i, _i, _i, _vp, _i64, _i, _i, _f, _vp, _vp, _vp]),
     "frcnn_roi_pool_bwd": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _i, _vp, _vp]),
     "frcnn_roi_pool_fwd_a16": (_i, [_vp, _i, _i, _i, _vp, _i64, _f, _vp, _vp, _vp]),

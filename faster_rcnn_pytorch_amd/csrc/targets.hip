@@ -35,17 +35,34 @@ __device__ __forceinline__ float iou_variant(int variant, float4 b, float4 g)
 }
 __device__ __forceinline__ bool anchor_inside(float4 a) { return a.x >= 0.0f && a.y >= 0.0f && a.z <= 1.0f && a.w <= 1.0f; }
 
+// The number of live GT rows.  n_gt_dev == NULL: all G_cap rows (a launch argument, the classic entry points).  Otherwise the count
+// is DATA: one word in device memory, read here once per kernel (a uniform load), so a captured step serves frames with any number
+// of boxes.  A count outside [1, G_cap] is clamped to [0, G_cap] and reported (*err = FRCNN_RPN_ERR_GT_COUNT == FRCNN_HT_ERR_GT_COUNT);
+// with G == 0 no GT row is read and no anchor / RoI takes part.
+#define GT_COUNT_ERR 16
+static_assert(GT_COUNT_ERR == FRCNN_RPN_ERR_GT_COUNT && GT_COUNT_ERR == FRCNN_HT_ERR_GT_COUNT, "one bit for both makers");
+__device__ __forceinline__ int live_gt_count(const int32_t *__restrict__ n_gt_dev, int G_cap, int *err)
+{
+    *err = 0;
+    if (!n_gt_dev) return G_cap;
+    const int g = *n_gt_dev;
+    if (g <= 0 || g > G_cap) *err = GT_COUNT_ERR;
+    return min(max(g, 0), G_cap);
+}
+
 // ------------------------------------------------------------------------------------------------
 // colkey[g * CK_STRIDE]: one 64-byte line per GT box, so the per-box atomics of different boxes go to different
 // L2 channels instead of serialising on one line (1944 same-line atomics cost ~23 us; this form ~2 us)
 #define CK_STRIDE 8
 
 __global__ __launch_bounds__(256) void rpn_colmax_kernel(int variant, const float4 *__restrict__ anchors, int N,
-                                                         const float4 *__restrict__ gt, int G,
+                                                         const float4 *__restrict__ gt, int G_cap, const int32_t *__restrict__ n_gt_dev,
                                                          unsigned long long *__restrict__ colkey, int32_t *__restrict__ counts_zero,
                                                          unsigned long long *__restrict__ philox_state, unsigned long long *__restrict__ philox_snap)
 {
     __shared__ unsigned long long s_k[4];
+    int gerr;
+    const int G = live_gt_count(n_gt_dev, G_cap, &gerr);
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (counts_zero && blockIdx.x == 0 && threadIdx.x < 4) counts_zero[threadIdx.x] = 0;
     // device-resident RNG stream: this call consumes ONE offset value.  It is snapshotted for the sampling kernels that follow on
@@ -59,7 +76,7 @@ __global__ __launch_bounds__(256) void rpn_colmax_kernel(int variant, const floa
     bool live = false;
     if (i < N) {
         a = anchors[i];
-        live = variant == 1 || anchor_inside(a);
+        live = G > 0 && (variant == 1 || anchor_inside(a));
     }
     if (__syncthreads_or(live) == 0) return;            // whole block outside the image: nothing to contribute
     for (int g = 0; g < G; ++g) {
@@ -122,7 +139,7 @@ struct RpnBList { unsigned long long e[2][RPN_BL_CAP]; };                       
 // the key histogram -- for rpn_apply_kernel, the next launch.  (seed, offset) come from the snapshot rpn_colmax_kernel took, if given.
 template <bool KEYS>
 __global__ __launch_bounds__(256) void rpn_label_kernel(int variant, const float4 *__restrict__ anchors, int N,
-                                                        const float4 *__restrict__ gt, int G,
+                                                        const float4 *__restrict__ gt, int G_cap, const int32_t *__restrict__ n_gt_dev,
                                                         const unsigned long long *__restrict__ colkey,
                                                         unsigned long long seed, unsigned long long offset, const unsigned long long *__restrict__ philox_snap,
                                                         int64_t *__restrict__ out_cls, float4 *__restrict__ out_reg,
@@ -131,7 +148,10 @@ __global__ __launch_bounds__(256) void rpn_label_kernel(int variant, const float
 {
     __shared__ int s_cnt[2][4];
     __shared__ unsigned s_hist[KEYS ? 2 * RSB : 1];
+    int gerr;
+    const int G = live_gt_count(n_gt_dev, G_cap, &gerr);
     const int i = blockIdx.x * 256 + threadIdx.x;
+    if (gerr && i == 0) counts[2] = gerr;                  // (rpn_colmax_kernel, the launch before, left the word zero)
     if constexpr (KEYS) {
         if (philox_snap) { seed = philox_snap[0]; offset = philox_snap[1]; }
         for (int b = threadIdx.x; b < 2 * RSB; b += 256) s_hist[b] = 0u;
@@ -141,7 +161,7 @@ __global__ __launch_bounds__(256) void rpn_label_kernel(int variant, const float
     if (i < N) {
         const float4 a = anchors[i];
         float4 reg = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (variant == 1 || anchor_inside(a)) {
+        if (G > 0 && (variant == 1 || anchor_inside(a))) {
             int arg;
             lab = rpn_label_anchor<false>(variant, a, i, gt, G, colkey, &arg);
             reg = encode4(xy_to_cxcy4(gt[arg]), xy_to_cxcy4(a));
@@ -270,6 +290,7 @@ __global__ __launch_bounds__(1024) void rpn_sample_kernel(int N, const int8_t *_
 {
     __shared__ int s_w[17];
     const int n_pos = counts[0], n_neg = counts[1];
+    const int gbit = counts[2] & GT_COUNT_ERR;              // rpn_label_kernel's report of the GT count stays beside the sampler's own codes
     const int np_eff = min(n_pos, 128);
     const bool drop_pos = n_pos > 128;
     const bool drop_neg = n_neg > 256 - n_pos;
@@ -288,7 +309,7 @@ __global__ __launch_bounds__(1024) void rpn_sample_kernel(int N, const int8_t *_
         if (n_c == 0 && n_perm == 0) continue;              // nothing to demote (n_pos > 256 makes `n_neg > 256 - n_pos` true for n_neg = 0:
                                                             // the reference draws randperm(0) there); a zero-length permutation needs no pointer
         if (perm == nullptr || n_perm != n_c) {             // uniform
-            if (threadIdx.x == 0) counts[2] = 1;
+            if (threadIdx.x == 0) counts[2] = 1 | gbit;
             continue;
         }
         // ordered compaction (ascending index): contiguous ownership + block scan
@@ -302,7 +323,7 @@ __global__ __launch_bounds__(1024) void rpn_sample_kernel(int N, const int8_t *_
         for (int j = keep + threadIdx.x; j < n_c; j += 1024) {
             const int64_t p = perm[j];
             if (p >= 0 && p < n_c) { const int i = list[p]; out_cls[i] = -1; }
-            else counts[2] = 2;
+            else counts[2] = 2 | gbit;
         }
         __syncthreads();
         // label8 is stale for the demoted entries from here on; the negative pass only looks at label 0
@@ -454,7 +475,7 @@ __device__ __forceinline__ void rpn_apply_resolve(RpnCut cn, RpnCut cp, RpnSel2 
         if (!ct.drop) continue;                                      // uniform
         const int m_raw = (int)agent_ld(&sel->nb[c]);
         const int m = min(m_raw, RPN_BL_CAP);
-        if (m_raw > RPN_BL_CAP && threadIdx.x == 0) counts[2] = 8;   // cannot happen below ~8 M anchors (the entry point's limit)
+        if (m_raw > RPN_BL_CAP && threadIdx.x == 0) counts[2] |= 8;  // cannot happen below ~8 M anchors (the entry point's limit)
         __syncthreads();
         for (int q = threadIdx.x; q < m; q += blockDim.x) s_e[q] = agent_ld(&bl->e[c][q]);
         __syncthreads();
@@ -471,7 +492,8 @@ __device__ __forceinline__ void rpn_apply_resolve(RpnCut cn, RpnCut cp, RpnSel2 
 }
 
 template <bool INLINE>
-__global__ __launch_bounds__(1024) void rpn_match_kernel(int variant, const float4 *__restrict__ anchors, int N, const float4 *__restrict__ gt, int G,
+__global__ __launch_bounds__(1024) void rpn_match_kernel(int variant, const float4 *__restrict__ anchors, int N, const float4 *__restrict__ gt, int G_cap,
+                                                         const int32_t *__restrict__ n_gt_dev,
                                                          unsigned long long *__restrict__ colkey, RpnCtl *__restrict__ ctl, RpnSel2 *__restrict__ sel,
                                                          RpnBList *__restrict__ bl,
                                                          unsigned long long seed, unsigned long long offset, unsigned long long *__restrict__ philox_state,
@@ -487,6 +509,8 @@ __global__ __launch_bounds__(1024) void rpn_match_kernel(int variant, const floa
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i = blockIdx.x * 1024 + tid;
     const int nb = (int)gridDim.x;
+    int gerr;
+    const int G = live_gt_count(n_gt_dev, G_cap, &gerr);
     RPN_T(blockIdx.x == 0 && tid == 0, 0);
     if (philox_state && blockIdx.x == 0 && tid == 0) {              // this call's (seed, offset); the stream moves on (frcnn_hip.h)
         const unsigned long long sd = philox_state[0], of = philox_state[1];
@@ -497,7 +521,7 @@ __global__ __launch_bounds__(1024) void rpn_match_kernel(int variant, const floa
     for (int b = tid; b < 2 * RSB; b += 1024) (&s_hist[0][0])[b] = 0u;
     float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
     bool live = false;
-    if (i < N) { a = anchors[i]; live = variant == 1 || anchor_inside(a); }
+    if (i < N) { a = anchors[i]; live = G > 0 && (variant == 1 || anchor_inside(a)); }
     // ---- (1) column maxima, 64 GT boxes per round
     const bool any_live = __syncthreads_or(live) != 0;
     if (any_live) {
@@ -595,7 +619,7 @@ __global__ __launch_bounds__(1024) void rpn_match_kernel(int variant, const floa
     const int n_neg = agent_ld(&ctl->n_neg);
     __syncthreads();
     if (tid == 0) {
-        counts[0] = n_pos; counts[1] = n_neg; counts[2] = 0; counts[3] = 0;
+        counts[0] = n_pos; counts[1] = n_neg; counts[2] = gerr; counts[3] = 0;
         agent_st(&ctl->n_pos, 0); agent_st(&ctl->n_neg, 0);
         agent_st(&ctl->flag[0], 0);
     }
@@ -646,7 +670,8 @@ __global__ __launch_bounds__(1024) void rpn_apply_kernel(int N, const int8_t *__
 #define HT_ROWS_MAX 1024
 
 __global__ __launch_bounds__(1024) void head_targets_kernel(int variant, const float4 *__restrict__ rois, const int32_t *__restrict__ n_rois_dev,
-                                                            int P_cap, const float4 *__restrict__ gt, const int64_t *__restrict__ gt_label, int G,
+                                                            int P_cap, const float4 *__restrict__ gt, const int64_t *__restrict__ gt_label, int G_cap,
+                                                            const int32_t *__restrict__ n_gt_dev,
                                                             int label_offset, int max_pos, int total,
                                                             const int64_t *__restrict__ perm_pos, int n_perm_pos,
                                                             const int64_t *__restrict__ perm_neg, int n_perm_neg,
@@ -654,7 +679,7 @@ __global__ __launch_bounds__(1024) void head_targets_kernel(int variant, const f
                                                             unsigned long long *__restrict__ philox_state,
                                                             int64_t *__restrict__ out_cls, float4 *__restrict__ out_reg,
                                                             float4 *__restrict__ out_rois, int64_t *__restrict__ out_keep,
-                                                            int32_t *__restrict__ counts, int32_t *__restrict__ sticky)
+                                                            int32_t *__restrict__ counts, int32_t *__restrict__ sticky, int32_t *__restrict__ empty_dev)
 {
     if (philox_state) { seed = philox_state[0]; offset = philox_state[1]; }   // every thread reads it here; thread 0 moves it on at the end
     __shared__ int s_w[17];
@@ -677,6 +702,10 @@ __global__ __launch_bounds__(1024) void head_targets_kernel(int variant, const f
     const int n_rois_raw = n_rois_dev ? *n_rois_dev : P_cap;
     const bool upstream_abort = n_rois_raw < 0;
     const int n_rois = min(max(n_rois_raw, 0), P_cap);
+    // G == 0 (a frame whose boxes a crop removed; the reference throws): no candidate matches anything, so no row can be sampled and
+    // every row is marked as FRCNN_HT_ERR_SHORT rows are
+    int gerr;
+    const int G = live_gt_count(n_gt_dev, G_cap, &gerr);
     const int n = n_rois + G;
 
     RPN_T(tid == 0, 8);
@@ -838,6 +867,8 @@ __global__ __launch_bounds__(1024) void head_targets_kernel(int variant, const f
         int err = s_err;                                            // FRCNN_HT_ERR_* bits (include/frcnn_hip.h)
         if (upstream_abort) err |= FRCNN_HT_ERR_UPSTREAM_ABORT;
         if (n_pos + n_neg < total) err |= FRCNN_HT_ERR_SHORT;
+        err |= gerr;
+        if (empty_dev) *empty_dev = G <= 0 ? 1 : 0;                  // this call's frame only (not sticky): DeviceSGD's guard word
         counts[0] = npc; counts[1] = nnc; counts[2] = (err & 3) ? 0 : n_pos + n_neg; counts[3] = err;
         if (sticky && err) atomicOr(sticky, err);
         if (philox_state) philox_state[1] = offset + 1ull;           // one offset value consumed per call (barriers lie between the reads and this)
@@ -871,10 +902,12 @@ static RpnWs carve_rpn(void *ws, int64_t N, int64_t G)
 size_t frcnn_ws_rpn_targets(int64_t N, int64_t G) { return carve_rpn(nullptr, N, G).total; }
 size_t frcnn_ws_head_targets(int64_t) { return 256; }
 
-FRCNN_EXPORT int frcnn_rpn_targets(int variant, const float *anchors, int64_t N, const float *gt, int64_t G,
-                                   const int64_t *perm_pos, int64_t n_perm_pos, const int64_t *perm_neg, int64_t n_perm_neg,
-                                   uint64_t seed, uint64_t offset, uint64_t *philox_state_dev, int64_t *out_cls, float *out_reg, int32_t *out_counts,
-                                   void *workspace, size_t workspace_bytes, void *stream)
+// G = the capacity of gt: everything the host decides (limits, the workspace carve, the staged form's memset) goes by it; the kernels
+// take the live count from n_gt_dev when it is given (live_gt_count)
+FRCNN_EXPORT int frcnn_rpn_targets_n(int variant, const float *anchors, int64_t N, const float *gt, int64_t G, const int32_t *n_gt_dev,
+                                     const int64_t *perm_pos, int64_t n_perm_pos, const int64_t *perm_neg, int64_t n_perm_neg,
+                                     uint64_t seed, uint64_t offset, uint64_t *philox_state_dev, int64_t *out_cls, float *out_reg, int32_t *out_counts,
+                                     void *workspace, size_t workspace_bytes, void *stream)
 {
     FRCNN_REQUIRE(variant == 0 || variant == 1, "rpn_targets: variant must be 0 (VGG) or 1 (FPN)");
     FRCNN_REQUIRE(N > 0 && N < ((int64_t)1 << 31), "rpn_targets: bad N");
@@ -899,11 +932,11 @@ FRCNN_EXPORT int frcnn_rpn_targets(int variant, const float *anchors, int64_t N,
     if (device_rng && !no_fuse && nb1024 <= 2 * n_cus) {
         const bool inl = N <= RS_LDS_MAX;                               // the last workgroup finishes the sampling itself
         if (inl)
-            FRCNN_LAUNCH(rpn_match_kernel<true>, dim3((unsigned)nb1024), dim3(1024), 0, s, variant, (const float4 *)anchors, (int)N, (const float4 *)gt, (int)G,
+            FRCNN_LAUNCH(rpn_match_kernel<true>, dim3((unsigned)nb1024), dim3(1024), 0, s, variant, (const float4 *)anchors, (int)N, (const float4 *)gt, (int)G, n_gt_dev,
                          w.colkey, w.ctl, w.sel2, w.bl, (unsigned long long)seed, (unsigned long long)offset, (unsigned long long *)philox_state_dev, out_cls,
                          (float4 *)out_reg, w.label8, w.keys, out_counts);
         else
-            FRCNN_LAUNCH(rpn_match_kernel<false>, dim3((unsigned)nb1024), dim3(1024), 0, s, variant, (const float4 *)anchors, (int)N, (const float4 *)gt, (int)G,
+            FRCNN_LAUNCH(rpn_match_kernel<false>, dim3((unsigned)nb1024), dim3(1024), 0, s, variant, (const float4 *)anchors, (int)N, (const float4 *)gt, (int)G, n_gt_dev,
                          w.colkey, w.ctl, w.sel2, w.bl, (unsigned long long)seed, (unsigned long long)offset, (unsigned long long *)philox_state_dev, out_cls,
                          (float4 *)out_reg, w.label8, w.keys, out_counts);
         FRCNN_CHECK_LAUNCH("rpn_match_kernel");
@@ -916,10 +949,10 @@ FRCNN_EXPORT int frcnn_rpn_targets(int variant, const float *anchors, int64_t N,
     if (hipMemsetAsync(w.colkey2, 0, (size_t)G * 8 * 8, s) != hipSuccess) return frcnn_set_error(FRCNN_ERR_LAUNCH, "rpn_targets: memset failed");
     const dim3 grid((unsigned)((N + 255) / 256)), block(256);
     FRCNN_LAUNCH(rpn_colmax_kernel, grid, block, 0, s, variant, (const float4 *)anchors, (int)N, (const float4 *)gt,
-                 (int)G, w.colkey2, out_counts, (unsigned long long *)philox_state_dev, w.snap);
+                 (int)G, n_gt_dev, w.colkey2, out_counts, (unsigned long long *)philox_state_dev, w.snap);
     FRCNN_CHECK_LAUNCH("rpn_colmax_kernel");
     if (device_rng) {
-        FRCNN_LAUNCH(rpn_label_kernel<true>, grid, block, 0, s, variant, (const float4 *)anchors, (int)N, (const float4 *)gt, (int)G, w.colkey2,
+        FRCNN_LAUNCH(rpn_label_kernel<true>, grid, block, 0, s, variant, (const float4 *)anchors, (int)N, (const float4 *)gt, (int)G, n_gt_dev, w.colkey2,
                      (unsigned long long)seed, (unsigned long long)offset, philox_state_dev ? w.snap : nullptr, out_cls, (float4 *)out_reg, w.label8, w.keys,
                      w.sel2, out_counts);
         FRCNN_CHECK_LAUNCH("rpn_label_kernel");
@@ -927,7 +960,7 @@ FRCNN_EXPORT int frcnn_rpn_targets(int variant, const float *anchors, int64_t N,
         FRCNN_CHECK_LAUNCH("rpn_apply_kernel");
         return FRCNN_OK;
     }
-    FRCNN_LAUNCH(rpn_label_kernel<false>, grid, block, 0, s, variant, (const float4 *)anchors, (int)N, (const float4 *)gt, (int)G, w.colkey2,
+    FRCNN_LAUNCH(rpn_label_kernel<false>, grid, block, 0, s, variant, (const float4 *)anchors, (int)N, (const float4 *)gt, (int)G, n_gt_dev, w.colkey2,
                  0ull, 0ull, nullptr, out_cls, (float4 *)out_reg, w.label8, nullptr, nullptr, out_counts);
     FRCNN_CHECK_LAUNCH("rpn_label_kernel");
     FRCNN_LAUNCH(rpn_sample_kernel, dim3(1), dim3(1024), 0, s, (int)N, w.label8, out_cls, perm_pos, (int)n_perm_pos, perm_neg,
@@ -936,11 +969,20 @@ FRCNN_EXPORT int frcnn_rpn_targets(int variant, const float *anchors, int64_t N,
     return FRCNN_OK;
 }
 
-FRCNN_EXPORT int frcnn_head_targets(int variant, const float *rois, const int32_t *n_rois_dev, int64_t P_cap, const float *gt,
-                                    const int64_t *gt_label, int64_t G, int64_t label_offset, int64_t max_pos, int64_t total,
-                                    const int64_t *perm_pos, int64_t n_perm_pos, const int64_t *perm_neg, int64_t n_perm_neg,
-                                    uint64_t seed, uint64_t offset, uint64_t *philox_state_dev, int64_t *out_cls, float *out_reg, float *out_rois,
-                                    int64_t *out_keep_index, int32_t *out_counts, int32_t *sticky_status, void *stream)
+FRCNN_EXPORT int frcnn_rpn_targets(int variant, const float *anchors, int64_t N, const float *gt, int64_t G,
+                                   const int64_t *perm_pos, int64_t n_perm_pos, const int64_t *perm_neg, int64_t n_perm_neg,
+                                   uint64_t seed, uint64_t offset, uint64_t *philox_state_dev, int64_t *out_cls, float *out_reg, int32_t *out_counts,
+                                   void *workspace, size_t workspace_bytes, void *stream)
+{
+    return frcnn_rpn_targets_n(variant, anchors, N, gt, G, nullptr, perm_pos, n_perm_pos, perm_neg, n_perm_neg, seed, offset, philox_state_dev,
+                               out_cls, out_reg, out_counts, workspace, workspace_bytes, stream);
+}
+
+FRCNN_EXPORT int frcnn_head_targets_n(int variant, const float *rois, const int32_t *n_rois_dev, int64_t P_cap, const float *gt,
+                                      const int64_t *gt_label, int64_t G, const int32_t *n_gt_dev, int64_t label_offset, int64_t max_pos, int64_t total,
+                                      const int64_t *perm_pos, int64_t n_perm_pos, const int64_t *perm_neg, int64_t n_perm_neg,
+                                      uint64_t seed, uint64_t offset, uint64_t *philox_state_dev, int64_t *out_cls, float *out_reg, float *out_rois,
+                                      int64_t *out_keep_index, int32_t *out_counts, int32_t *sticky_status, int32_t *empty_dev, void *stream)
 {
     FRCNN_REQUIRE(variant == 0 || variant == 1, "head_targets: variant must be 0 (VGG) or 1 (FPN)");
     FRCNN_REQUIRE(P_cap >= 0 && G > 0, "head_targets: need P_cap >= 0 and G >= 1");
@@ -950,9 +992,20 @@ FRCNN_EXPORT int frcnn_head_targets(int variant, const float *rois, const int32_
     FRCNN_REQUIRE(n_perm_pos >= 0 && n_perm_neg >= 0, "head_targets: bad perm length");
     hipStream_t s = (hipStream_t)stream;
     FRCNN_LAUNCH(head_targets_kernel, dim3(1), dim3(1024), 0, s, variant, (const float4 *)rois, n_rois_dev, (int)P_cap,
-                 (const float4 *)gt, gt_label, (int)G, (int)label_offset, (int)max_pos, (int)total, perm_pos, (int)n_perm_pos, perm_neg,
+                 (const float4 *)gt, gt_label, (int)G, n_gt_dev, (int)label_offset, (int)max_pos, (int)total, perm_pos, (int)n_perm_pos, perm_neg,
                  (int)n_perm_neg, (unsigned long long)seed, (unsigned long long)offset, (unsigned long long *)philox_state_dev, out_cls, (float4 *)out_reg, (float4 *)out_rois,
-                 out_keep_index, out_counts, sticky_status);
+                 out_keep_index, out_counts, sticky_status, empty_dev);
     FRCNN_CHECK_LAUNCH("head_targets_kernel");
     return FRCNN_OK;
+}
+
+FRCNN_EXPORT int frcnn_head_targets(int variant, const float *rois, const int32_t *n_rois_dev, int64_t P_cap, const float *gt,
+                                    const int64_t *gt_label, int64_t G, int64_t label_offset, int64_t max_pos, int64_t total,
+                                    const int64_t *perm_pos, int64_t n_perm_pos, const int64_t *perm_neg, int64_t n_perm_neg,
+                                    uint64_t seed, uint64_t offset, uint64_t *philox_state_dev, int64_t *out_cls, float *out_reg, float *out_rois,
+                                    int64_t *out_keep_index, int32_t *out_counts, int32_t *sticky_status, void *stream)
+{
+    return frcnn_head_targets_n(variant, rois, n_rois_dev, P_cap, gt, gt_label, G, nullptr, label_offset, max_pos, total, perm_pos, n_perm_pos,
+                                perm_neg, n_perm_neg, seed, offset, philox_state_dev, out_cls, out_reg, out_rois, out_keep_index, out_counts,
+                                sticky_status, nullptr, stream);
 }

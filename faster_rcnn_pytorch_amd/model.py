@@ -208,20 +208,22 @@ class FastRcnnTargetMaker(nn.Module):
         super().__init__()
         self.sampler = sampler or _Sampler()
 
-    def forward(self, bbox, label, rois, n_rois=None):
+    def forward(self, bbox, label, rois, n_rois=None, n_gt=None, empty=None):
+        """n_gt (device int32): bbox / label are fixed-capacity lists with n_gt live rows (ops.head_targets); empty: see there."""
         bbox = _unwrap(bbox)
         label = _unwrap(label).to(torch.int64)
         s = self.sampler
         if s.sampling == "host":
-            c = ops.head_targets(rois, bbox, label, n_rois=n_rois)[4].cpu().tolist()     # learn the candidate counts
+            c = ops.head_targets(rois, bbox, label, n_rois=n_rois, n_gt=n_gt)[4].cpu().tolist()     # learn the candidate counts
             perm_pos = torch.randperm(c[0])                                                # model_.py:149
             perm_neg = torch.randperm(c[1])                                                # model_.py:155
-            cls, reg, srois, _, counts = ops.head_targets(rois, bbox, label, n_rois=n_rois, perm_pos=perm_pos, perm_neg=perm_neg)
+            cls, reg, srois, _, counts = ops.head_targets(rois, bbox, label, n_rois=n_rois, perm_pos=perm_pos, perm_neg=perm_neg, n_gt=n_gt,
+                                                          empty=empty)
             if counts.cpu().tolist()[2] != 128:
                 raise RuntimeError("FastRcnnTargetMaker: fewer than 128 samples (the reference fails here too, model_.py:340)")
         else:
             cls, reg, srois, _, _ = ops.head_targets(rois, bbox, label, n_rois=n_rois, philox_state=s.state(rois.device),
-                                                     status=s.status.word(rois.device))
+                                                     status=s.status.word(rois.device), n_gt=n_gt, empty=empty)
         return cls, reg, srois
 
 
@@ -232,18 +234,22 @@ class RPNTargetMaker(nn.Module):
         super().__init__()
         self.sampler = sampler or _Sampler()
 
-    def forward(self, bbox, anchor):
+    def forward(self, bbox, anchor, n_gt=None):
+        """n_gt (device int32): bbox is a fixed-capacity list with n_gt live rows (ops.rpn_targets)."""
         bbox = _unwrap(bbox)
         s = self.sampler
         if s.sampling == "host":
-            n_pos, n_neg = ops.rpn_targets(anchor, bbox)[2].cpu().tolist()[:2]
+            n_pos, n_neg = ops.rpn_targets(anchor, bbox, n_gt=n_gt)[2].cpu().tolist()[:2]
             perm_pos = torch.randperm(n_pos) if n_pos > 128 else None                      # model_.py:225-229
             perm_neg = torch.randperm(n_neg) if n_neg > 256 - n_pos else None              # model_.py:231-236
-            cls, reg, counts = ops.rpn_targets(anchor, bbox, perm_pos=perm_pos, perm_neg=perm_neg)
-            if counts.cpu().tolist()[2] != 0:
+            cls, reg, counts = ops.rpn_targets(anchor, bbox, perm_pos=perm_pos, perm_neg=perm_neg, n_gt=n_gt)
+            err = counts.cpu().tolist()[2]
+            if err & ~ops._lib.RPN_ERR_GT_COUNT:
                 raise RuntimeError("RPNTargetMaker: permutation length mismatch")
+            if err:
+                raise RuntimeError("RPNTargetMaker: n_gt outside [1, %d]" % bbox.shape[0])
         else:
-            cls, reg, _ = ops.rpn_targets(anchor, bbox, philox_state=s.state(anchor.device))
+            cls, reg, _ = ops.rpn_targets(anchor, bbox, philox_state=s.state(anchor.device), n_gt=n_gt)
         return cls, reg
 
 
@@ -282,14 +288,17 @@ class FRCNN(nn.Module):
         gradient first, and its all-reduce runs under the backward of the rest."""
         return {"cut_module": self.fast_rcnn_head.roi_pool, "late_modules": (self.classifier, self.fast_rcnn_head.cls_head, self.fast_rcnn_head.reg_head)}
 
-    def forward(self, x, bbox, label):
+    def forward(self, x, bbox, label, n_gt=None, empty=None):
+        """n_gt (device int32[1]): bbox / label come as fixed-capacity lists straight from the device input stage, rows at and above
+        n_gt are padding; the target makers read the count on the device, so nothing about the number of boxes is frozen into a captured
+        step (parallel.FrameSlot).  empty (device int32[1]): set to 1 by a frame without boxes, else 0 -- DeviceSGD's guard= tensor."""
         hw = x.size()[2:]
         # 5. rpn targets depend only on the anchors and the ground truth (model.py:324), not on the network: they are enqueued first.
         #    (Round 1 ran them on a second HIP stream "underneath" the backbone.  Measured A/B on one box, four runs: the fork / join
         #    and the single-workgroup sampler competing with MIOpen's kernels cost more than the 48 us they hide: 14.77-14.80 ms per step
         #    with the side stream, 14.63-14.67 ms without; the same experiment in the FPN mirror: 18.64 vs 18.17 ms.)
         anchor = self.anchor_maker.device_anchors(hw, x.device)           # model.py:310-312: resident in HBM
-        target_rpn_cls, target_rpn_reg = self.rpn_target_maker(bbox=bbox, anchor=anchor)
+        target_rpn_cls, target_rpn_reg = self.rpn_target_maker(bbox=bbox, anchor=anchor, n_gt=n_gt)
         # 1. extract features                                                  model.py:307
         features = self.extractor(x)
         # 3. forward rpn                                                       model.py:315
@@ -300,7 +309,7 @@ class FRCNN(nn.Module):
         self.last_proposal_count = n_rois                                     # device int32[1]: how many proposals survived NMS (<= 2000)
         # 6. fast rcnn targets                                                 model.py:328
         target_fast_rcnn_cls, target_fast_rcnn_reg, sample_rois = self.fast_rcnn_target_maker(bbox=bbox, label=label, rois=rois,
-                                                                                              n_rois=n_rois)
+                                                                                              n_rois=n_rois, n_gt=n_gt, empty=empty)
         # 7. fast rcnn head                                                    model.py:335
         pred_fast_rcnn_cls, pred_fast_rcnn_reg = self.fast_rcnn_head(features, sample_rois)
         # 8. regression row of the target class                                model.py:340-341

@@ -369,20 +369,21 @@ class FRCNNTargetMaker(nn.Module):
         super().__init__()
         self.sampler = sampler or _Sampler()
 
-    def forward(self, boxes, labels, rois, n_rois=None):
+    def forward(self, boxes, labels, rois, n_rois=None, n_gt=None, empty=None):
+        """n_gt (device int32): boxes / labels are fixed-capacity lists with n_gt live rows (ops.head_targets); empty: see there."""
         boxes = _unwrap(boxes)
         labels = _unwrap(labels).to(torch.int64)
         s = self.sampler
-        kw = dict(n_rois=n_rois, variant=1, label_offset=0, max_pos=128, total=512)
+        kw = dict(n_rois=n_rois, variant=1, label_offset=0, max_pos=128, total=512, n_gt=n_gt)
         if s.sampling == "host":
             c = ops.head_targets(rois, boxes, labels, **kw)[4].cpu().tolist()
             perm_pos, perm_neg = torch.randperm(c[0]), torch.randperm(c[1])        # new_model.py:175,180
-            cls, reg, srois, _, counts = ops.head_targets(rois, boxes, labels, perm_pos=perm_pos, perm_neg=perm_neg, **kw)
+            cls, reg, srois, _, counts = ops.head_targets(rois, boxes, labels, perm_pos=perm_pos, perm_neg=perm_neg, empty=empty, **kw)
             if counts.cpu().tolist()[2] != 512:
                 raise RuntimeError("FRCNNTargetMaker: fewer than 512 samples (assert at new_model.py:183)")
         else:
             cls, reg, srois, _, _ = ops.head_targets(rois, boxes, labels, philox_state=s.state(rois.device),
-                                                     status=s.status.word(rois.device), **kw)
+                                                     status=s.status.word(rois.device), empty=empty, **kw)
         return cls, reg, srois
 
 
@@ -393,18 +394,22 @@ class RPNTargetMaker(nn.Module):
         super().__init__()
         self.sampler = sampler or _Sampler()
 
-    def forward(self, boxes, anchors):
+    def forward(self, boxes, anchors, n_gt=None):
+        """n_gt (device int32): boxes is a fixed-capacity list with n_gt live rows (ops.rpn_targets)."""
         boxes = _unwrap(boxes)
         s = self.sampler
         if s.sampling == "host":
-            n_pos, n_neg = ops.rpn_targets(anchors, boxes, variant=1)[2].cpu().tolist()[:2]
+            n_pos, n_neg = ops.rpn_targets(anchors, boxes, variant=1, n_gt=n_gt)[2].cpu().tolist()[:2]
             perm_pos = torch.randperm(n_pos) if n_pos > 128 else None
             perm_neg = torch.randperm(n_neg) if n_neg > 256 - n_pos else None
-            cls, reg, counts = ops.rpn_targets(anchors, boxes, variant=1, perm_pos=perm_pos, perm_neg=perm_neg)
-            if counts.cpu().tolist()[2] != 0:
+            cls, reg, counts = ops.rpn_targets(anchors, boxes, variant=1, perm_pos=perm_pos, perm_neg=perm_neg, n_gt=n_gt)
+            err = counts.cpu().tolist()[2]
+            if err & ~ops._lib.RPN_ERR_GT_COUNT:
                 raise RuntimeError("RPNTargetMaker: permutation length mismatch")
+            if err:
+                raise RuntimeError("RPNTargetMaker: n_gt outside [1, %d]" % boxes.shape[0])
         else:
-            cls, reg, _ = ops.rpn_targets(anchors, boxes, variant=1, philox_state=s.state(anchors.device))
+            cls, reg, _ = ops.rpn_targets(anchors, boxes, variant=1, philox_state=s.state(anchors.device), n_gt=n_gt)
         return cls, reg
 
 
@@ -436,13 +441,14 @@ class FRCNN(nn.Module):
         """Where parallel.GraphStep cuts the backward (see models.model.FRCNN.graph_stages): behind the multi-scale RoIAlign."""
         return {"cut_module": self.frcnn_head.roi_pool, "late_modules": (self.classifier, self.frcnn_head.cls_head, self.frcnn_head.reg_head)}
 
-    def forward(self, x, boxes, labels):
+    def forward(self, x, boxes, labels, n_gt=None, empty=None):
+        """n_gt / empty (device int32[1]): as models.model.FRCNN.forward -- boxes / labels are fixed-capacity lists with n_gt live rows."""
         features = self.backbone(x)                                                # new_model.py:394
         pred_rpn_cls, pred_rpn_reg, rois, n_rois, anchors = self.rpn.propose(x, features, "train")
         self.last_proposal_count = n_rois                                          # device int32[1]: proposals that survived NMS (<= 1000)
-        target_rpn_cls, target_rpn_reg = self.rpn_target_maker(boxes=boxes, anchors=anchors)
+        target_rpn_cls, target_rpn_reg = self.rpn_target_maker(boxes=boxes, anchors=anchors, n_gt=n_gt)
         target_fast_rcnn_cls, target_fast_rcnn_reg, sample_rois = self.frcnn_target_maker(boxes=boxes, labels=labels, rois=rois,
-                                                                                          n_rois=n_rois)
+                                                                                          n_rois=n_rois, n_gt=n_gt, empty=empty)
         pred_fast_rcnn_cls, pred_fast_rcnn_reg = self.frcnn_head(features, sample_rois, x.shape[2:])
         pred_fast_rcnn_reg = pred_fast_rcnn_reg.reshape(512, -1, 4)
         # row i keeps the regression of its target class (reference: pred[arange(512), cls], advanced indexing).  torch.gather selects the

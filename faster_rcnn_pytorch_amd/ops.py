@@ -1495,7 +1495,8 @@ def describe_status(bits):
     """Names of the _lib.HT_ERR_* bits set in a status word."""
     names = ((_lib.HT_ERR_PERM_LENGTH, "permutation length mismatch"), (_lib.HT_ERR_PERM_RANGE, "permutation entry out of range"),
              (_lib.HT_ERR_UPSTREAM_ABORT, "the proposal stage reported an aborted NMS scan (count < 0)"),
-             (_lib.HT_ERR_SHORT, "fewer RoI samples than requested (the reference throws here)"))
+             (_lib.HT_ERR_SHORT, "fewer RoI samples than requested (the reference throws here)"),
+             (_lib.HT_ERR_GT_COUNT, "the device count of ground-truth boxes was outside [1, capacity]"))
     return [n for b, n in names if bits & b]
 
 
@@ -1544,9 +1545,21 @@ def _philox(state):
     return _req(state, torch.int64, "philox_state")
 
 
-def rpn_targets(anchors, gt, variant=0, perm_pos=None, perm_neg=None, seed=0, offset=0, philox_state=None):
+def _n_gt(n_gt):
+    if n_gt is None:
+        return None
+    n_gt = _req(n_gt, torch.int32, "n_gt")
+    if n_gt.numel() < 1:
+        raise ValueError("n_gt: need a device int32 tensor with at least one element")
+    return n_gt
+
+
+def rpn_targets(anchors, gt, variant=0, perm_pos=None, perm_neg=None, seed=0, offset=0, philox_state=None, n_gt=None):
     """RPNTargetMaker.forward.  Returns (cls[N] i64, reg[N,4], counts int32[4] device = n_pos, n_neg, err, -).
-    philox_state (int64[2] on the device, see ops.philox_state) overrides (seed, offset) and is advanced by the call."""
+    philox_state (int64[2] on the device, see ops.philox_state) overrides (seed, offset) and is advanced by the call.
+    n_gt (device int32, first element): gt is a fixed-capacity list whose first n_gt rows are live; the count is read on the device
+    (no sync, nothing frozen into a captured graph) and the result is that of the call on gt[:n_gt].  A count outside
+    [1, gt.shape[0]] raises _lib.RPN_ERR_GT_COUNT in counts[2] (include/frcnn_hip.h: frcnn_rpn_targets_n)."""
     anchors = _req(anchors, name="anchors").reshape(-1, 4)
     gt = _req(gt, name="gt").reshape(-1, 4)
     N, G = anchors.shape[0], gt.shape[0]
@@ -1558,16 +1571,23 @@ def rpn_targets(anchors, gt, variant=0, perm_pos=None, perm_neg=None, seed=0, of
     pn, npn = _perm(perm_neg, dev)
     nb = _lib.workspace_bytes(_lib.OP_RPN_TARGETS, N, G)
     ws = _ctrl_workspace(dev, "rpn_targets", nb)          # holds the fused kernel's barrier / ticket words: zero on first use, left zero by every call
+    n_gt = _n_gt(n_gt)
     with torch.cuda.device(dev):
-        check(lib.frcnn_rpn_targets(int(variant), _ptr(anchors), N, _ptr(gt), G, _ptr(pp), npp, _ptr(pn), npn, int(seed), int(offset),
-                                    _ptr(_philox(philox_state)), _ptr(cls), _ptr(reg), _ptr(counts), _ptr(ws), ws.numel(), _stream()), "rpn_targets")
+        if n_gt is None:
+            check(lib.frcnn_rpn_targets(int(variant), _ptr(anchors), N, _ptr(gt), G, _ptr(pp), npp, _ptr(pn), npn, int(seed), int(offset),
+                                        _ptr(_philox(philox_state)), _ptr(cls), _ptr(reg), _ptr(counts), _ptr(ws), ws.numel(), _stream()), "rpn_targets")
+        else:
+            check(lib.frcnn_rpn_targets_n(int(variant), _ptr(anchors), N, _ptr(gt), G, _ptr(n_gt), _ptr(pp), npp, _ptr(pn), npn, int(seed), int(offset),
+                                          _ptr(_philox(philox_state)), _ptr(cls), _ptr(reg), _ptr(counts), _ptr(ws), ws.numel(), _stream()), "rpn_targets")
     return cls, reg, counts
 
 
 def head_targets(rois, gt, gt_label, n_rois=None, variant=0, label_offset=1, max_pos=32, total=128,
-                 perm_pos=None, perm_neg=None, seed=0, offset=0, want_keep=False, status=None, philox_state=None):
+                 perm_pos=None, perm_neg=None, seed=0, offset=0, want_keep=False, status=None, philox_state=None, n_gt=None, empty=None):
     """FastRcnnTargetMaker.forward.  Returns (cls[total] i64, reg[total,4], sample_rois[total,4], keep|None, counts int32[4]).
-    counts[3] holds the _lib.HT_ERR_* bits; they are also OR-ed into `status` (device int32[1], sticky across steps) if given."""
+    counts[3] holds the _lib.HT_ERR_* bits; they are also OR-ed into `status` (device int32[1], sticky across steps) if given.
+    n_gt (device int32, first element): the first n_gt rows of gt / gt_label are live, as in rpn_targets.  empty (device int32[1], needs
+    n_gt) is written by every call: 1 when n_gt <= 0, else 0 -- the guard= tensor of optim.DeviceSGD."""
     rois = _req(rois, name="rois").reshape(-1, 4)
     gt = _req(gt, name="gt").reshape(-1, 4)
     gt_label = _req(gt_label, torch.int64, "gt_label").reshape(-1)
@@ -1583,11 +1603,25 @@ def head_targets(rois, gt, gt_label, n_rois=None, variant=0, label_offset=1, max
     pn, npn = _perm(perm_neg, dev)
     if status is not None:
         status = _req(status, torch.int32, "status")
+    n_gt = _n_gt(n_gt)
+    if empty is not None:
+        if n_gt is None:
+            raise ValueError("head_targets: empty= goes with n_gt= (without a device count the frame is never empty)")
+        empty = _req(empty, torch.int32, "empty")
+    if n_gt is not None and gt_label.shape[0] != gt.shape[0]:
+        raise ValueError("head_targets: %d labels for %d boxes" % (gt_label.shape[0], gt.shape[0]))
     with torch.cuda.device(dev):
-        check(lib.frcnn_head_targets(int(variant), _ptr(rois), _ptr(n_rois), rois.shape[0], _ptr(gt), _ptr(gt_label), gt.shape[0],
-                                     int(label_offset), int(max_pos), int(total), _ptr(pp), npp, _ptr(pn), npn, int(seed), int(offset),
-                                     _ptr(_philox(philox_state)), _ptr(cls), _ptr(reg), _ptr(srois), _ptr(keep), _ptr(counts), _ptr(status), _stream()),
-              "head_targets")
+        if n_gt is None:
+            check(lib.frcnn_head_targets(int(variant), _ptr(rois), _ptr(n_rois), rois.shape[0], _ptr(gt), _ptr(gt_label), gt.shape[0],
+                                         int(label_offset), int(max_pos), int(total), _ptr(pp), npp, _ptr(pn), npn, int(seed), int(offset),
+                                         _ptr(_philox(philox_state)), _ptr(cls), _ptr(reg), _ptr(srois), _ptr(keep), _ptr(counts), _ptr(status), _stream()),
+                  "head_targets")
+        else:
+            check(lib.frcnn_head_targets_n(int(variant), _ptr(rois), _ptr(n_rois), rois.shape[0], _ptr(gt), _ptr(gt_label), gt.shape[0], _ptr(n_gt),
+                                           int(label_offset), int(max_pos), int(total), _ptr(pp), npp, _ptr(pn), npn, int(seed), int(offset),
+                                           _ptr(_philox(philox_state)), _ptr(cls), _ptr(reg), _ptr(srois), _ptr(keep), _ptr(counts), _ptr(status),
+                                           _ptr(empty), _stream()),
+                  "head_targets")
     return cls, reg, srois, keep, counts
 
 

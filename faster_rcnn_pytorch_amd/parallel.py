@@ -118,6 +118,86 @@ def barrier():
         dist.barrier()
 
 
+class FrameSlot(object):
+    """The one resident frame a captured training step reads: static device tensors at fixed addresses, refilled before every replay.
+
+        x [1, 3, H, W] f32 | boxes [cap, 4] f32 | labels [cap] i64 | n_gt int32[1] | empty int32[1]
+
+    The number of ground-truth boxes is DATA here (n_gt), not a shape: `model(slot.x, slot.boxes, slot.labels, n_gt=slot.n_gt,
+    empty=slot.empty)` hands the target makers the whole fixed-capacity lists and they read the count on the device (ops.rpn_targets /
+    ops.head_targets), so ONE captured graph set trains on any stream of frames -- straight from the device input stage
+    (MosaicResult / CropResult / DeviceMultiScaleStage: boxes, labels, count), without the count.item() that slicing would need:
+
+        slot = FrameSlot((H, W), cap, device)
+        opt = DeviceSGD(params, ..., guard=slot.empty)          # a frame without boxes makes the captured update a no-op
+        gs = GraphStep(model, opt, lambda f: loss_of(model(slot.x, slot.boxes, slot.labels, n_gt=slot.n_gt, empty=slot.empty)), 1, device,
+                       **model.graph_stages()).capture()
+        for i, (x, boxes, labels, count) in enumerate(stream):
+            slot.load(x, boxes, labels, count)
+            gs.step(i)
+
+    `empty` is written by the head target maker at every step (1: the frame had no live box -- the reference raises there; the step's
+    loss is NaN and, with guard=slot.empty, nothing is updated; 0 otherwise), never by load().  A count above the capacity cannot be
+    refused without reading it: the first `cap` rows are used and _lib.HT_ERR_GT_COUNT lands in the model's sticky status word.
+
+    One slot -- and one graph set -- serves ONE input shape.  A recipe with several padded shapes (the multi-scale stage) needs a slot
+    and a GraphStep per distinct shape; choosing between them is the caller's (a shape-bucketing cache is not part of this class)."""
+
+    def __init__(self, image_hw, gt_capacity, device):
+        try:
+            H, W = (int(v) for v in image_hw)
+        except (TypeError, ValueError):
+            raise ValueError("FrameSlot: image_hw must be (H, W), got %r" % (image_hw,))
+        if H <= 0 or W <= 0:
+            raise ValueError("FrameSlot: image_hw must be positive, got %r" % (image_hw,))
+        if isinstance(gt_capacity, bool) or not isinstance(gt_capacity, int) or not 1 <= gt_capacity <= 4096:
+            raise ValueError("FrameSlot: gt_capacity must be an int in [1, 4096] (the target makers' limit), got %r" % (gt_capacity,))
+        self.device = torch.device(device)
+        self.capacity = gt_capacity
+        self.x = torch.zeros(1, 3, H, W, dtype=torch.float32, device=self.device)
+        self.boxes = torch.zeros(gt_capacity, 4, dtype=torch.float32, device=self.device)
+        self.labels = torch.zeros(gt_capacity, dtype=torch.int64, device=self.device)
+        self.n_gt = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.empty = torch.zeros(1, dtype=torch.int32, device=self.device)
+
+    def load(self, x, boxes, labels, count=None):
+        """Stream-ordered copies into the static tensors; nothing is read back.  boxes [r, 4] / labels [r] with r <= capacity (rows
+        r .. capacity are cleared); count: a device tensor of one element, a Python int, or None (= r).  Whatever the host knows is
+        checked here (ValueError); a device count is checked by the kernels (see the class)."""
+        if not torch.is_tensor(x) or tuple(x.shape[-3:]) != tuple(self.x.shape[1:]) or x.numel() != self.x.numel():
+            raise ValueError("FrameSlot.load: x must be [1, 3, %d, %d] (one slot serves one input shape), got %s"
+                             % (self.x.shape[2], self.x.shape[3], tuple(x.shape) if torch.is_tensor(x) else type(x).__name__))
+        if not torch.is_tensor(boxes) or boxes.dim() != 2 or boxes.shape[1] != 4:
+            raise ValueError("FrameSlot.load: boxes must be [r, 4]")
+        r = boxes.shape[0]
+        if r > self.capacity:
+            raise ValueError("FrameSlot.load: %d boxes, the slot holds %d" % (r, self.capacity))
+        if not torch.is_tensor(labels) or labels.numel() != r:
+            raise ValueError("FrameSlot.load: %d boxes need %d labels" % (r, r))
+        if count is None:
+            count = r
+        if torch.is_tensor(count):
+            if count.numel() != 1 or count.dtype.is_floating_point or count.dtype == torch.bool:
+                raise ValueError("FrameSlot.load: count must be ONE integer")
+        else:
+            if isinstance(count, bool) or not isinstance(count, int):
+                raise ValueError("FrameSlot.load: count must be a device tensor or a Python int, got %r" % (count,))
+            if not 0 <= count <= r:
+                raise ValueError("FrameSlot.load: count %d outside [0, %d rows]" % (count, r))
+        with torch.no_grad():
+            self.x.copy_(x.reshape(self.x.shape), non_blocking=True)
+            self.boxes[:r].copy_(boxes, non_blocking=True)
+            self.labels[:r].copy_(labels.reshape(-1), non_blocking=True)
+            if r < self.capacity:
+                self.boxes[r:].zero_()
+                self.labels[r:].zero_()
+            if torch.is_tensor(count):
+                self.n_gt.copy_(count.reshape(1), non_blocking=True)
+            else:
+                self.n_gt.fill_(count)
+        return self
+
+
 class GraphStep(object):
     """The data-parallel training step of train.py:31-37 under models/build.py:8-14, submitted as HIP graphs instead of ~400 (VGG16) /
     ~2500 (ResNet-50-FPN) launches enqueued from Python, with the gradient all-reduce issued BETWEEN the replays (RCCL is not captured):
@@ -129,7 +209,8 @@ class GraphStep(object):
         all-reduce    of the second buffer
         replay U      the optimizer step, reading p.grad = views into the two flat buffers
 
-    A[f] / B[f] exist once per resident frame f (the number of ground-truth boxes is a launch argument), U once.  The backward is cut at
+    A[f] / B[f] exist once per resident frame f (the SHAPE of a frame's ground-truth tensors is frozen into its graphs), U once.  To train on
+    a stream of frames use n_frames = 1 and a forward_loss that reads a FrameSlot (above): the count of boxes is then device data.  The backward is cut at
     the output of `cut_module` (the RoI pooling) and at the RPN's predictions: A takes d loss / d {those tensors, head parameters} with
     torch.autograd.grad, B continues from them -- the same nodes the single backward() runs, each once, so the gradients are the
     ones DDP computes.  Like DDP's reducer the average is taken by scaling BEFORE the sum (here: the backward is seeded with 1 / world,

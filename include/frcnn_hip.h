@@ -339,6 +339,25 @@ int frcnn_rpn_targets(int variant, const float *anchors /*[N,4]*/, int64_t N, co
                       uint64_t seed, uint64_t offset, uint64_t *philox_state_dev /*[2] device, or NULL*/,
                       int64_t *out_cls /*[N]*/, float *out_reg /*[N,4]*/, int32_t *out_counts /*[4]*/,
                       void *workspace, size_t workspace_bytes, void *stream);
+/* The same with the number of ground-truth boxes as DATA: gt is [G_cap, 4] and *n_gt_dev (device int32, read by every kernel of the call,
+ * no host sync) says how many of its rows are live, so a step captured in a HIP graph serves frames with any number of boxes.
+ *   n_gt_dev == NULL : all G_cap rows are live -- frcnn_rpn_targets, which is this call with NULL.
+ *   otherwise        : G = min(*n_gt_dev, G_cap); outputs, counts and the Philox state are bit for bit those of frcnn_rpn_targets on
+ *                      gt[:G].  Rows >= G are never read into a result (they may hold NaN, infinities, copies of anchors).
+ * Everything the host decides goes by G_cap: 1 <= G_cap <= 4096, workspace >= frcnn_workspace_bytes(FRCNN_OP_RPN_TARGETS, N, G_cap).
+ * The reference raises for a frame without boxes; a captured step cannot, so the two cases outside [1, G_cap] are defined here:
+ *   *n_gt_dev > G_cap : the first G_cap rows are used and out_counts[2] carries FRCNN_RPN_ERR_GT_COUNT;
+ *   *n_gt_dev <= 0    : every out_cls = -1 (no anchor takes part in the loss), out_reg = 0, out_counts = {0, 0, FRCNN_RPN_ERR_GT_COUNT, 0}.
+ * out_counts[2] values: 1 / 2 a permutation's length / an entry is wrong (parity mode), 4 the in-kernel barrier timed out, 8 the
+ * sampler's boundary list overflowed; FRCNN_RPN_ERR_GT_COUNT is OR-ed to 1, 2 and 8 (a barrier time-out reports 4 alone).
+ * The workspace invariant (left zero by every call) holds for every count, 0 included. */
+#define FRCNN_RPN_ERR_GT_COUNT 16       /* *n_gt_dev outside [1, G_cap] */
+int frcnn_rpn_targets_n(int variant, const float *anchors /*[N,4]*/, int64_t N, const float *gt /*[G_cap,4]*/, int64_t G_cap,
+                        const int32_t *n_gt_dev /* device int32, or NULL */,
+                        const int64_t *perm_pos, int64_t n_perm_pos, const int64_t *perm_neg, int64_t n_perm_neg,
+                        uint64_t seed, uint64_t offset, uint64_t *philox_state_dev /*[2] device, or NULL*/,
+                        int64_t *out_cls /*[N]*/, float *out_reg /*[N,4]*/, int32_t *out_counts /*[4]*/,
+                        void *workspace, size_t workspace_bytes, void *stream);
 
 /* FastRcnnTargetMaker.forward (models/model_.py:127-179; FPN: models/new_model.py:157-206).
  * rois [P_cap,4] with a device count n_rois_dev (NULL = P_cap rows are live); candidates = cat(rois, gt).
@@ -361,6 +380,23 @@ int frcnn_head_targets(int variant, const float *rois, const int32_t *n_rois_dev
                        int64_t *out_cls /*[total]*/, float *out_reg /*[total,4]*/, float *out_rois /*[total,4]*/,
                        int64_t *out_keep_index /*[total] or NULL*/, int32_t *out_counts /*[4]*/,
                        int32_t *sticky_status /* device int32 or NULL */, void *stream);
+/* The same with a device count for gt / gt_label ([G_cap, 4] / [G_cap]) as well: see frcnn_rpn_targets_n.  n_gt_dev == NULL is
+ * frcnn_head_targets; otherwise the result is bit for bit that of frcnn_head_targets on gt[:G], gt_label[:G], G = min(*n_gt_dev, G_cap).
+ * Limits go by G_cap (G_cap >= 1, P_cap + G_cap <= 4096).
+ *   *n_gt_dev > G_cap : the first G_cap rows, and FRCNN_HT_ERR_GT_COUNT in out_counts[3] / *sticky_status;
+ *   *n_gt_dev <= 0    : every row gets class -1 and zero boxes, as FRCNN_HT_ERR_SHORT rows do; FRCNN_HT_ERR_SHORT | FRCNN_HT_ERR_GT_COUNT.
+ * empty_dev (device int32 or NULL) is written by EVERY call: 1 when the frame has no live box, else 0 (not sticky).  It is made to be
+ * DeviceSGD's guard word: an empty frame then makes the captured optimizer step a no-op and the next frame trains normally. */
+#define FRCNN_HT_ERR_GT_COUNT 16        /* *n_gt_dev outside [1, G_cap] */
+int frcnn_head_targets_n(int variant, const float *rois, const int32_t *n_rois_dev, int64_t P_cap,
+                         const float *gt /*[G_cap,4]*/, const int64_t *gt_label /*[G_cap]*/, int64_t G_cap,
+                         const int32_t *n_gt_dev /* device int32, or NULL */,
+                         int64_t label_offset, int64_t max_pos, int64_t total,
+                         const int64_t *perm_pos, int64_t n_perm_pos, const int64_t *perm_neg, int64_t n_perm_neg,
+                         uint64_t seed, uint64_t offset, uint64_t *philox_state_dev,
+                         int64_t *out_cls /*[total]*/, float *out_reg /*[total,4]*/, float *out_rois /*[total,4]*/,
+                         int64_t *out_keep_index /*[total] or NULL*/, int32_t *out_counts /*[4]*/,
+                         int32_t *sticky_status /* device int32 or NULL */, int32_t *empty_dev /* device int32 or NULL */, void *stream);
 
 /* ---- RoI pooling ---------------------------------------------------------------------------------- */
 /* torchvision.ops.RoIPool((PH,PW), spatial_scale) forward/backward (models/model.py:97,113); one image,
