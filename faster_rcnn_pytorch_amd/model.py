@@ -116,18 +116,33 @@ class RegionProposal(nn.Module):
         return rois[:ops.host_count(cnt, 'region_proposal')]
 
 
-class RegionProposalNetwork(nn.Module):
-    """models/model.py:61-84."""
+class _RPNHead(nn.Module):
+    """The three convolutions of both mirrors' RPN heads and their reference form (models/model.py:68-83, models/new_model.py:96-113)."""
 
-    def __init__(self, in_channels=512, out_channels=512):
+    def __init__(self, in_channels, out_channels, num_anchors):
         super().__init__()
-        num_anchors = 9
         self.inter_layer = nn.Conv2d(in_channels, out_channels, kernel_size=3, padding=1)
         self.cls_layer = nn.Conv2d(in_channels, num_anchors * 2, kernel_size=1)
         self.reg_layer = nn.Conv2d(in_channels, num_anchors * 4, kernel_size=1)
         normal_init(self.inter_layer, 0, 0.01)
         normal_init(self.cls_layer, 0, 0.01)
         normal_init(self.reg_layer, 0, 0.01)
+
+    def forward(self, features):
+        batch_size = features.size(0)
+        x = torch.relu(self.inter_layer(features))
+        pred_cls = self.cls_layer(x)
+        pred_reg = self.reg_layer(x)
+        pred_reg = pred_reg.permute(0, 2, 3, 1).contiguous().view(batch_size, -1, 4)
+        pred_cls = pred_cls.permute(0, 2, 3, 1).contiguous().view(batch_size, -1, 2)
+        return pred_cls, pred_reg
+
+
+class RegionProposalNetwork(_RPNHead):
+    """models/model.py:61-84."""
+
+    def __init__(self, in_channels=512, out_channels=512):
+        super().__init__(in_channels, out_channels, num_anchors=9)
 
     def forward(self, features):
         if (features.is_cuda and features.dtype == torch.float32 and features.size(0) == 1 and not torch.is_autocast_enabled()
@@ -137,13 +152,7 @@ class RegionProposalNetwork(nn.Module):
             raw = ops.rpn_conv3x3([features], self.inter_layer.weight)[0]
             return ops.rpn_head_tail(raw, self.inter_layer.bias, self.cls_layer.weight, self.cls_layer.bias,
                                      self.reg_layer.weight, self.reg_layer.bias)
-        batch_size = features.size(0)                                              # reference form (autocast / batch > 1)
-        x = torch.relu(self.inter_layer(features))
-        pred_cls = self.cls_layer(x)
-        pred_reg = self.reg_layer(x)
-        pred_reg = pred_reg.permute(0, 2, 3, 1).contiguous().view(batch_size, -1, 4)
-        pred_cls = pred_cls.permute(0, 2, 3, 1).contiguous().view(batch_size, -1, 2)
-        return pred_cls, pred_reg
+        return super().forward(features)                                           # reference form (autocast / batch > 1)
 
 
 class FastRCNNHead(nn.Module):
@@ -202,7 +211,10 @@ class _Sampler(object):
 
 
 class FastRcnnTargetMaker(nn.Module):
-    """models/model_.py:123-179."""
+    """models/model_.py:123-179.  The FPN mirror's head target maker is this one with other constants (ops.head_targets) and its own
+    reference line in the short-sample message."""
+    variant, label_offset, max_pos, total = 0, 1, 32, 128
+    cite = "the reference fails here too, model_.py:340"
 
     def __init__(self, sampler=None):
         super().__init__()
@@ -213,22 +225,23 @@ class FastRcnnTargetMaker(nn.Module):
         bbox = _unwrap(bbox)
         label = _unwrap(label).to(torch.int64)
         s = self.sampler
+        kw = dict(n_rois=n_rois, variant=self.variant, label_offset=self.label_offset, max_pos=self.max_pos, total=self.total, n_gt=n_gt)
         if s.sampling == "host":
-            c = ops.head_targets(rois, bbox, label, n_rois=n_rois, n_gt=n_gt)[4].cpu().tolist()     # learn the candidate counts
-            perm_pos = torch.randperm(c[0])                                                # model_.py:149
-            perm_neg = torch.randperm(c[1])                                                # model_.py:155
-            cls, reg, srois, _, counts = ops.head_targets(rois, bbox, label, n_rois=n_rois, perm_pos=perm_pos, perm_neg=perm_neg, n_gt=n_gt,
-                                                          empty=empty)
-            if counts.cpu().tolist()[2] != 128:
-                raise RuntimeError("FastRcnnTargetMaker: fewer than 128 samples (the reference fails here too, model_.py:340)")
+            c = ops.head_targets(rois, bbox, label, **kw)[4].cpu().tolist()                # learn the candidate counts
+            perm_pos = torch.randperm(c[0])                                                # model_.py:149, new_model.py:175
+            perm_neg = torch.randperm(c[1])                                                # model_.py:155, new_model.py:180
+            cls, reg, srois, _, counts = ops.head_targets(rois, bbox, label, perm_pos=perm_pos, perm_neg=perm_neg, empty=empty, **kw)
+            if counts.cpu().tolist()[2] != self.total:
+                raise RuntimeError("%s: fewer than %d samples (%s)" % (type(self).__name__, self.total, self.cite))
         else:
-            cls, reg, srois, _, _ = ops.head_targets(rois, bbox, label, n_rois=n_rois, philox_state=s.state(rois.device),
-                                                     status=s.status.word(rois.device), n_gt=n_gt, empty=empty)
+            cls, reg, srois, _, _ = ops.head_targets(rois, bbox, label, philox_state=s.state(rois.device),
+                                                     status=s.status.word(rois.device), empty=empty, **kw)
         return cls, reg, srois
 
 
 class RPNTargetMaker(nn.Module):
-    """models/model_.py:182-266."""
+    """models/model_.py:182-266.  The FPN mirror's RPN target maker is this one with variant = 1 (ops.rpn_targets)."""
+    variant = 0
 
     def __init__(self, sampler=None):
         super().__init__()
@@ -239,21 +252,94 @@ class RPNTargetMaker(nn.Module):
         bbox = _unwrap(bbox)
         s = self.sampler
         if s.sampling == "host":
-            n_pos, n_neg = ops.rpn_targets(anchor, bbox, n_gt=n_gt)[2].cpu().tolist()[:2]
+            n_pos, n_neg = ops.rpn_targets(anchor, bbox, variant=self.variant, n_gt=n_gt)[2].cpu().tolist()[:2]
             perm_pos = torch.randperm(n_pos) if n_pos > 128 else None                      # model_.py:225-229
             perm_neg = torch.randperm(n_neg) if n_neg > 256 - n_pos else None              # model_.py:231-236
-            cls, reg, counts = ops.rpn_targets(anchor, bbox, perm_pos=perm_pos, perm_neg=perm_neg, n_gt=n_gt)
+            cls, reg, counts = ops.rpn_targets(anchor, bbox, variant=self.variant, perm_pos=perm_pos, perm_neg=perm_neg, n_gt=n_gt)
             err = counts.cpu().tolist()[2]
             if err & ~ops._lib.RPN_ERR_GT_COUNT:
                 raise RuntimeError("RPNTargetMaker: permutation length mismatch")
             if err:
                 raise RuntimeError("RPNTargetMaker: n_gt outside [1, %d]" % bbox.shape[0])
         else:
-            cls, reg, _ = ops.rpn_targets(anchor, bbox, philox_state=s.state(anchor.device), n_gt=n_gt)
+            cls, reg, _ = ops.rpn_targets(anchor, bbox, variant=self.variant, philox_state=s.state(anchor.device), n_gt=n_gt)
         return cls, reg
 
 
-class FRCNN(nn.Module):
+class _Detector(nn.Module):
+    """What the two FRCNN mirrors share, and the interface parallel.GraphStep / FrameSlot, inference.DetectGraph and bench.py rely on:
+    forward(x, boxes, labels, n_gt=, empty=), predict, detect, graph_stages(), check_device_status(), and the attributes num_classes,
+    sampler and last_proposal_count.  A mirror writes forward and graph_stages itself and gives predict / detect two hooks:
+        _test_proposals(x)         -> (features, rois [P,4] fixed capacity, n_rois device int32[1]), test mode, no host sync
+        _head(features, rois, x)   -> (head_cls [R,C], head_reg [R,4C])"""
+
+    def count_parameters(self):
+        return sum(p.numel() for p in self.parameters() if p.requires_grad)
+
+    def check_device_status(self):
+        """Raises if a device-side failure was recorded since the last call (an aborted NMS scan upstream of the head target
+        maker, or fewer than 128 / 512 RoI samples -- where the reference throws, model.py:340, or asserts, new_model.py:182).  One
+        host sync: call it at the logging / checkpoint interval.  The same failures turn the step's loss into NaN, so a caller that
+        prints loss.item() sees them even without this call."""
+        self.sampler.status.check()
+
+    @staticmethod
+    def _target_class_rows(pred_reg, target_cls, rows):
+        """models/model.py:340-341 in both mirrors: row i of the `rows` sampled RoIs keeps the regression of its target class (reference:
+        pred[arange(rows), cls], advanced indexing).  torch.gather selects the same elements with one kernel forward and one backward;
+        the indexing form costs an arange, an index kernel and a rocprim sort + scatter in backward (~30 us and 7 launches per step)."""
+        idx = target_cls.clamp(min=0).view(-1, 1, 1).expand(-1, 1, 4)             # (-1 = unsampled row: its loss is NaN anyway)
+        return torch.gather(pred_reg.reshape(rows, -1, 4), 1, idx).squeeze(1)
+
+    def _decode(self, rois, head_cls, head_reg):
+        """models/model.py:369-378, models/new_model.py:437-445: (clamped boxes [R, 4C], probabilities [R, C]) of the live RoIs."""
+        pred_cls = torch.softmax(head_cls, dim=-1)                               # model.py:369
+        head_reg = head_reg.reshape(-1, self.num_classes, 4) * ops.const_tensor((0.1, 0.1, 0.2, 0.2), head_reg.device)   # model.py:372 (SURVEY Q10)
+        rois = rois.reshape(-1, 1, 4).expand_as(head_reg)
+        pred_bbox = ops.cxcy_to_xy(ops.decode(head_reg.reshape(-1, 4).contiguous(), ops.xy_to_cxcy(rois.reshape(-1, 4).contiguous())))
+        return pred_bbox.reshape(-1, self.num_classes * 4).clamp(min=0, max=1), pred_cls
+
+    @torch.no_grad()
+    def predict(self, x, opts):
+        """opts: an object with .thres (model.py:346) or a bare float threshold (model_.py:346)."""
+        threshold = float(getattr(opts, "thres", opts))
+        features, rois, n_rois = self._test_proposals(x)
+        rois = rois[:ops.host_count(n_rois, 'region_proposal')]
+        head_cls, head_reg = self._head(features, rois, x)
+        return self._suppress(*self._decode(rois, head_cls, head_reg), threshold)
+
+    @torch.no_grad()
+    def detect(self, x, opts_or_threshold, threshold_dev=None, want_prob=False):
+        """predict without a host sync (graph-capturable): the test-mode path with the fixed-capacity proposals and their device count,
+        the head on all P rows, and the post-processing of models/model.py:368-402 / models/new_model.py:420-470 in
+        ops.detect_postprocess.  threshold_dev (a device float32[1]) overrides the threshold when given.  Returns ops.Detections (its
+        n_rois is the proposal count); .to_host() gives what predict returns."""
+        threshold = float(getattr(opts_or_threshold, "thres", opts_or_threshold))
+        features, rois, n_rois = self._test_proposals(x)
+        head_cls, head_reg = self._head(features, rois, x)                        # rows >= n_rois: zero boxes, ignored below
+        return ops.detect_postprocess(head_cls, head_reg, rois, n_rois, threshold, 0.3, threshold_dev=threshold_dev, want_prob=want_prob)
+
+    def _suppress(self, raw_cls_bbox, raw_prob, threshold):
+        """models/model.py:382-402 (per-class score mask + nms(0.3), class 0 = background skipped, results concatenated
+        class by class) as ONE class-aware NMS: 2 host syncs in total instead of 2 per class."""
+        R = raw_prob.shape[0]
+        boxes = raw_cls_bbox.reshape((R, self.num_classes, 4))[:, 1:, :]
+        prob = raw_prob[:, 1:]
+        ridx, cidx = (prob > threshold).nonzero(as_tuple=True)                    # sync 1: number of candidates
+        cand_box = boxes[ridx, cidx].contiguous()
+        cand_score = prob[ridx, cidx].contiguous()
+        keep = ops.batched_nms(cand_box, cand_score, cidx, 0.3)                   # sync 2: number kept (score-descending)
+        bbox = cand_box[keep].cpu().numpy()
+        label = cidx[keep].cpu().numpy()                                          # 0-based: l - 1 in the reference
+        score = cand_score[keep].cpu().numpy()
+        order = np.argsort(label, kind="stable")                                  # class-major, score-descending inside a class
+        bbox = torch.from_numpy(bbox[order].astype(np.float32))
+        label = torch.from_numpy(label[order].astype(np.int32))
+        score = torch.from_numpy(score[order].astype(np.float32))
+        return bbox, label, score
+
+
+class FRCNN(_Detector):
     """models/model.py:269-402 (VGG16 Faster R-CNN)."""
 
     def __init__(self, num_classes=81, pretrained=False, sampling="device", seed=0):
@@ -272,16 +358,6 @@ class FRCNN(nn.Module):
         self.fast_rcnn_target_maker = FastRcnnTargetMaker(self.sampler)
         self.fast_rcnn_head = FastRCNNHead(num_classes=num_classes, roi_size=7, classifier=self.classifier)
         self.last_proposal_count = None
-
-    def count_parameters(self):
-        return sum(p.numel() for p in self.parameters() if p.requires_grad)
-
-    def check_device_status(self):
-        """Raises if a device-side failure was recorded since the last call (an aborted NMS scan upstream of the head target
-        maker, or fewer than 128 RoI samples -- where the reference throws, model.py:340).  One host sync: call it at the
-        logging / checkpoint interval.  The same failures turn the step's loss into NaN, so a caller that prints loss.item()
-        sees them even without this call."""
-        self.sampler.status.check()
 
     def graph_stages(self):
         """Where parallel.GraphStep cuts the backward: everything behind the RoI pooling (the FC head: 120 M of the 137 M parameters) has its
@@ -313,68 +389,19 @@ class FRCNN(nn.Module):
         # 7. fast rcnn head                                                    model.py:335
         pred_fast_rcnn_cls, pred_fast_rcnn_reg = self.fast_rcnn_head(features, sample_rois)
         # 8. regression row of the target class                                model.py:340-341
-        pred_fast_rcnn_reg = pred_fast_rcnn_reg.reshape(128, -1, 4)
-        # row i keeps the regression of its target class (reference: pred[arange(128), cls], advanced indexing).  torch.gather selects the
-        # same elements with one kernel forward and one backward; the indexing form costs an arange, an index kernel and a rocprim sort
-        # + scatter in backward (~30 us and 7 launches per step).
-        pred_fast_rcnn_reg = torch.gather(pred_fast_rcnn_reg, 1, target_fast_rcnn_cls.clamp(min=0).view(-1, 1, 1).expand(-1, 1, 4)).squeeze(1)   # (-1 = unsampled row: its loss is NaN anyway)
+        pred_fast_rcnn_reg = self._target_class_rows(pred_fast_rcnn_reg, target_fast_rcnn_cls, 128)
         return (pred_rpn_cls, pred_rpn_reg, pred_fast_rcnn_cls, pred_fast_rcnn_reg), \
                (target_rpn_cls, target_rpn_reg, target_fast_rcnn_cls, target_fast_rcnn_reg)
 
-    @torch.no_grad()
-    def predict(self, x, opts):
-        """opts: an object with .thres (model.py:346) or a bare float threshold (model_.py:346)."""
-        threshold = float(getattr(opts, "thres", opts))
+    def _test_proposals(self, x):
         features = self.extractor(x)
-        hw = x.size()[2:]
         pred_rpn_cls, pred_rpn_reg = self.rpn(features)
         rois, n_rois, _ = self.rp.propose(pred_rpn_cls.squeeze(0), pred_rpn_reg.squeeze(0), None, "test",
-                                          grid=self.anchor_maker.grid_desc(hw))
-        rois = rois[:ops.host_count(n_rois, 'region_proposal')]
-        pred_fast_rcnn_cls, pred_fast_rcnn_reg = self.fast_rcnn_head(features, rois)
-        pred_cls = torch.softmax(pred_fast_rcnn_cls, dim=-1)                    # model.py:369
-        pred_fast_rcnn_reg = pred_fast_rcnn_reg.reshape(-1, self.num_classes, 4)
-        pred_fast_rcnn_reg = pred_fast_rcnn_reg * ops.const_tensor((0.1, 0.1, 0.2, 0.2), x.device)   # model.py:372 (SURVEY Q10)
-        rois = rois.reshape(-1, 1, 4).expand_as(pred_fast_rcnn_reg)
-        pred_bbox = ops.decode(pred_fast_rcnn_reg.reshape(-1, 4).contiguous(), ops.xy_to_cxcy(rois.reshape(-1, 4).contiguous()))
-        pred_bbox = ops.cxcy_to_xy(pred_bbox)
-        pred_bbox = pred_bbox.reshape(-1, self.num_classes * 4).clamp(min=0, max=1)
-        return self._suppress(pred_bbox, pred_cls, threshold)
+                                          grid=self.anchor_maker.grid_desc(x.size()[2:]))
+        return features, rois, n_rois
 
-    @torch.no_grad()
-    def detect(self, x, opts_or_threshold, threshold_dev=None, want_prob=False):
-        """predict without a host sync (graph-capturable): the test-mode path with the fixed-capacity proposals and their device count,
-        the head on all P rows, and the post-processing of models/model.py:368-402 in ops.detect_postprocess.  threshold_dev (a device
-        float32[1]) overrides the threshold when given.  Returns ops.Detections (its n_rois is the proposal count); .to_host() gives
-        what predict returns."""
-        threshold = float(getattr(opts_or_threshold, "thres", opts_or_threshold))
-        features = self.extractor(x)
-        hw = x.size()[2:]
-        pred_rpn_cls, pred_rpn_reg = self.rpn(features)
-        rois, n_rois, _ = self.rp.propose(pred_rpn_cls.squeeze(0), pred_rpn_reg.squeeze(0), None, "test",
-                                          grid=self.anchor_maker.grid_desc(hw))
-        pred_fast_rcnn_cls, pred_fast_rcnn_reg = self.fast_rcnn_head(features, rois)      # rows >= n_rois: zero boxes, ignored below
-        return ops.detect_postprocess(pred_fast_rcnn_cls, pred_fast_rcnn_reg, rois, n_rois, threshold, 0.3, threshold_dev=threshold_dev,
-                                      want_prob=want_prob)
-
-    def _suppress(self, raw_cls_bbox, raw_prob, threshold):
-        """models/model.py:382-402 (per-class score mask + nms(0.3), class 0 = background skipped, results concatenated
-        class by class) as ONE class-aware NMS: 2 host syncs in total instead of 2 per class."""
-        R = raw_prob.shape[0]
-        boxes = raw_cls_bbox.reshape((R, self.num_classes, 4))[:, 1:, :]
-        prob = raw_prob[:, 1:]
-        ridx, cidx = (prob > threshold).nonzero(as_tuple=True)                    # sync 1: number of candidates
-        cand_box = boxes[ridx, cidx].contiguous()
-        cand_score = prob[ridx, cidx].contiguous()
-        keep = ops.batched_nms(cand_box, cand_score, cidx, 0.3)                   # sync 2: number kept (score-descending)
-        bbox = cand_box[keep].cpu().numpy()
-        label = cidx[keep].cpu().numpy()                                          # 0-based: l - 1 in the reference
-        score = cand_score[keep].cpu().numpy()
-        order = np.argsort(label, kind="stable")                                  # class-major, score-descending inside a class
-        bbox = torch.from_numpy(bbox[order].astype(np.float32))
-        label = torch.from_numpy(label[order].astype(np.int32))
-        score = torch.from_numpy(score[order].astype(np.float32))
-        return bbox, label, score
+    def _head(self, features, rois, x):
+        return self.fast_rcnn_head(features, rois)
 
 
 def build_model(opts=None, num_classes=21, device=None, **kw):

@@ -17,8 +17,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops
-from .model import _Sampler, _unwrap, normal_init
+from . import model, ops
+from .model import _Detector, _RPNHead, _Sampler, normal_init
 
 
 class FrozenBatchNorm2d(nn.Module):
@@ -246,18 +246,11 @@ class BackboneWithFPN(nn.Module):
         return self.fpn(self.body(x))
 
 
-class RPNHead(nn.Module):
-    """models/new_model.py:89-114."""
+class RPNHead(_RPNHead):
+    """models/new_model.py:89-114; forward (one level) is the reference form."""
 
     def __init__(self, in_channels=256, out_channels=256):
-        super().__init__()
-        num_anchors = 3
-        self.inter_layer = nn.Conv2d(in_channels, out_channels, kernel_size=3, padding=1)
-        self.cls_layer = nn.Conv2d(in_channels, num_anchors * 2, kernel_size=1)
-        self.reg_layer = nn.Conv2d(in_channels, num_anchors * 4, kernel_size=1)
-        normal_init(self.inter_layer, 0, 0.01)
-        normal_init(self.cls_layer, 0, 0.01)
-        normal_init(self.reg_layer, 0, 0.01)
+        super().__init__(in_channels, out_channels, num_anchors=3)
         self.fused_bf16_conv = True          # under bf16 autocast: the hand-written implicit-GEMM head (csrc/rpn_conv.hip) instead of MIOpen + tail
 
     def forward_levels(self, feats):
@@ -284,15 +277,6 @@ class RPNHead(nn.Module):
                                                     mfma="bf16" if raws[0].dtype == torch.bfloat16 else "f32")
         cls, reg = zip(*[self.forward(f) for f in feats])                          # reference form (batch > 1)
         return torch.cat(cls, dim=1), torch.cat(reg, dim=1)
-
-    def forward(self, features):
-        batch_size = features.size(0)
-        x = torch.relu(self.inter_layer(features))
-        pred_cls = self.cls_layer(x)
-        pred_reg = self.reg_layer(x)
-        pred_reg = pred_reg.permute(0, 2, 3, 1).contiguous().view(batch_size, -1, 4)
-        pred_cls = pred_cls.permute(0, 2, 3, 1).contiguous().view(batch_size, -1, 2)
-        return pred_cls, pred_reg
 
 
 class RegionProposalNetwork(nn.Module):
@@ -362,58 +346,24 @@ class FRCNNHead(nn.Module):
         return self.cls_head(x), self.reg_head(x)
 
 
-class FRCNNTargetMaker(nn.Module):
+class FRCNNTargetMaker(model.FastRcnnTargetMaker):
     """models/new_model.py:153-206: box_iou (no eps), labels used raw, <= 128 positives of 512 samples."""
-
-    def __init__(self, sampler=None):
-        super().__init__()
-        self.sampler = sampler or _Sampler()
+    variant, label_offset, max_pos, total = 1, 0, 128, 512
+    cite = "assert at new_model.py:183"
 
     def forward(self, boxes, labels, rois, n_rois=None, n_gt=None, empty=None):
-        """n_gt (device int32): boxes / labels are fixed-capacity lists with n_gt live rows (ops.head_targets); empty: see there."""
-        boxes = _unwrap(boxes)
-        labels = _unwrap(labels).to(torch.int64)
-        s = self.sampler
-        kw = dict(n_rois=n_rois, variant=1, label_offset=0, max_pos=128, total=512, n_gt=n_gt)
-        if s.sampling == "host":
-            c = ops.head_targets(rois, boxes, labels, **kw)[4].cpu().tolist()
-            perm_pos, perm_neg = torch.randperm(c[0]), torch.randperm(c[1])        # new_model.py:175,180
-            cls, reg, srois, _, counts = ops.head_targets(rois, boxes, labels, perm_pos=perm_pos, perm_neg=perm_neg, empty=empty, **kw)
-            if counts.cpu().tolist()[2] != 512:
-                raise RuntimeError("FRCNNTargetMaker: fewer than 512 samples (assert at new_model.py:183)")
-        else:
-            cls, reg, srois, _, _ = ops.head_targets(rois, boxes, labels, philox_state=s.state(rois.device),
-                                                     status=s.status.word(rois.device), empty=empty, **kw)
-        return cls, reg, srois
+        return super().forward(boxes, labels, rois, n_rois, n_gt, empty)
 
 
-class RPNTargetMaker(nn.Module):
+class RPNTargetMaker(model.RPNTargetMaker):
     """models/new_model.py:299-349: no inside filter, tie-inclusive low-quality matches."""
-
-    def __init__(self, sampler=None):
-        super().__init__()
-        self.sampler = sampler or _Sampler()
+    variant = 1
 
     def forward(self, boxes, anchors, n_gt=None):
-        """n_gt (device int32): boxes is a fixed-capacity list with n_gt live rows (ops.rpn_targets)."""
-        boxes = _unwrap(boxes)
-        s = self.sampler
-        if s.sampling == "host":
-            n_pos, n_neg = ops.rpn_targets(anchors, boxes, variant=1, n_gt=n_gt)[2].cpu().tolist()[:2]
-            perm_pos = torch.randperm(n_pos) if n_pos > 128 else None
-            perm_neg = torch.randperm(n_neg) if n_neg > 256 - n_pos else None
-            cls, reg, counts = ops.rpn_targets(anchors, boxes, variant=1, perm_pos=perm_pos, perm_neg=perm_neg, n_gt=n_gt)
-            err = counts.cpu().tolist()[2]
-            if err & ~ops._lib.RPN_ERR_GT_COUNT:
-                raise RuntimeError("RPNTargetMaker: permutation length mismatch")
-            if err:
-                raise RuntimeError("RPNTargetMaker: n_gt outside [1, %d]" % boxes.shape[0])
-        else:
-            cls, reg, _ = ops.rpn_targets(anchors, boxes, variant=1, philox_state=s.state(anchors.device), n_gt=n_gt)
-        return cls, reg
+        return super().forward(boxes, anchors, n_gt)
 
 
-class FRCNN(nn.Module):
+class FRCNN(_Detector):
     """models/new_model.py:366-470."""
 
     def __init__(self, num_classes, sampling="device", seed=0):
@@ -429,14 +379,6 @@ class FRCNN(nn.Module):
         self.frcnn_head = FRCNNHead(num_classes=num_classes, roi_size=7, classifier=self.classifier)
         self.last_proposal_count = None
 
-    def count_parameters(self):
-        return sum(p.numel() for p in self.parameters() if p.requires_grad)
-
-    def check_device_status(self):
-        """As models.model.FRCNN.check_device_status: raises if a device-side failure (aborted NMS scan, fewer than 512 RoI
-        samples -- the reference asserts there, new_model.py:182) was recorded since the last call; one host sync."""
-        self.sampler.status.check()
-
     def graph_stages(self):
         """Where parallel.GraphStep cuts the backward (see models.model.FRCNN.graph_stages): behind the multi-scale RoIAlign."""
         return {"cut_module": self.frcnn_head.roi_pool, "late_modules": (self.classifier, self.frcnn_head.cls_head, self.frcnn_head.reg_head)}
@@ -450,53 +392,13 @@ class FRCNN(nn.Module):
         target_fast_rcnn_cls, target_fast_rcnn_reg, sample_rois = self.frcnn_target_maker(boxes=boxes, labels=labels, rois=rois,
                                                                                           n_rois=n_rois, n_gt=n_gt, empty=empty)
         pred_fast_rcnn_cls, pred_fast_rcnn_reg = self.frcnn_head(features, sample_rois, x.shape[2:])
-        pred_fast_rcnn_reg = pred_fast_rcnn_reg.reshape(512, -1, 4)
-        # row i keeps the regression of its target class (reference: pred[arange(512), cls], advanced indexing).  torch.gather selects the
-        # same elements with one kernel forward and one backward; the indexing form costs an arange, an index kernel and a rocprim sort
-        # + scatter in backward (~30 us and 7 launches per step).
-        pred_fast_rcnn_reg = torch.gather(pred_fast_rcnn_reg, 1, target_fast_rcnn_cls.clamp(min=0).view(-1, 1, 1).expand(-1, 1, 4)).squeeze(1)   # (-1 = unsampled row: its loss is NaN anyway)
+        pred_fast_rcnn_reg = self._target_class_rows(pred_fast_rcnn_reg, target_fast_rcnn_cls, 512)
         return (pred_rpn_cls.unsqueeze(0), pred_rpn_reg.unsqueeze(0), pred_fast_rcnn_cls, pred_fast_rcnn_reg), \
                (target_rpn_cls, target_rpn_reg, target_fast_rcnn_cls, target_fast_rcnn_reg)
 
-    @torch.no_grad()
-    def predict(self, x, opts):
-        threshold = float(getattr(opts, "thres", opts))
+    def _test_proposals(self, x):
         features = self.backbone(x)
-        _, _, rois, n_rois, _ = self.rpn.propose(x, features, "test")
-        rois = rois[:ops.host_count(n_rois, 'region_proposal')]
-        pred_fast_rcnn_cls, pred_fast_rcnn_reg = self.frcnn_head(features, rois, x.shape[2:])
-        pred_cls = torch.softmax(pred_fast_rcnn_cls, dim=-1)
-        pred_fast_rcnn_reg = pred_fast_rcnn_reg.reshape(-1, self.num_classes, 4) * ops.const_tensor((0.1, 0.1, 0.2, 0.2), x.device)
-        rois = rois.reshape(-1, 1, 4).expand_as(pred_fast_rcnn_reg)
-        pred_bbox = ops.cxcy_to_xy(ops.decode(pred_fast_rcnn_reg.reshape(-1, 4).contiguous(), ops.xy_to_cxcy(rois.reshape(-1, 4).contiguous())))
-        pred_bbox = pred_bbox.reshape(-1, self.num_classes * 4).clamp(min=0, max=1)
-        return self._suppress(pred_bbox, pred_cls, threshold)
+        return (features,) + self.rpn.propose(x, features, "test")[2:4]
 
-    @torch.no_grad()
-    def detect(self, x, opts_or_threshold, threshold_dev=None, want_prob=False):
-        """predict without a host sync (see models.model.FRCNN.detect): models/new_model.py:420-470 on the fixed-capacity proposals."""
-        threshold = float(getattr(opts_or_threshold, "thres", opts_or_threshold))
-        features = self.backbone(x)
-        _, _, rois, n_rois, _ = self.rpn.propose(x, features, "test")
-        pred_fast_rcnn_cls, pred_fast_rcnn_reg = self.frcnn_head(features, rois, x.shape[2:])
-        return ops.detect_postprocess(pred_fast_rcnn_cls, pred_fast_rcnn_reg, rois, n_rois, threshold, 0.3, threshold_dev=threshold_dev,
-                                      want_prob=want_prob)
-
-    def _suppress(self, raw_cls_bbox, raw_prob, threshold):
-        """models/model.py:382-402 (per-class score mask + nms(0.3), class 0 = background skipped, results concatenated
-        class by class) as ONE class-aware NMS: 2 host syncs in total instead of 2 per class."""
-        R = raw_prob.shape[0]
-        boxes = raw_cls_bbox.reshape((R, self.num_classes, 4))[:, 1:, :]
-        prob = raw_prob[:, 1:]
-        ridx, cidx = (prob > threshold).nonzero(as_tuple=True)                    # sync 1: number of candidates
-        cand_box = boxes[ridx, cidx].contiguous()
-        cand_score = prob[ridx, cidx].contiguous()
-        keep = ops.batched_nms(cand_box, cand_score, cidx, 0.3)                   # sync 2: number kept (score-descending)
-        bbox = cand_box[keep].cpu().numpy()
-        label = cidx[keep].cpu().numpy()                                          # 0-based: l - 1 in the reference
-        score = cand_score[keep].cpu().numpy()
-        order = np.argsort(label, kind="stable")                                  # class-major, score-descending inside a class
-        bbox = torch.from_numpy(bbox[order].astype(np.float32))
-        label = torch.from_numpy(label[order].astype(np.int32))
-        score = torch.from_numpy(score[order].astype(np.float32))
-        return bbox, label, score
+    def _head(self, features, rois, x):
+        return self.frcnn_head(features, rois, x.shape[2:])

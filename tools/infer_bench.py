@@ -53,14 +53,8 @@ def build(config, dev):
 
 
 def old_chain(m, rois, n, hc, hr, thr):
-    """The post-processing lines of FRCNN.predict (model.py / new_model.py), on the head outputs of n live rows."""
-    rois = rois[:n]
-    pred_cls = torch.softmax(hc, dim=-1)
-    reg = hr.reshape(-1, m.num_classes, 4) * ops.const_tensor((0.1, 0.1, 0.2, 0.2), hc.device)
-    r = rois.reshape(-1, 1, 4).expand_as(reg)
-    box = ops.cxcy_to_xy(ops.decode(reg.reshape(-1, 4).contiguous(), ops.xy_to_cxcy(r.reshape(-1, 4).contiguous())))
-    box = box.reshape(-1, m.num_classes * 4).clamp(min=0, max=1)
-    return m._suppress(box, pred_cls, thr)
+    """The post-processing lines of FRCNN.predict (model._Detector), on the head outputs of n live rows."""
+    return m._suppress(*m._decode(rois[:n], hc, hr), thr)
 
 
 def rate(fn, steps, warmup):
