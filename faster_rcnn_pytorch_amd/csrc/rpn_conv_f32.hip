@@ -1857,6 +1857,55 @@ static int wn_pick_m(const int *H, const int *W, int n_levels)
 
 static bool wn_dims_ok(int Cin, int Cout) { return Cin > 0 && Cout > 0 && Cin % WN_KC == 0 && Cout % WN_KC == 0 && Cin <= 4096 && Cout <= 4096; }
 
+// A product of the stage as the host plans it: the tile shape, the tile and unit counts, the workgroups and how the units are cut among them.  wn_run and
+// wn_wgrad launch from these, frcnn_conv3x3_f32_supported checks their limits, frcnn_conv3x3_f32_plan reports them: one copy of every rule.
+struct WnProduct { int MT, NW, n_m_tiles, n_t_tiles, Kc; long long n_tiles, units; int G, whole, sched; };
+static bool wn_product_ok(const WnProduct &p) { return p.n_tiles <= CF_MAX_TILES && p.units < (1ll << 31); }
+static bool wn_no_fuse()                                             // development A/B: FRCNN_WINO_NO_FUSE=1 keeps the 64 -> 64 product and its output transform apart
+{
+    static const bool no_fuse = [] { const char *e = getenv("FRCNN_WINO_NO_FUSE"); return e && atoi(e) != 0; }();
+    return no_fuse;
+}
+// forward (Mo = Cout, K = Cin) or data gradient (Mo = Cin, K = Cout): the K-major product over Ttot tiles padded to tg
+static WnProduct wn_product(int M, int Mo, int K, long long Ttot, int tg)
+{
+    WnProduct p;
+    p.MT = Mo % CF_MT == 0 ? CF_MT : 64;                             // a 64-channel output side (conv1_2, the data gradient of conv2_1): 64-row tiles
+    p.NW = tg;
+    p.n_m_tiles = Mo / p.MT; p.n_t_tiles = (int)(Ttot / tg); p.Kc = K / WN_KC;
+    p.n_tiles = (long long)(M + 2) * (M + 2) * p.n_m_tiles * p.n_t_tiles;
+    p.units = p.n_tiles * p.Kc;
+    p.G = (int)std::min<long long>(cf_ranges(), p.units);
+    p.whole = 0; p.sched = FRCNN_CONV_SCHED_STREAM_K;
+    if (M == 4 && Mo == 64 && K == 64 && !wn_no_fuse()) {            // 64 -> 64 channels: the product with the output transform fused in (no product planes)
+        p.sched = FRCNN_CONV_SCHED_FUSED_OUT64;
+        return p;
+    }
+    if (p.G < 1) return p;                                           // (no units: the entry points refuse such channel counts)
+    // several tiles per workgroup: cut the ranges at tile boundaries (no partial tiles, no slabs, no tickets) when the rounding costs less
+    // than 16 % (128 -> 128 on 300 x 500: 5.2 tiles per workgroup, 132 -> 124 us; 256 -> 256 on 150 x 250: 2.7, 121 -> 118)
+    const long long per = (p.n_tiles + p.G - 1) / p.G;
+    if (p.n_tiles >= 2ll * p.G && per * p.G * 100 <= p.n_tiles * 116) { p.whole = 1; p.sched = FRCNN_CONV_SCHED_WHOLE_RANGES; }
+    // nearly one tile per workgroup slot (432 tiles of 512 -> 512 on 37 x 62): one whole tile each on fewer workgroups, rather than 13.5 chunks each
+    // with two partial segments, their slabs and a reduction per tile
+    else if (p.n_tiles <= p.G && p.n_tiles * WN_ONE_TILE_DEN >= (long long)p.G * WN_ONE_TILE_NUM) {
+        p.G = (int)p.n_tiles; p.whole = 1; p.sched = FRCNN_CONV_SCHED_ONE_TILE;
+    }
+    return p;
+}
+// weight gradient: the k-contiguous product dU [Cout][Cin] per plane, K = the padded tile total
+static WnProduct wn_wgrad_product(int M, int Cin, int Cout, long long Ttot)
+{
+    WnProduct p;
+    p.MT = Cout % CF_MT == 0 ? CF_MT : 64; p.NW = Cin % CF_NT == 0 ? CF_NT : 64;
+    p.n_m_tiles = Cout / p.MT; p.n_t_tiles = Cin / p.NW; p.Kc = (int)(Ttot / WN_KC);
+    p.n_tiles = (long long)(M + 2) * (M + 2) * p.n_m_tiles * p.n_t_tiles;
+    p.units = p.n_tiles * p.Kc;
+    p.G = (int)std::min<long long>(wn_ranges_nt(), p.units);
+    p.whole = 0; p.sched = FRCNN_CONV_SCHED_STREAM_K;
+    return p;
+}
+
 static CfWs wn_carve(void *workspace, int Cin, int Cout, int M, long long Ttot)
 {
     const int C = ((std::max(Cin, Cout) + CF_MT - 1) / CF_MT) * CF_MT, P = (M + 2) * (M + 2);
@@ -1881,11 +1930,13 @@ FRCNN_EXPORT size_t frcnn_rpn_conv3x3_f32_workspace(const int *H_host, const int
 }
 
 template <int M>
-static int wn_strips(WnStrips *st, const WnArgs &a, const int *H, int n_levels, long long channels, int halo, size_t *lds_bytes, int sm = M)
+static int wn_strips(WnStrips *st, const WnArgs &a, const int *H, int n_levels, long long channels, int halo, size_t *lds_bytes, int sm = M,
+                     int *settled = nullptr)
 {
     int n_strips = 0;
     for (int per_block = Wn<M>::TPB; per_block >= 256; per_block /= 2) {       // the largest strips that still give the chip >= 4096 workgroups
         n_strips = 0;
+        if (settled) *settled = per_block;                           // (frcnn_conv3x3_f32_plan reports it)
         for (int l = 0; l < FRCNN_MAX_LEVELS; ++l) {
             st->first[l] = n_strips;
             const int tw = l < n_levels ? a.lv[l].tw : 1, th = l < n_levels ? (H[l] + M - 1) / M : 1;
@@ -1924,10 +1975,9 @@ static int wn_run(const float *const *in, float *const *out, const unsigned shor
     a.bits = bits_in;
     FRCNN_REQUIRE(Ttot < (1ll << 24) && (long long)P * std::max(K, Mo) * Ttot < (1ll << 31) * 4, "conv3x3_f32: %lld output tiles are too many", Ttot);
     const CfWs ws = wn_carve(workspace, Cin, Cout, M, Ttot);
-    const int MT = Mo % CF_MT == 0 ? CF_MT : 64;                     // a 64-channel output side (conv1_2, the data gradient of conv2_1): 64-row tiles
-    const int n_m_tiles = Mo / MT, n_t_tiles = (int)(Ttot / a.tg), Kc = K / WN_KC;
-    const long long n_tiles = (long long)P * n_m_tiles * n_t_tiles, units = n_tiles * Kc;
-    FRCNN_REQUIRE(n_tiles <= CF_MAX_TILES && units < (1ll << 31), "conv3x3_f32: %lld tiles above the limit %d", n_tiles, CF_MAX_TILES);
+    const WnProduct pr = wn_product(M, Mo, K, Ttot, a.tg);
+    const int MT = pr.MT;
+    FRCNN_REQUIRE(wn_product_ok(pr), "conv3x3_f32: %lld tiles above the limit %d", pr.n_tiles, CF_MAX_TILES);
     const unsigned wb = (unsigned)((Mo / 16) * (K / 16));
     const float *Uuse = ws.U;
     // the weight transform rides in the input transform's launch (rpn_wino_weight_input_kernel) where that is the plain one (MODE 0, not pooled).
@@ -1965,8 +2015,7 @@ static int wn_run(const float *const *in, float *const *out, const unsigned shor
     } else FRCNN_LAUNCH((rpn_wino_input_kernel<M, 0, false>), dim3((unsigned)n_strips, (unsigned)K), dim3(256), lds, s, a, st, Vb);
     FRCNN_CHECK_LAUNCH("rpn_wino_input_kernel");
     if constexpr (M == 4) {
-        static const bool no_fuse = [] { const char *e = getenv("FRCNN_WINO_NO_FUSE"); return e && atoi(e) != 0; }();
-        if (Mo == 64 && K == 64 && !no_fuse) {                           // 64 -> 64 channels: the product with the output transform fused in (no product planes)
+        if (pr.sched == FRCNN_CONV_SCHED_FUSED_OUT64) {                  // 64 -> 64 channels: the product with the output transform fused in (wn_product)
             a.C = Mo; a.bias = bias; a.relu = relu; a.bits_out = bits_out;
             const size_t wl = (size_t)WO_NB * K * (64 + WO_TB) * sizeof(float);      // 96 KB
             // per call: the attribute is per device, and a process may drive several (the call is a table lookup in the runtime)
@@ -1979,17 +2028,9 @@ static int wn_run(const float *const *in, float *const *out, const unsigned shor
             return FRCNN_OK;
         }
     }
+    // (the schedule -- whole-tile ranges, one tile per workgroup, or ranges that cut tiles -- is wn_product's)
     WgArgs g = {Uuse, Vb, ws.M, (long long)Mo * K, (long long)K * Ttot, (long long)Mo * Ttot, Mo, (int)Ttot, (int)Ttot,
-                n_m_tiles, n_t_tiles, Kc, (int)units, (int)std::min<long long>(cf_ranges(), units), 0};
-    {
-        // several tiles per workgroup: cut the ranges at tile boundaries (no partial tiles, no slabs, no tickets) when the rounding costs less
-        // than 16 % (128 -> 128 on 300 x 500: 5.2 tiles per workgroup, 132 -> 124 us; 256 -> 256 on 150 x 250: 2.7, 121 -> 118)
-        const long long per = (n_tiles + g.G - 1) / g.G;
-        if (n_tiles >= 2ll * g.G && per * g.G * 100 <= n_tiles * 116) g.whole = 1;
-        // nearly one tile per workgroup slot (432 tiles of 512 -> 512 on 37 x 62): one whole tile each on fewer workgroups, rather than 13.5 chunks each
-        // with two partial segments, their slabs and a reduction per tile
-        else if (n_tiles <= g.G && n_tiles * WN_ONE_TILE_DEN >= (long long)g.G * WN_ONE_TILE_NUM) { g.G = (int)n_tiles; g.whole = 1; }
-    }
+                pr.n_m_tiles, pr.n_t_tiles, pr.Kc, (int)pr.units, pr.G, pr.whole};
     // (not where this product reads the workspace's U, which the weight gradient's product overwrites: only with the forward's rotated transform at hand)
     if (later && later->products && relu != 2 && Uuse != ws.U) { later->g = g; later->MT = MT; later->NW = a.tg; later->gemm_pending = true; }
     else { const int rc = wn_launch_gemm(false, MT, a.tg, g, ws.part, ws.cnt, s); if (rc) return rc; }
@@ -2047,14 +2088,54 @@ FRCNN_EXPORT int frcnn_conv3x3_f32_supported(const int *H_host, const int *W_hos
     for (int l = 0; l < n_levels; ++l)
         if (H_host[l] <= 0 || W_host[l] <= 0 || (long long)H_host[l] * W_host[l] * Cm >= (1ll << 31)) return 0;
     if (Ttot >= (1ll << 24) || (long long)P * Cm * Ttot >= (1ll << 31) * 4) return 0;
-    auto side = [](long long c) { return c % CF_MT == 0 ? c / CF_MT : c / 64; };                 // tiles along a channel side (128 wide, or 64)
-    auto tiles_ok = [&](long long mt, long long nt, long long k_chunks) {
-        const long long n = P * mt * nt;
-        return n <= CF_MAX_TILES && n * k_chunks < (1ll << 31);
-    };
-    if (!tiles_ok(side(Cout), Ttot / a.tg, Cin / WN_KC)) return 0;                               // forward
-    if (need_grads && (!tiles_ok(side(Cin), Ttot / a.tg, Cout / WN_KC) || !tiles_ok(side(Cout), side(Cin), Ttot / WN_KC))) return 0;      // data gradient, weight gradient
+    if (!wn_product_ok(wn_product(M, Cout, Cin, Ttot, a.tg))) return 0;                          // forward
+    if (need_grads && (!wn_product_ok(wn_product(M, Cin, Cout, Ttot, a.tg)) || !wn_product_ok(wn_wgrad_product(M, Cin, Cout, Ttot)))) return 0;      // data gradient, weight gradient
     return 1;
+}
+
+template <int M>
+static void wn_plan_strips(int *o, const WnArgs &a, const int *H, int n_levels, long long channels)
+{
+    WnStrips st;
+    size_t lds = 0;
+    o[1] = wn_strips<M>(&st, a, H, n_levels, channels, 1, &lds, M, &o[0]);
+    for (int l = 0; l < n_levels; ++l) {
+        const int th = (H[l] + M - 1) / M, tw = a.lv[l].tw;
+        int *q = o + 2 + 4 * l;
+        q[0] = st.segs[l]; q[1] = st.rows[l];
+        q[2] = th % st.rows[l];                                      // a last strip with fewer tile rows than the others (a level of one short strip included)
+        q[3] = tw % Wn<M>::WT;                                       // a last segment with fewer tiles than WT
+    }
+}
+FRCNN_EXPORT int frcnn_conv3x3_f32_plan(const int *H_host, const int *W_host, int n_levels, int Cin, int Cout, int *plan_host, int plan_len)
+{
+    static_assert(FRCNN_CONV_PLAN_MAX_LEVELS == FRCNN_MAX_LEVELS, "the plan's per-level records");
+    FRCNN_REQUIRE(H_host && W_host && plan_host, "conv3x3_f32_plan: NULL pointer");
+    FRCNN_REQUIRE(plan_len >= FRCNN_CONV_PLAN_INTS, "conv3x3_f32_plan: plan_len %d < %d", plan_len, FRCNN_CONV_PLAN_INTS);
+    FRCNN_REQUIRE(n_levels >= 1 && n_levels <= FRCNN_MAX_LEVELS, "conv3x3_f32_plan: 1 <= n_levels <= %d", FRCNN_MAX_LEVELS);
+    for (int l = 0; l < n_levels; ++l) FRCNN_REQUIRE(H_host[l] > 0 && W_host[l] > 0, "conv3x3_f32_plan: bad level %d", l);
+    if (!frcnn_conv3x3_f32_supported(H_host, W_host, n_levels, Cin, Cout, 0))
+        return frcnn_set_error(FRCNN_ERR_UNSUPPORTED, "conv3x3_f32_plan: the forward does not take Cin=%d / Cout=%d on these shapes", Cin, Cout);
+    const bool grads = frcnn_conv3x3_f32_supported(H_host, W_host, n_levels, Cin, Cout, 1) != 0;
+    for (int i = 0; i < FRCNN_CONV_PLAN_INTS; ++i) plan_host[i] = 0;
+    const int M = wn_pick_m(H_host, W_host, n_levels);
+    WnArgs a;
+    const long long Ttot = wn_fill(&a, M, nullptr, nullptr, H_host, W_host, n_levels);
+    int *o = plan_host;
+    o[0] = M; o[1] = a.tg; o[2] = (int)Ttot; o[3] = n_levels; o[4] = cf_ranges(); o[5] = wn_ranges_nt(); o[6] = M == 4 ? 1 : 0;
+    o += FRCNN_CONV_PLAN_HEAD;
+    const WnProduct pr[3] = {wn_product(M, Cout, Cin, Ttot, a.tg), grads ? wn_product(M, Cin, Cout, Ttot, a.tg) : WnProduct{},
+                             grads ? wn_wgrad_product(M, Cin, Cout, Ttot) : WnProduct{}};
+    for (int k = 0; k < 3; ++k, o += FRCNN_CONV_PLAN_PRODUCT) {
+        if (k > 0 && !grads) continue;
+        const WnProduct &p = pr[k];
+        o[0] = 1; o[1] = p.MT; o[2] = p.NW; o[3] = p.n_m_tiles; o[4] = p.n_t_tiles; o[5] = p.Kc; o[6] = (int)p.n_tiles; o[7] = (int)p.units; o[8] = p.G; o[9] = p.sched;
+    }
+    for (int k = 0; k < 2; ++k, o += FRCNN_CONV_PLAN_STRIPS) {
+        if (M == 4) wn_plan_strips<4>(o, a, H_host, n_levels, k ? Cout : Cin);
+        else wn_plan_strips<2>(o, a, H_host, n_levels, k ? Cout : Cin);
+    }
+    return FRCNN_OK;
 }
 
 FRCNN_EXPORT int frcnn_conv3x3_f32_tile_size(const int *H_host, const int *W_host, int n_levels)
@@ -2109,15 +2190,13 @@ static int wn_wgrad(const float *const *feats, const float *const *d_outs, const
                     float *dw, float *dbias, const float *xt, void *workspace, hipStream_t s, bool pooled = false, const float *dm_in = nullptr,
                     const WnOutLater *later = nullptr)
 {
-    constexpr int P = Wn<M>::P;
     WnArgs a;
     const long long Ttot = wn_fill(&a, M, feats, nullptr, H, W, n_levels);
     FRCNN_REQUIRE(Ttot < (1ll << 24), "conv3x3_f32_wgrad: %lld output tiles are too many", Ttot);
     const CfWs ws = wn_carve(workspace, Cin, Cout, M, Ttot);
-    const int MT = Cout % CF_MT == 0 ? CF_MT : 64, NW = Cin % CF_NT == 0 ? CF_NT : 64;
-    const int mt = Cout / MT, nt = Cin / NW, C9 = ((std::max(Cin, Cout) + CF_MT - 1) / CF_MT) * CF_MT;     // ws.wt holds C9^2 * 9 floats
-    const long long n_tiles = (long long)P * mt * nt, Kc = Ttot / WN_KC, units = n_tiles * Kc;
-    FRCNN_REQUIRE(n_tiles <= CF_MAX_TILES && units < (1ll << 31), "conv3x3_f32_wgrad: %lld tiles above the limit %d", n_tiles, CF_MAX_TILES);
+    const WnProduct pr = wn_wgrad_product(M, Cin, Cout, Ttot);
+    const int MT = pr.MT, NW = pr.NW, C9 = ((std::max(Cin, Cout) + CF_MT - 1) / CF_MT) * CF_MT;            // ws.wt holds C9^2 * 9 floats
+    FRCNN_REQUIRE(wn_product_ok(pr), "conv3x3_f32_wgrad: %lld tiles above the limit %d", pr.n_tiles, CF_MAX_TILES);
     WnStrips st;
     a.C = Cin; a.zero_pad = 1;
     size_t lds = 0;
@@ -2143,8 +2222,8 @@ static int wn_wgrad(const float *const *feats, const float *const *d_outs, const
         if constexpr (M == 4) FRCNN_LAUNCH((rpn_wino_input_kernel<4, 1, true>), dim3((unsigned)n_strips, (unsigned)Cout), dim3(256), lds, s, g1, st, ws.M);
     } else FRCNN_LAUNCH((rpn_wino_input_kernel<M, 1, false>), dim3((unsigned)n_strips, (unsigned)Cout), dim3(256), lds, s, g1, st, ws.M);
     FRCNN_CHECK_LAUNCH("rpn_wino_input_kernel");
-    WgArgs g = {dm_in ? dm_in : ws.M, xt ? xt : ws.V, ws.U, Ttot * Cout, Ttot * Cin, (long long)Cout * Cin, (int)Ttot, (int)Ttot, Cin, mt, nt, (int)Kc, (int)units,
-                (int)std::min<long long>(wn_ranges_nt(), units), 0};
+    WgArgs g = {dm_in ? dm_in : ws.M, xt ? xt : ws.V, ws.U, Ttot * Cout, Ttot * Cin, (long long)Cout * Cin, (int)Ttot, (int)Ttot, Cin, pr.n_m_tiles, pr.n_t_tiles, pr.Kc,
+                (int)pr.units, pr.G, pr.whole};
     bool both = false;
     if (later && later->gemm_pending) {
         // the data gradient's product, which that call left to this one: one launch for both where the pair of tile shapes is built, else its own launch first

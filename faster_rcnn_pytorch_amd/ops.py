@@ -1142,6 +1142,36 @@ def conv3x3_supported(x, weight, need_input_grad=None):
     return bool(lib.frcnn_conv3x3_f32_supported(_np_ptr(Hh), _np_ptr(Wh), 1, Cin, Cout, 1 if grads else 0))       # channel multiples and the control block's limits
 
 
+CONV3X3_SCHEDULES = ("stream_k", "whole_ranges", "one_tile", "fused_out64")       # FRCNN_CONV_SCHED_*
+
+
+def conv3x3_plan(shapes, Cin, Cout, device=None):
+    """What conv3x3_fwd / _bwd_data / _wgrad execute for levels of sizes shapes = [(h, w), ...] (frcnn_conv3x3_f32_plan: the host functions the launches use;
+    nothing is launched).  device: the HIP device whose CU count decides the workgroup slots (default: the current one; without a device 256 CUs).
+    Returns a dict: tile (2 | 4), tg (64 | 128), padded_tiles, G (slots of the forward's / data gradient's product), G_wgrad, pool (the pooled forms are
+    available), fwd / bwd_data / wgrad = None where the call does not take the shapes, else a dict tile_h, tile_w, m_tiles, t_tiles, Kc, n_tiles, units, G,
+    schedule (one of CONV3X3_SCHEDULES), and strips_in / strips_out (the transform launches over Cin / Cout channels) = a dict per_block, n_strips, levels =
+    [dict segments, rows, last_strip_rows (0: full), last_segment_tiles (0: full)]."""
+    Hh, Wh = _host_i32([h for h, _ in shapes]), _host_i32([w_ for _, w_ in shapes])
+    HEAD, PROD, STRIPS, n = 8, 10, 2 + 4 * 8, len(shapes)
+    out = np.zeros(HEAD + 3 * PROD + 2 * STRIPS, dtype=np.int32)
+    if device is not None and torch.device(device).type == "cuda":
+        with torch.cuda.device(device):
+            check(lib.frcnn_conv3x3_f32_plan(_np_ptr(Hh), _np_ptr(Wh), n, int(Cin), int(Cout), _np_ptr(out), out.size), "conv3x3_f32_plan")
+    else:
+        check(lib.frcnn_conv3x3_f32_plan(_np_ptr(Hh), _np_ptr(Wh), n, int(Cin), int(Cout), _np_ptr(out), out.size), "conv3x3_f32_plan")
+    v = [int(t) for t in out]
+    plan = {"tile": v[0], "tg": v[1], "padded_tiles": v[2], "G": v[4], "G_wgrad": v[5], "pool": bool(v[6])}
+    for k, name in enumerate(("fwd", "bwd_data", "wgrad")):
+        p = v[HEAD + k * PROD:HEAD + (k + 1) * PROD]
+        plan[name] = dict(zip(("tile_h", "tile_w", "m_tiles", "t_tiles", "Kc", "n_tiles", "units", "G"), p[1:9]), schedule=CONV3X3_SCHEDULES[p[9]]) if p[0] else None
+    for k, name in enumerate(("strips_in", "strips_out")):
+        s = v[HEAD + 3 * PROD + k * STRIPS:HEAD + 3 * PROD + (k + 1) * STRIPS]
+        plan[name] = {"per_block": s[0], "n_strips": s[1],
+                      "levels": [dict(zip(("segments", "rows", "last_strip_rows", "last_segment_tiles"), s[2 + 4 * l:6 + 4 * l])) for l in range(n)]}
+    return plan
+
+
 class _Conv3x3F32Fn(torch.autograd.Function):
     """args: (act, w, bias | None, x) -> act(bias + conv3x3(x, w)), act = 0 none / 1 ReLU / 2 ReLU + max_pool2d(2, 2); the activation's backward
     rides in the gradient kernels' transforms."""

@@ -254,6 +254,29 @@ size_t frcnn_conv3x3_f32_relu_bits_words(const int *H_host, const int *W_host, i
 int frcnn_conv3x3_f32_tile_size(const int *H_host, const int *W_host, int n_levels);
 /* 1 when _fwd (and, with need_grads, _bwd_data and _wgrad) would accept these shapes, else 0: the question a caller's dispatch asks before routing a layer here. */
 int frcnn_conv3x3_f32_supported(const int *H_host, const int *W_host, int n_levels, int Cin, int Cout, int need_grads);
+/* What the three calls would execute for these shapes, from the host functions the launches themselves use; launches nothing (without a device: 256 CUs).
+ * plan_host receives FRCNN_CONV_PLAN_INTS ints (plan_len >= that):
+ *   head     [0] output tile size m (2 or 4)   [1] tile padding tg (64 or 128)   [2] padded tile total   [3] n_levels   [4] workgroup slots of the forward's /
+ *            data gradient's product   [5] of the weight gradient's   [6] 1 when the pooled forms (relu = 2, pooled = 1) are available (m = 4)   [7] 0
+ *   products three of FRCNN_CONV_PLAN_PRODUCT ints at FRCNN_CONV_PLAN_HEAD: forward, data gradient, weight gradient
+ *            [0] 1 when the call accepts the shapes (else the rest is 0)   [1] product tile height   [2] width   [3] tiles along the channel side   [4] along the
+ *            other side   [5] K chunks of 32   [6] n_tiles   [7] units = n_tiles x chunks   [8] G = workgroups launched   [9] schedule (FRCNN_CONV_SCHED_*)
+ *   strips   two of FRCNN_CONV_PLAN_STRIPS ints behind the products: the transform launches over Cin channels (forward's input, the weight gradient's
+ *            activations) and over Cout channels (the output gradient)
+ *            [0] per_block the strips settled on   [1] strips per channel   then per level (FRCNN_CONV_PLAN_MAX_LEVELS x 4; zeros past n_levels)
+ *            [0] segments per tile row   [1] tile rows per strip   [2] tile rows of the last strip where it is partial, else 0   [3] tiles of the last segment
+ *            where it is partial, else 0
+ * Returns FRCNN_OK, or FRCNN_ERR_UNSUPPORTED / FRCNN_ERR_INVALID_ARG where the forward would not take the shapes. */
+#define FRCNN_CONV_SCHED_STREAM_K 0        /* ranges of K chunks across tile boundaries: partial tiles, slabs, tickets */
+#define FRCNN_CONV_SCHED_WHOLE_RANGES 1    /* several tiles per workgroup, ranges cut at tile boundaries */
+#define FRCNN_CONV_SCHED_ONE_TILE 2        /* one whole tile per workgroup, G = n_tiles */
+#define FRCNN_CONV_SCHED_FUSED_OUT64 3     /* 64 -> 64 on the 4 x 4 tile: product and output transform in one kernel (no product tiles: [6]..[8] are what the unfused product would have) */
+#define FRCNN_CONV_PLAN_MAX_LEVELS 8
+#define FRCNN_CONV_PLAN_HEAD 8
+#define FRCNN_CONV_PLAN_PRODUCT 10
+#define FRCNN_CONV_PLAN_STRIPS (2 + 4 * FRCNN_CONV_PLAN_MAX_LEVELS)
+#define FRCNN_CONV_PLAN_INTS (FRCNN_CONV_PLAN_HEAD + 3 * FRCNN_CONV_PLAN_PRODUCT + 2 * FRCNN_CONV_PLAN_STRIPS)
+int frcnn_conv3x3_f32_plan(const int *H_host, const int *W_host, int n_levels, int Cin, int Cout, int *plan_host, int plan_len);
 /* How the stage's products (M = U . V per Winograd plane; the weight gradient's dU = dM . V^T) are taken -- a process-wide switch, 0 by default:
  *   0  v_mfma_f32_32x32x2_f32 on the fp32 operands;
  *   1  the same fp32 operands cut into three bf16 pieces each in registers (exactly) and six v_mfma_f32_32x32x16_bf16 per 16 k rows, fp32 accumulation:

@@ -1918,12 +1918,21 @@ def test_conv3x3_f32_fused_relu_maxpool(ops, Cin, Cout, H, W):
         ops.conv3x3_wgrad([small], [torch.zeros(1, 128, 6, 10, device=DEV)], bits_small, pooled=True)
 
 
-@pytest.mark.parametrize("Cout,H,W", [(64, 75, 130), (32, 9, 700), (80, 33, 257), (64, 600, 1000)], ids=["vgg_like", "wide", "two_words", "vgg_conv1_1_full"])
+@pytest.mark.parametrize("Cout,H,W", [(64, 75, 130), (32, 9, 700), (80, 33, 257), (64, 600, 1000), (64, 129, 20), (64, 7, 256), (48, 5, 512), (64, 1, 1)],
+                         ids=["vgg_like", "wide", "two_words", "vgg_conv1_1_full", "tall_short_last_block", "one_forward_block_wide", "two_forward_blocks_wide", "one_pixel"])
 def test_conv3x3_c3_first_convolution(ops, Cout, H, W):
     """frcnn_conv3x3_c3_fwd / _wgrad: `vgg16.features[0]` + `[1]` (Conv2d(3, 64, 3, padding=1) + ReLU) and their backward -- weight and bias
     gradient, the ReLU's backward from the forward's sign words -- against float64 (mask from the device output) and, through
-    ops.conv3x3_c3 under autograd, against torch's own conv2d + relu on the device; bit-reproducible."""
+    ops.conv3x3_c3 under autograd, against torch's own conv2d + relu on the device; bit-reproducible.
+    The weight gradient puts several image rows in a block only where H x (groups of 32 channels) exceeds the CU count (frcnn_conv3x3_c3_wgrad):
+    H = 600 takes five rows, which divide it; H = 129 with 64 channels takes two on 256 CUs and leaves ONE row to the last block.  W = 256 and 512 are
+    the forward's block width exactly (no partial block), 1 x 1 is a map that is all border."""
     import torch.nn.functional as F
+    if (Cout, H, W) == (64, 129, 20):
+        cus = torch.cuda.get_device_properties(DEV).multi_processor_count         # hipDeviceAttributeMultiprocessorCount, what the launch asks
+        rows = max(1, min((150 * 1024) // (12 * (W + 2)) - 2, -(-H * ((Cout + 31) // 32) // cus)))
+        print("\n[c3 tall] %d CUs: %d rows per block, %d blocks, %d rows in the last" % (cus, rows, -(-H // rows), H - (-(-H // rows) - 1) * rows))
+        assert cus != 256 or (rows == 2 and H % rows == 1)
     g = torch.Generator().manual_seed(Cout + W)
     x = torch.randn(1, 3, H, W, generator=g)
     wt = torch.randn(Cout, 3, 3, 3, generator=g) * 0.3
