@@ -117,6 +117,9 @@ SIGNATURES = {
     "frcnn_grad_norm_workspace_bytes": (_sz, [_i]),
     "frcnn_grad_norm": (_i, [_vp, _sz, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "frcnn_sgd_step_scaled": (_i, [_vp, _sz, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    "frcnn_grad_accum_rows_per_launch": (_i, []),
+    "frcnn_grad_accumulate": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "frcnn_grad_accum_advance": (_i, [_vp, _vp, _vp]),
     "frcnn_diag_occupy": (_i, [_i, _i, _vp]),
     "frcnn_prof_enable": (_i, [_i]),
     "frcnn_prof_collect": (_i, []),

@@ -7,7 +7,8 @@
 //     how large a bucket can get (round 3, 14:49: DESIGN.md section 7);
 //   * SgdHeader / SgdRow + SGD_CHUNK / SGD_THREADS (sgd_dev.h): the optimizer's table, BUILT in sgd.hip and walked by the kernels of sgd.hip
 //     and grad_norm.hip; frcnn_grad_norm_state (include/frcnn_hip.h): written by grad_norm.hip, its coef and skip words read by sgd.hip's
-//     kernels through pointers the caller derives from the same struct;
+//     kernels through pointers the caller derives from the same struct; frcnn_grad_accum_state (include/frcnn_hip.h): written by
+//     grad_accum.hip, its hold word read by the same kernels as their skip word or user guard;
 //   * the profiling table size and the ABI version.
 // Every object registers its stamp in a static initialiser; frcnn_layout_check() (api.cpp; also run by frcnn_abi_version()) compares
 // them all with api.cpp's own and names the object that disagrees -- the library then refuses to load (FRCNN_ERR_UNSUPPORTED) instead of
@@ -48,6 +49,9 @@ constexpr uint64_t frcnn_layout_stamp_value()
     LAY(offsetof(frcnn_grad_norm_state, sumsq)); LAY(offsetof(frcnn_grad_norm_state, norm)); LAY(offsetof(frcnn_grad_norm_state, coef));
     LAY(offsetof(frcnn_grad_norm_state, skip)); LAY(offsetof(frcnn_grad_norm_state, nonfinite)); LAY(offsetof(frcnn_grad_norm_state, steps));
     LAY(offsetof(frcnn_grad_norm_state, skipped_steps)); LAY(FRCNN_GRAD_NORM_FINISH_THREADS);
+    LAY(sizeof(frcnn_grad_accum_state)); LAY(offsetof(frcnn_grad_accum_state, window)); LAY(offsetof(frcnn_grad_accum_state, phase));
+    LAY(offsetof(frcnn_grad_accum_state, live)); LAY(offsetof(frcnn_grad_accum_state, hold)); LAY(offsetof(frcnn_grad_accum_state, windows));
+    LAY(offsetof(frcnn_grad_accum_state, frames)); LAY(offsetof(frcnn_grad_accum_state, dropped)); LAY(FRCNN_GRAD_ACCUM_ROWS);
 #ifdef FRCNN_LAYOUT_TEST_SKEW          // tests/test_cabi.py builds ONE object with this defined and expects the library to refuse to load
     LAY(FRCNN_LAYOUT_TEST_SKEW);
 #endif
@@ -68,6 +72,11 @@ static_assert(sizeof(frcnn_grad_norm_state) == 64 && offsetof(frcnn_grad_norm_st
                   offsetof(frcnn_grad_norm_state, nonfinite) == 28 && offsetof(frcnn_grad_norm_state, steps) == 32 &&
                   offsetof(frcnn_grad_norm_state, skipped_steps) == 36,
               "frcnn_grad_norm_state: the offsets include/frcnn_hip.h documents (optim.py reads the block by them)");
+static_assert(sizeof(frcnn_grad_accum_state) == 64 && offsetof(frcnn_grad_accum_state, window) == 0 && offsetof(frcnn_grad_accum_state, phase) == 4 &&
+                  offsetof(frcnn_grad_accum_state, live) == 8 && offsetof(frcnn_grad_accum_state, hold) == 12 &&
+                  offsetof(frcnn_grad_accum_state, windows) == 16 && offsetof(frcnn_grad_accum_state, frames) == 20 &&
+                  offsetof(frcnn_grad_accum_state, dropped) == 24,
+              "frcnn_grad_accum_state: the offsets include/frcnn_hip.h documents (optim.py reads the block by them; hold is sgd.hip's skip word)");
 
 void frcnn_layout_register(const char *object, uint64_t stamp);
 int frcnn_layout_check_impl(void);

@@ -19,6 +19,9 @@ it reads the gradient: no extra pass over the gradients, `p.grad` is NOT scaled 
 launches whatever the tensors are.  `max_grad_norm` is a Python float that `push_hyper()` carries to the device like the lr.  With both
 options off nothing changes: the same two launches and no further allocation.
 
+GradAccumulator (csrc/grad_accum.hip) sums the gradients of a window of K frames in front of ONE update -- write, add or leave a frame out,
+decided on the device -- and its `hold` word is the guard that keeps the update off until a window with a live frame has closed.
+
 There is no fallback: anything the kernel does not cover (dampening, Nesterov, maximize, non-fp32, sparse or non-contiguous tensors or
 gradients, a trainable parameter without a gradient, CPU tensors) is refused with an exception."""
 import ctypes as C
@@ -69,17 +72,128 @@ GN_STATE_FORMAT = "<fIdffiiii24x"
 GN_CLIP, GN_SKIP_NONFINITE = 1, 2
 
 
-def _check_dense(t, what, device=None):
+def _check_dense(t, what, device=None, who="DeviceSGD", role="the optimizer"):
     if not torch.is_tensor(t) or t.layout != torch.strided or t.is_sparse:
-        raise TypeError("DeviceSGD: %s is not a dense strided tensor" % what)
+        raise TypeError("%s: %s is not a dense strided tensor" % (who, what))
     if t.device.type != "cuda":
-        raise RuntimeError("DeviceSGD: %s is on %s: the optimizer runs only on a HIP device (no CPU fallback)" % (what, t.device))
+        raise RuntimeError("%s: %s is on %s: %s runs only on a HIP device (no CPU fallback)" % (who, what, t.device, role))
     if device is not None and t.device != device:
-        raise RuntimeError("DeviceSGD: %s is on %s, the optimizer's tensors are on %s" % (what, t.device, device))
+        raise RuntimeError("%s: %s is on %s, %s's tensors are on %s" % (who, what, t.device, role, device))
     if t.dtype != torch.float32:
-        raise TypeError("DeviceSGD: %s is %s: fp32 only" % (what, t.dtype))
+        raise TypeError("%s: %s is %s: fp32 only" % (who, what, t.dtype))
     if not t.is_contiguous():
-        raise TypeError("DeviceSGD: %s is not contiguous (dense tensors only)" % what)
+        raise TypeError("%s: %s is not contiguous (dense tensors only)" % (who, what))
+
+
+# the state block of csrc/grad_accum.hip (frcnn_grad_accum_state, include/frcnn_hip.h): byte offsets, and the whole block for struct.unpack
+GA_STATE_BYTES, GA_OFF_WINDOW, GA_OFF_PHASE, GA_OFF_LIVE, GA_OFF_HOLD, GA_OFF_WINDOWS = 64, 0, 4, 8, 12, 16
+GA_STATE_FORMAT = "<iiiiiii36x"
+GA_STATE_KEYS = ("window", "phase", "live", "hold", "windows", "frames", "dropped")
+
+
+class GradAccumulator(object):
+    """GradAccumulator(window, device, frame_skip=None): gradient accumulation over a window of `window` frames whose state lives in
+    device memory (csrc/grad_accum.hip), so that ONE captured graph serves every micro-step of every window.
+
+        acc = GradAccumulator(K, device, frame_skip=slot.empty)
+        opt = DeviceSGD(params, ..., guard=acc.hold)          # p.grad are the tensors `accs` below
+        per frame:  acc.accumulate(accs, grads)               # one call per group of tensors; all calls of a frame see the same phase
+                    acc.advance()                             # once per frame, behind the last accumulate
+                    opt.step()                                # may be attempted after EVERY frame: hold keeps it a no-op until a window closes
+
+    A window's first frame WRITES the accumulators (they are not read: nothing has to be zeroed between windows), every later frame adds,
+    one rounding per element -- the bits of torch's `grad.add_(g)`.  `frame_skip`: a one-element int32 device tensor (typically a
+    FrameSlot's `empty`); while it is non-zero the frame is left out: its gradients are not read (they may be NaN), it contributes zero, and
+    the divisor of the mean stays `window` (the caller seeds its backward with 1 / window).  A window whose frames were all left out
+    closes with hold == 1: the optimizer does not step.  These are this project's definitions: the reference has no accumulation and
+    raises on a frame without boxes (docs/PARITY.md).
+
+    The host keeps a mirror of the phase (`closing`): advance() moves both when it runs eagerly.  Under capture it only records the
+    launch -- nothing runs, so neither moves; whoever replays a graph that holds an advance() calls tick() once per replay.  The window
+    state is not checkpointed: a resumed run starts a new window.  There is no CPU fallback."""
+
+    def __init__(self, window, device, frame_skip=None):
+        if isinstance(window, bool) or not isinstance(window, int) or window < 1:
+            raise ValueError("GradAccumulator: window must be an int >= 1, got %r" % (window,))
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("GradAccumulator: device %s: the accumulation runs only on a HIP device (no CPU fallback)" % self.device)
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        if frame_skip is not None:
+            if not torch.is_tensor(frame_skip) or frame_skip.dtype != torch.int32 or frame_skip.numel() != 1 or frame_skip.device != self.device:
+                raise TypeError("GradAccumulator: frame_skip must be a one-element int32 tensor on %s" % self.device)
+        self.window, self.frame_skip = window, frame_skip
+        with torch.no_grad():
+            self._state = torch.zeros(GA_STATE_BYTES, dtype=torch.uint8, device=self.device)      # one address for good
+            self._state[GA_OFF_WINDOW:GA_OFF_WINDOW + 4].view(torch.int32).fill_(window)
+        self.hold = self._state[GA_OFF_HOLD:GA_OFF_HOLD + 4].view(torch.int32)
+        self._phase = 0
+
+    @property
+    def closing(self):
+        """Host bool: the next advance() closes a window."""
+        return self._phase == self.window - 1
+
+    def _pointers(self):
+        skip = C.c_void_p(self.frame_skip.data_ptr()) if self.frame_skip is not None else None
+        return C.c_void_p(self._state.data_ptr()), skip, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def accumulate(self, accs, grads):
+        """One frcnn_grad_accumulate call: accs[i] = grads[i], or += grads[i], or nothing -- the table in the class docstring, decided on
+        the device.  Dense contiguous fp32 tensors on this device, of equal shapes; anything else is refused."""
+        accs, grads = list(accs), list(grads)
+        if len(accs) != len(grads):
+            raise ValueError("GradAccumulator: %d accumulators, %d gradients" % (len(accs), len(grads)))
+        if not accs:
+            return
+        for k, (a, g) in enumerate(zip(accs, grads)):
+            _check_dense(a, "accumulator %d" % k, self.device, "GradAccumulator", "the accumulation")
+            _check_dense(g, "gradient %d" % k, self.device, "GradAccumulator", "the accumulation")
+            if a.shape != g.shape:
+                raise RuntimeError("GradAccumulator: gradient %d has shape %s, its accumulator %s" % (k, tuple(g.shape), tuple(a.shape)))
+        n = len(accs)
+        vp = C.c_void_p * n
+        state, skip, stream = self._pointers()
+        spare = self._state.data_ptr()                                    # an empty tensor has no address; its row is legal but may not be NULL
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib.frcnn_grad_accumulate(n, vp(*[g.data_ptr() or spare for g in grads]), vp(*[a.data_ptr() or spare for a in accs]),
+                                                      (C.c_int64 * n)(*[a.numel() for a in accs]), state, skip, stream), "frcnn_grad_accumulate")
+
+    def tick(self):
+        """The host mirror alone: once per replay of a graph that holds an advance()."""
+        self._phase = (self._phase + 1) % self.window
+
+    def advance(self):
+        """Once per frame, behind its last accumulate(): frcnn_grad_accum_advance.  Run eagerly it moves the device state and the host
+        mirror; under capture it records the launch and moves neither (see tick())."""
+        state, skip, stream = self._pointers()
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib.frcnn_grad_accum_advance(state, skip, stream), "frcnn_grad_accum_advance")
+        if not torch.cuda.is_current_stream_capturing():
+            self.tick()
+
+    def _outside_graphs(self, what):
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("GradAccumulator: %s writes the state block from the host side and the stream is capturing: call it outside graphs" % what)
+
+    def reset_window(self):
+        """Phase and live count back to 0, on the device (stream-ordered, no synchronisation) and in the host mirror: the next frame opens
+        a window.  What the accumulators hold is overwritten by that frame.  Outside graphs only."""
+        self._outside_graphs("reset_window()")
+        with torch.no_grad():
+            self._state[GA_OFF_PHASE:GA_OFF_LIVE + 4].zero_()
+        self._phase = 0
+
+    def reset_stats(self):
+        """The running counters (windows, frames, dropped) back to 0, e.g. after the warm-up passes of a capture.  Outside graphs only."""
+        self._outside_graphs("reset_stats()")
+        with torch.no_grad():
+            self._state[GA_OFF_WINDOWS:GA_OFF_WINDOWS + 12].zero_()
+
+    def stats(self):
+        """The state block as a dict: window, phase, live, hold, windows, frames, dropped.  A device read-back: synchronises."""
+        return dict(zip(GA_STATE_KEYS, struct.unpack(GA_STATE_FORMAT, bytes(self._state.cpu().numpy()))))
 
 
 class DeviceSGD(torch.optim.Optimizer):

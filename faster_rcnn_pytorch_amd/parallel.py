@@ -219,13 +219,33 @@ class GraphStep(object):
 
     `forward_loss(f) -> (losses, pred)`: losses[0] is the scalar to minimise, pred the model's prediction tuple (pred[0], pred[1] = the
     RPN's class / box predictions).  `record(f, losses)` runs inside the capture right after the forward (copy what must survive the
-    shared memory pool).  With graphs=False every piece runs eagerly (CPU tensors, gloo: the world-size-2 tests) through the same code."""
+    shared memory pool).  With graphs=False every piece runs eagerly (CPU tensors, gloo: the world-size-2 tests) through the same code.
 
-    def __init__(self, model, optimizer, forward_loss, n_frames, device, cut_module=None, late_modules=(), record=None, graphs=True):
+    `accumulate=K` (default 1: nothing below applies, the code path is the one described above): gradient accumulation over windows of K
+    steps, decided on the device (optim.GradAccumulator, csrc/grad_accum.hip), in the SAME graph set.  The backward is seeded with
+    1 / (world * K) -- the gradient of loss / K, the torch idiom, and the mean over ranks as before; A and B run on every step and SUM
+    into the flat buffers (a window's first step writes them, the later ones add: the bits of `grad.add_(g)`); the two all-reduces and U
+    run only on the step that closes a window -- the host knows the phase, so the other steps issue no collective and replay no
+    optimizer graph.  `frame_skip=`: a one-element int32 device tensor, typically the FrameSlot's `empty`: a frame for which it is
+    non-zero is left out of its window -- its (NaN) gradients are not read, it contributes zero and the divisor stays K -- and a window
+    whose frames were ALL left out updates nothing.  That last decision is the accumulator's `hold` word, which the optimizer must read as
+    its guard.  The accumulator is made here, so the optimizer is HANDED OVER afterwards: construct with optimizer=None, build
+    `DeviceSGD(..., guard=gs.accumulator.hold)`, then `gs.set_optimizer(opt)`, before capture().  A DeviceSGD with any other guard
+    is refused.  (Another optimizer class does not read hold: it also steps after an all-empty window, on the zeros that window's first
+    step wrote.)  At world > 1 the closing step also all-reduces hold with MIN, so every rank takes the same
+    decision: step if any rank had a live frame; a rank whose window was empty contributes zeros.  The window state is not checkpointed: a
+    resumed run starts a new window (reset_window()).  Both are this project's definitions -- the reference has no accumulation and raises
+    on a frame without boxes (docs/PARITY.md).  K > 1 needs a HIP device."""
+
+    def __init__(self, model, optimizer, forward_loss, n_frames, device, cut_module=None, late_modules=(), record=None, graphs=True,
+                 accumulate=1, frame_skip=None):
         self.model, self.opt, self.forward_loss, self.n, self.device = model, optimizer, forward_loss, n_frames, device
         self.record = record
         self.graphs = bool(graphs) and device.type == "cuda"
         self.world = dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
+        self.accumulator, self.accumulate = None, 1
+        if type(accumulate) is not int or accumulate != 1 or frame_skip is not None:      # the default takes no step into the new code
+            self._init_accumulator(accumulate, frame_skip, device)
         params = [p for p in model.parameters() if p.requires_grad]                       # parameters() lists an aliased module's tensors once
         late_ids = {id(p) for m in late_modules for p in m.parameters() if p.requires_grad} if cut_module is not None else set()
         self.late = [p for p in params if id(p) in late_ids]
@@ -251,10 +271,46 @@ class GraphStep(object):
             self.flat.append(buf)
         for p in params:
             p.grad = self.views[id(p)]                                                    # for good: the optimizer graph reads these addresses
-        self.seed = torch.full((), 1.0 / self.world, dtype=torch.float32, device=device)
+        self.seed = torch.full((), 1.0 / (self.world * self.accumulate), dtype=torch.float32, device=device)
         self._cut = []
         self.gA, self.gB, self.gU = [], [], None
         self.comm_bytes = [0 if b is None else b.numel() * b.element_size() for b in self.flat]
+        if self.accumulator is not None and optimizer is not None:
+            self._check_guard(optimizer)
+
+    # ---- accumulation over a window of K steps (accumulate > 1)
+    def _init_accumulator(self, accumulate, frame_skip, device):
+        from .optim import GradAccumulator
+        if isinstance(accumulate, bool) or not isinstance(accumulate, int) or accumulate < 1:
+            raise ValueError("GraphStep: accumulate must be an int >= 1, got %r" % (accumulate,))
+        if accumulate == 1:
+            raise ValueError("GraphStep: frame_skip= is read by the accumulation only (accumulate > 1); with accumulate=1 a frame is "
+                             "left out by the optimizer's guard")
+        if torch.device(device).type != "cuda":
+            raise ValueError("GraphStep: accumulate=%d needs a HIP device, got %s (the accumulation has no CPU fallback)" % (accumulate, device))
+        self.accumulator, self.accumulate = GradAccumulator(accumulate, device, frame_skip=frame_skip), accumulate
+
+    def _check_guard(self, optimizer):
+        from .optim import DeviceSGD
+        if isinstance(optimizer, DeviceSGD):
+            g = optimizer.guard
+            if g is None or g.data_ptr() != self.accumulator.hold.data_ptr():
+                raise ValueError("GraphStep: with accumulate > 1 a DeviceSGD must be built with guard=<this GraphStep>.accumulator.hold (the "
+                                 "word that keeps the update a no-op until a window with a live frame has closed)")
+
+    def set_optimizer(self, optimizer):
+        """For an optimizer that could only be built after this object (guard=self.accumulator.hold).  Before capture()."""
+        if self.gU is not None:
+            raise RuntimeError("GraphStep: the optimizer's graph is captured already")
+        if self.accumulator is not None:
+            self._check_guard(optimizer)
+        self.opt = optimizer
+        return self
+
+    def reset_window(self):
+        """The next step opens a window (device state and host mirror); outside graphs.  A no-op with accumulate=1."""
+        if self.accumulator is not None:
+            self.accumulator.reset_window()
 
     # ---- the pieces (eager or under capture)
     def _stage_a(self, f):
@@ -274,6 +330,8 @@ class GraphStep(object):
         if self.cut_module is None:
             grads = torch.autograd.grad([total], self.early, [seed], allow_unused=True)
             self._store(self.early, grads)
+            if self.accumulator is not None:
+                self.accumulator.advance()
             return None
         cuts = [t for t in list(self._cut) + [pred[0], pred[1]] if torch.is_tensor(t) and t.requires_grad]
         del self._cut[:]
@@ -286,18 +344,29 @@ class GraphStep(object):
         roots, seeds = carry
         grads = torch.autograd.grad(roots, self.early, seeds, allow_unused=True)
         self._store(self.early, grads)
+        if self.accumulator is not None:
+            self.accumulator.advance()                  # once per step, behind the last _store: both stores saw the same phase
 
     def _store(self, params, grads):
         if any(g is None for g in grads):
             # torch's optimizers skip a parameter whose .grad is None (no weight decay, no momentum); a captured optimizer step cannot, so --
             # like DDP with find_unused_parameters=False (models/build.py:12) -- every trainable parameter must take part in the loss
             raise RuntimeError("GraphStep: %d trainable parameter(s) received no gradient" % sum(g is None for g in grads))
-        if params:
-            torch._foreach_copy_([self.views[id(p)] for p in params], list(grads))
+        if not params:
+            return
+        if self.accumulator is not None:                # write, add or leave out: decided on the device (a strided gradient is packed first, in the graph)
+            self.accumulator.accumulate([self.views[id(p)] for p in params], [g if g.is_contiguous() else g.contiguous() for g in grads])
+            return
+        torch._foreach_copy_([self.views[id(p)] for p in params], list(grads))
 
     def _reduce(self, k):
         if self.world > 1 and self.flat[k] is not None:
             return dist.all_reduce(self.flat[k], op=dist.ReduceOp.SUM, async_op=True)
+        return None
+
+    def _reduce_hold(self):
+        if self.world > 1:
+            return dist.all_reduce(self.accumulator.hold, op=dist.ReduceOp.MIN, async_op=True)
         return None
 
     # ---- capture
@@ -309,7 +378,7 @@ class GraphStep(object):
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
-            for _ in range(warm):
+            for _ in range(warm * self.accumulate):     # whole windows: the optimizer steps, the phase is back at 0
                 for f in range(self.n):
                     self._eager(f)
         torch.cuda.current_stream().wait_stream(side)
@@ -337,6 +406,9 @@ class GraphStep(object):
         with torch.cuda.graph(self.gU, pool=pool):
             self.opt.step()
         self.sync_state()
+        if self.accumulator is not None:
+            self.accumulator.reset_window()
+            self.accumulator.reset_stats()
         return self
 
     def sync_state(self):
@@ -352,6 +424,8 @@ class GraphStep(object):
                 dist.broadcast(t, 0)
 
     def _eager(self, f):
+        if self.accumulator is not None:
+            return self._eager_window(f)
         carry = self._stage_a(f)
         w0 = self._reduce(0)
         if carry is not None:
@@ -362,10 +436,39 @@ class GraphStep(object):
                 w.wait()
         self.opt.step()
 
+    def _eager_window(self, f):
+        closing = self.accumulator.closing              # read before stage A / B: their advance() moves the mirror
+        carry = self._stage_a(f)
+        w0 = self._reduce(0) if closing else None
+        if carry is not None:
+            self._stage_b(carry)
+        if closing:
+            self._close_window(w0)
+            self.opt.step()
+
+    def _close_window(self, w0):
+        for w in (w0, self._reduce(1), self._reduce_hold()):
+            if w is not None:
+                w.wait()
+
+    def _step_window(self, f):
+        """accumulate > 1: A and B on every step; the collectives and U only when the window closes."""
+        closing = self.accumulator.closing
+        self.gA[f].replay()
+        w0 = self._reduce(0) if closing else None
+        if self.gB[f] is not None:
+            self.gB[f].replay()
+        self.accumulator.tick()                         # the replayed advance() moved the device's phase
+        if closing:
+            self._close_window(w0)
+            self.gU.replay()
+
     def step(self, i):
         f = i % self.n
         if not self.graphs:
             return self._eager(f)
+        if self.accumulator is not None:
+            return self._step_window(f)
         self.gA[f].replay()
         w0 = self._reduce(0)                            # on the process group's stream, behind what the replay enqueued
         if self.gB[f] is not None:
@@ -379,4 +482,5 @@ class GraphStep(object):
     def report(self):
         return {"submission": "HIP graphs: A (forward + loss + head backward) | all-reduce | B (trunk backward) | all-reduce | optimizer" if self.graphs else "eager pieces",
                 "world": self.world, "head_gradient_bytes": self.comm_bytes[0], "trunk_gradient_bytes": self.comm_bytes[1],
-                "parameter_tensors": len(self.late) + len(self.early), "graphs": (len(self.gA) + sum(g is not None for g in self.gB) + 1) if self.graphs else 0}
+                "parameter_tensors": len(self.late) + len(self.early), "graphs": (len(self.gA) + sum(g is not None for g in self.gB) + 1) if self.graphs else 0,
+                "accumulate": self.accumulate}

@@ -810,6 +810,60 @@ int frcnn_grad_norm(const void *table, size_t table_bytes, int n_tensors, int n_
 int frcnn_sgd_step_scaled(const void *table, size_t table_bytes, int n_tensors, int n_chunks, const float *hyper, int n_groups, int32_t *born,
                           const int32_t *skip, const float *grad_scale, void *stream);
 
+/* ---- optimizer: gradient accumulation over a window of K frames, the window's state in device memory -----------------------------------
+ * The reference trains on one frame per update (train.py:31-37: forward, loss.backward(), optimizer.step()) and has no accumulation; the
+ * usual recipe for a larger effective batch is K backward passes of loss / K summed into .grad and ONE optimizer step.  Here the sum is
+ * formed by a multi-tensor launch whose decision -- write (a window's first frame), add (a later frame) or leave the frame out (a frame
+ * without boxes, whose gradients are NaN) -- is read from device memory, so one captured graph serves every micro-step of every window.
+ *
+ * The state block: 64 bytes of DEVICE memory, 16-byte aligned.  window is written by the caller outside any graph; the caller zeroes the
+ * rest once.  frcnn_grad_accumulate only READS the block; frcnn_grad_accum_advance is the one writer. */
+typedef struct {
+    int32_t window;          /*  0  in   K >= 1, written by the caller outside any graph */
+    int32_t phase;           /*  4  i/o  0 .. K-1: the micro-step inside the window */
+    int32_t live;            /*  8  i/o  frames of this window that contributed */
+    int32_t hold;            /* 12  out  written by advance: 1 unless this call closed a window with live > 0 */
+    int32_t windows;         /* 16  i/o  windows closed */
+    int32_t frames;          /* 20  i/o  advance calls */
+    int32_t dropped;         /* 24  i/o  frames left out (frame_skip != 0) */
+    int32_t reserved[9];     /* 28       not touched */
+} frcnn_grad_accum_state;
+#define FRCNN_GRAD_ACCUM_ROWS 96
+/* frcnn_grad_accumulate, fp32 only.  p = state->phase and s = frame_skip ? *frame_skip : 0 are read on the device, once per workgroup;
+ * then, for every element of every tensor:
+ *
+ *                              s == 0                                 s != 0
+ *   p == 0                     acc = src   (acc is NOT read)          acc = +0.0f   (neither is read)
+ *   0 < p < window             acc = acc + src, rounded once          nothing is read or written
+ *   p outside 0 .. window-1    nothing is touched                     nothing is touched
+ *
+ * One rounding per add: the bits of torch's grad.add_(g).  Only acc is written.  src_host / acc_host / numel_host are HOST arrays of
+ * n_tensors device pointers and element counts (the sources are typically autograd's gradient tensors, whose addresses exist only inside
+ * a capture, where nothing can be uploaded): the library hands them to its kernel BY VALUE in the kernel arguments, which a graph node
+ * stores, at most FRCNN_GRAD_ACCUM_ROWS rows per launch (frcnn_grad_accum_rows_per_launch returns that number).  The number of launches
+ * is ceil(n_tensors / rows per launch) minus the launches whose rows are all empty: it depends on the tensor list only, never on data.
+ * One workgroup of 256 threads per 8192-element chunk of a tensor; 16-byte accesses when both pointers of a row are 16-byte aligned,
+ * dword accesses for such a row's tail and for all of any other row.  No atomics, no workgroup waits on another.
+ *
+ * frcnn_grad_accum_advance, one small launch, is the window's bookkeeping (a call of its own because one micro-step may make several
+ * frcnn_grad_accumulate calls, which must all see the same phase):
+ *   1. frames += 1, dropped += (s != 0), live += (s == 0)
+ *   2. phase + 1 == window:  hold = (live == 0), windows += 1, phase = 0, live = 0
+ *   3. otherwise:            hold = 1, phase += 1
+ * (a block whose phase lies outside 0 .. window-1 is not ours: nothing is written).  Pass &state->hold as the `skip` word of
+ * frcnn_sgd_step, or as the user_guard of frcnn_grad_norm: an update attempted after every frame then happens exactly when a window
+ * with at least one live frame has closed.  A frame that is left out contributes zero; the divisor of the mean stays K (the caller
+ * seeds its backward with 1 / K).  tests/grad_accum_ref.py restates both functions in numpy.
+ *
+ * Both make no host synchronisation and are capturable.  FRCNN_ERR_INVALID_ARG before anything is launched: a NULL array or state,
+ * n_tensors outside 1 .. 65536, a negative size or one above 2^40, a NULL pointer in a row or one that is not 4-byte aligned, a state that
+ * is not 16-byte aligned, a frame_skip that is not 4-byte aligned, two overlapping acc ranges, a src range that overlaps any acc range.
+ * Tensors of size 0 are legal rows; if every tensor is empty nothing is launched. */
+int frcnn_grad_accum_rows_per_launch(void);
+int frcnn_grad_accumulate(int n_tensors, const void *const *src_host, void *const *acc_host, const int64_t *numel_host,
+                          const frcnn_grad_accum_state *state, const int32_t *frame_skip, void *stream);
+int frcnn_grad_accum_advance(frcnn_grad_accum_state *state, const int32_t *frame_skip, void *stream);
+
 /* ---- in-library kernel timing (HIP events on the launch stream) -------------------------------------- */
 /* When enabled, every kernel launch made by this library is bracketed by two hipEventRecord on the
  * caller's stream.  frcnn_prof_collect() synchronises those events (call it after the stream is idle)
