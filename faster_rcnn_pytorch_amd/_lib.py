@@ -120,6 +120,11 @@ SIGNATURES = {
     "frcnn_grad_accum_rows_per_launch": (_i, []),
     "frcnn_grad_accumulate": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "frcnn_grad_accum_advance": (_i, [_vp, _vp, _vp]),
+    "frcnn_ema_table_bytes": (_sz, [_i, _vp]),
+    "frcnn_ema_table_build_host": (_i, [_i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "frcnn_ema_update": (_i, [_vp, _sz, _i, _i, _vp, _vp, _vp]),
+    "frcnn_ema_swap": (_i, [_vp, _sz, _i, _i, _vp, _vp]),
+    "frcnn_sgd_step_ema": (_i, [_vp, _sz, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     "frcnn_diag_occupy": (_i, [_i, _i, _vp]),
     "frcnn_prof_enable": (_i, [_i]),
     "frcnn_prof_collect": (_i, []),

@@ -9,6 +9,9 @@
 //     and grad_norm.hip; frcnn_grad_norm_state (include/frcnn_hip.h): written by grad_norm.hip, its coef and skip words read by sgd.hip's
 //     kernels through pointers the caller derives from the same struct; frcnn_grad_accum_state (include/frcnn_hip.h): written by
 //     grad_accum.hip, its hold word read by the same kernels as their skip word or user guard;
+//   * EmaHeader / EmaRow (ema_dev.h): the weight average's table, BUILT in ema.hip and walked by the kernels of ema.hip and by sgd.hip's
+//     fused update; frcnn_ema_state (include/frcnn_hip.h): written by ema.hip's advance and swap kernels, its w and swapped words read by
+//     sgd.hip's kernels;
 //   * the profiling table size and the ABI version.
 // Every object registers its stamp in a static initialiser; frcnn_layout_check() (api.cpp; also run by frcnn_abi_version()) compares
 // them all with api.cpp's own and names the object that disagrees -- the library then refuses to load (FRCNN_ERR_UNSUPPORTED) instead of
@@ -20,6 +23,7 @@
 #include "frcnn_internal.h"
 #include "topk_dev.h"
 #include "sgd_dev.h"
+#include "ema_dev.h"
 
 constexpr uint64_t frcnn_lay_mix(uint64_t h, uint64_t v) { return (h ^ v) * 0x100000001b3ull; }
 
@@ -52,6 +56,10 @@ constexpr uint64_t frcnn_layout_stamp_value()
     LAY(sizeof(frcnn_grad_accum_state)); LAY(offsetof(frcnn_grad_accum_state, window)); LAY(offsetof(frcnn_grad_accum_state, phase));
     LAY(offsetof(frcnn_grad_accum_state, live)); LAY(offsetof(frcnn_grad_accum_state, hold)); LAY(offsetof(frcnn_grad_accum_state, windows));
     LAY(offsetof(frcnn_grad_accum_state, frames)); LAY(offsetof(frcnn_grad_accum_state, dropped)); LAY(FRCNN_GRAD_ACCUM_ROWS);
+    LAY(sizeof(EmaHeader)); LAY(sizeof(EmaRow)); LAY(offsetof(EmaRow, p)); LAY(offsetof(EmaRow, e)); LAY(offsetof(EmaRow, numel)); LAY(offsetof(EmaRow, vec));
+    LAY(sizeof(frcnn_ema_state)); LAY(offsetof(frcnn_ema_state, decay)); LAY(offsetof(frcnn_ema_state, num_updates)); LAY(offsetof(frcnn_ema_state, w));
+    LAY(offsetof(frcnn_ema_state, flags)); LAY(offsetof(frcnn_ema_state, swapped)); LAY(offsetof(frcnn_ema_state, skipped));
+    LAY(offsetof(frcnn_ema_state, refused));
 #ifdef FRCNN_LAYOUT_TEST_SKEW          // tests/test_cabi.py builds ONE object with this defined and expects the library to refuse to load
     LAY(FRCNN_LAYOUT_TEST_SKEW);
 #endif
@@ -77,6 +85,10 @@ static_assert(sizeof(frcnn_grad_accum_state) == 64 && offsetof(frcnn_grad_accum_
                   offsetof(frcnn_grad_accum_state, windows) == 16 && offsetof(frcnn_grad_accum_state, frames) == 20 &&
                   offsetof(frcnn_grad_accum_state, dropped) == 24,
               "frcnn_grad_accum_state: the offsets include/frcnn_hip.h documents (optim.py reads the block by them; hold is sgd.hip's skip word)");
+static_assert(sizeof(frcnn_ema_state) == 64 && offsetof(frcnn_ema_state, decay) == 0 && offsetof(frcnn_ema_state, num_updates) == 8 &&
+                  offsetof(frcnn_ema_state, w) == 16 && offsetof(frcnn_ema_state, flags) == 20 && offsetof(frcnn_ema_state, swapped) == 24 &&
+                  offsetof(frcnn_ema_state, skipped) == 28 && offsetof(frcnn_ema_state, refused) == 32,
+              "frcnn_ema_state: the offsets include/frcnn_hip.h documents (optim.py reads and writes the block by them)");
 
 void frcnn_layout_register(const char *object, uint64_t stamp);
 int frcnn_layout_check_impl(void);

@@ -25,6 +25,7 @@
 #include "frcnn_internal.h"
 #include "frcnn_layout.h"
 #include "sgd_dev.h"
+#include "ema_dev.h"
 #include <algorithm>
 #include <vector>
 FRCNN_LAYOUT_STAMP(sgd);
@@ -43,13 +44,27 @@ __device__ __forceinline__ float sgd_one(float p, float g, float *m, float neg_l
 // SCALE = false: the rule above on the gradient as it is.  SCALE = true: every gradient element is first multiplied by the device float
 // *grad_scale (one rounding, __fmul_rn) -- the bits of torch's in-place g.mul_(coef) followed by torch.optim.SGD; the gradient itself is
 // not written.
-template <bool SCALE>
+// EMA = true: the weight average (ema.hip, ema_dev.h) rides in the same pass: behind p' the kernel loads the shadow e, applies ema_one and
+// stores e' -- p' is still in registers, so the average costs 8 B per element instead of a 12 B pass of its own.  The EMA row of a tensor
+// stands under the same tensor number (the two maps are equal entry for entry); the shadow pointer is NOT covered by SgdRow.vec, so a row
+// takes the 16-byte path only when both rows say so.  While the state's swapped word is set the parameters hold the average: the whole
+// step changes nothing.  With EMA = false none of this is compiled in: the two instantiations of before are what they were.
+template <bool SCALE, bool EMA>
 __global__ __launch_bounds__(SGD_THREADS) void sgd_update_kernel(const SgdRow *__restrict__ rows, const int2 *__restrict__ map, int n_tensors,
                                                                  const float4 *__restrict__ hyper, int n_groups,
                                                                  const int32_t *__restrict__ born, const int32_t *__restrict__ skip,
-                                                                 const float *__restrict__ grad_scale)
+                                                                 const float *__restrict__ grad_scale, const EmaRow *__restrict__ erows,
+                                                                 const frcnn_ema_state *__restrict__ est)
 {
     if (skip && *skip != 0) return;
+    float w = 0.0f, wm1 = 0.0f;
+    bool small = false;
+    if (EMA) {
+        if (est->swapped != 0) return;
+        w = est->w;
+        wm1 = __fsub_rn(w, 1.0f);
+        small = fabsf(w) < 0.5f;
+    }
     float gs = 1.0f;
     if (SCALE) gs = *grad_scale;
     const int2 c = map[blockIdx.x];
@@ -65,14 +80,22 @@ __global__ __launch_bounds__(SGD_THREADS) void sgd_update_kernel(const SgdRow *_
     const bool use_wd = wd != 0.0f, keep = mu != 0.0f, first = born[c.x] == 0;
     float *p = r.p + off, *m = r.m + off;
     const float *g = r.g + off;
+    float *e = nullptr;
+    bool vec = r.vec != 0;
+    if (EMA) {
+        const EmaRow er = erows[c.x];
+        if (er.p != r.p || er.numel != r.numel) return;                    // an EMA table that is not this table's: touch nothing
+        e = er.e + off;
+        vec = vec && er.vec != 0;
+    }
     const int tid = threadIdx.x;
     int done = 0;
-    if (r.vec) {
-        sgd_f4 *p4 = (sgd_f4 *)p, *m4 = (sgd_f4 *)m;
+    if (vec) {
+        sgd_f4 *p4 = (sgd_f4 *)p, *m4 = (sgd_f4 *)m, *e4 = (sgd_f4 *)e;
         const sgd_f4 *g4 = (const sgd_f4 *)g;
         const int n4 = n >> 2;
         for (int base = 0; base < n4; base += 4 * SGD_THREADS) {
-            sgd_f4 vp[4], vg[4], vm[4];
+            sgd_f4 vp[4], vg[4], vm[4], ve[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const int i = base + k * SGD_THREADS + tid;
@@ -80,6 +103,7 @@ __global__ __launch_bounds__(SGD_THREADS) void sgd_update_kernel(const SgdRow *_
                     vp[k] = p4[i];
                     vg[k] = __builtin_nontemporal_load(&g4[i]);
                     if (keep && !first) vm[k] = m4[i];
+                    if (EMA) ve[k] = e4[i];
                 }
             }
 #pragma unroll
@@ -96,6 +120,12 @@ __global__ __launch_bounds__(SGD_THREADS) void sgd_update_kernel(const SgdRow *_
                     }
                     if (keep) m4[i] = mv;
                     p4[i] = q;
+                    if (EMA) {
+                        sgd_f4 a;
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) a[j] = ema_one(q[j], ve[k][j], w, wm1, small);
+                        e4[i] = a;
+                    }
                 }
             }
         }
@@ -104,18 +134,24 @@ __global__ __launch_bounds__(SGD_THREADS) void sgd_update_kernel(const SgdRow *_
     for (int i = done + tid; i < n; i += SGD_THREADS) {                     // the tail of an aligned tensor; all of a misaligned one
         float mv = 0.0f;
         if (keep && !first) mv = m[i];
+        float ev = 0.0f;
+        if (EMA) ev = e[i];
         const float ge = SCALE ? __fmul_rn(g[i], gs) : g[i];
         const float q = sgd_one(p[i], ge, &mv, neg_lr, mu, wd, use_wd, keep, first);
         if (keep) m[i] = mv;
         p[i] = q;
+        if (EMA) e[i] = ema_one(q, ev, w, wm1, small);
     }
 }
 
 // after the update: a tensor whose group keeps momentum has one now
+// (est: NULL, or the state of the weight average fused into the update: while its swapped word is set the step did not happen)
 __global__ __launch_bounds__(SGD_THREADS) void sgd_born_kernel(const SgdRow *__restrict__ rows, int n_tensors, const float4 *__restrict__ hyper, int n_groups,
-                                                               int32_t *__restrict__ born, const int32_t *__restrict__ skip)
+                                                               int32_t *__restrict__ born, const int32_t *__restrict__ skip,
+                                                               const frcnn_ema_state *__restrict__ est)
 {
     if (skip && *skip != 0) return;
+    if (est && est->swapped != 0) return;
     const int t = blockIdx.x * SGD_THREADS + threadIdx.x;
     if (t >= n_tensors) return;
     const int grp = rows[t].group;
@@ -204,37 +240,49 @@ FRCNN_EXPORT int frcnn_sgd_table_build_host(int n_tensors, const void *const *pa
 }
 
 static int sgd_step_launch(const char *who, const void *table, size_t table_bytes, int n_tensors, int n_chunks, const float *hyper, int n_groups, int32_t *born,
-                           const int32_t *skip, const float *grad_scale, bool scaled, void *stream)
+                           const int32_t *skip, const float *grad_scale, bool scaled, const void *ema_table, size_t ema_bytes,
+                           frcnn_ema_state *ema_state, bool ema, void *stream)
 {
-    FRCNN_REQUIRE(table && hyper && born && (!scaled || grad_scale), "%s: NULL pointer", who);
+    FRCNN_REQUIRE(table && hyper && born && (!scaled || grad_scale) && (!ema || (ema_table && ema_state)), "%s: NULL pointer", who);
     FRCNN_REQUIRE(n_tensors >= 1 && n_tensors <= SGD_MAX_TENSORS && n_chunks >= 0, "%s: bad counts (%d tensors, %d chunks)", who, n_tensors, n_chunks);
     FRCNN_REQUIRE(n_groups >= 1 && n_groups <= SGD_MAX_GROUPS, "%s: n_groups %d outside 1 .. %d", who, n_groups, SGD_MAX_GROUPS);
     FRCNN_REQUIRE(((uintptr_t)table & 15) == 0 && ((uintptr_t)hyper & 15) == 0 && ((uintptr_t)born & 3) == 0 && ((uintptr_t)skip & 3) == 0 &&
                       ((uintptr_t)grad_scale & 3) == 0,
                   "%s: table and hyper must be 16-byte aligned, born, skip and grad_scale 4-byte aligned", who);
+    FRCNN_REQUIRE(((uintptr_t)ema_table & 15) == 0 && ((uintptr_t)ema_state & 15) == 0, "%s: the EMA table and state must be 16-byte aligned", who);
     const size_t need = sgd_table_bytes(n_tensors, n_chunks);
     if (table_bytes < need) return frcnn_set_error(FRCNN_ERR_WORKSPACE, "%s: short table, %zu < %zu bytes", who, table_bytes, need);
-    if (n_chunks == 0) return FRCNN_OK;                                     // every tensor is empty
+    if (ema && ema_bytes < ema_table_bytes(n_tensors, n_chunks))
+        return frcnn_set_error(FRCNN_ERR_WORKSPACE, "%s: short EMA table, %zu < %zu bytes", who, ema_bytes, ema_table_bytes(n_tensors, n_chunks));
+    hipStream_t s = (hipStream_t)stream;
+    if (n_chunks == 0) return ema ? ema_advance_launch(ema_state, skip, s) : FRCNN_OK;      // every tensor is empty
     const SgdRow *rows = (const SgdRow *)((const char *)table + sizeof(SgdHeader));
     const int2 *map = (const int2 *)((const char *)table + sizeof(SgdHeader) + (size_t)n_tensors * sizeof(SgdRow));
-    hipStream_t s = (hipStream_t)stream;
-    if (scaled)
-        FRCNN_LAUNCH(sgd_update_kernel<true>, dim3((unsigned)n_chunks), dim3(SGD_THREADS), 0, s, rows, map, n_tensors, (const float4 *)hyper, n_groups,
-                     (const int32_t *)born, skip, grad_scale);
-    else
-        FRCNN_LAUNCH(sgd_update_kernel<false>, dim3((unsigned)n_chunks), dim3(SGD_THREADS), 0, s, rows, map, n_tensors, (const float4 *)hyper, n_groups,
-                     (const int32_t *)born, skip, (const float *)nullptr);
+    const EmaRow *erows = ema ? (const EmaRow *)((const char *)ema_table + sizeof(EmaHeader)) : nullptr;
+    const frcnn_ema_state *est = ema ? ema_state : nullptr;
+    const float *gs = scaled ? grad_scale : nullptr;
+#define SGD_UPDATE(S, E)                                                                                                                            \
+    FRCNN_LAUNCH((sgd_update_kernel<S, E>), dim3((unsigned)n_chunks), dim3(SGD_THREADS), 0, s, rows, map, n_tensors, (const float4 *)hyper, n_groups, \
+                 (const int32_t *)born, skip, gs, erows, est)
+    if (ema) {
+        if (scaled) SGD_UPDATE(true, true);
+        else SGD_UPDATE(false, true);
+    } else {
+        if (scaled) SGD_UPDATE(true, false);
+        else SGD_UPDATE(false, false);
+    }
+#undef SGD_UPDATE
     FRCNN_LAUNCH(sgd_born_kernel, dim3((unsigned)((n_tensors + SGD_THREADS - 1) / SGD_THREADS)), dim3(SGD_THREADS), 0, s, rows, n_tensors,
-                 (const float4 *)hyper, n_groups, born, skip);
+                 (const float4 *)hyper, n_groups, born, skip, est);
     FRCNN_CHECK_LAUNCH("sgd kernels");
-    return FRCNN_OK;
+    return ema ? ema_advance_launch(ema_state, skip, s) : FRCNN_OK;
 }
 
 // train.py:35-37 (optimizer.step()) for the optimizer main.py:58-61 constructs.  Two launches, no host synchronisation, capturable.
 FRCNN_EXPORT int frcnn_sgd_step(const void *table, size_t table_bytes, int n_tensors, int n_chunks, const float *hyper, int n_groups, int32_t *born,
                                 const int32_t *skip, void *stream)
 {
-    return sgd_step_launch("sgd_step", table, table_bytes, n_tensors, n_chunks, hyper, n_groups, born, skip, nullptr, false, stream);
+    return sgd_step_launch("sgd_step", table, table_bytes, n_tensors, n_chunks, hyper, n_groups, born, skip, nullptr, false, nullptr, 0, nullptr, false, stream);
 }
 
 // train.py:35-37 with the gradient clipping torch.nn.utils.clip_grad_norm_ would do in front of optimizer.step(): the same two launches,
@@ -242,5 +290,16 @@ FRCNN_EXPORT int frcnn_sgd_step(const void *table, size_t table_bytes, int n_ten
 FRCNN_EXPORT int frcnn_sgd_step_scaled(const void *table, size_t table_bytes, int n_tensors, int n_chunks, const float *hyper, int n_groups, int32_t *born,
                                        const int32_t *skip, const float *grad_scale, void *stream)
 {
-    return sgd_step_launch("sgd_step_scaled", table, table_bytes, n_tensors, n_chunks, hyper, n_groups, born, skip, grad_scale, true, stream);
+    return sgd_step_launch("sgd_step_scaled", table, table_bytes, n_tensors, n_chunks, hyper, n_groups, born, skip, grad_scale, true, nullptr, 0, nullptr, false,
+                           stream);
+}
+
+// train.py:35-37 with the weight average (ema.hip) fused into the update: either of the two above (grad_scale NULL or given), then the
+// average's one-thread bookkeeping: three launches, one skip word for all of them, no host synchronisation, capturable.
+FRCNN_EXPORT int frcnn_sgd_step_ema(const void *table, size_t table_bytes, int n_tensors, int n_chunks, const float *hyper, int n_groups, int32_t *born,
+                                    const int32_t *skip, const float *grad_scale, const void *ema_table, size_t ema_table_bytes, frcnn_ema_state *ema_state,
+                                    void *stream)
+{
+    return sgd_step_launch("sgd_step_ema", table, table_bytes, n_tensors, n_chunks, hyper, n_groups, born, skip, grad_scale, grad_scale != nullptr, ema_table,
+                           ema_table_bytes, ema_state, true, stream);
 }

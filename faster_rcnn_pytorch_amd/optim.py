@@ -22,8 +22,13 @@ options off nothing changes: the same two launches and no further allocation.
 GradAccumulator (csrc/grad_accum.hip) sums the gradients of a window of K frames in front of ONE update -- write, add or leave a frame out,
 decided on the device -- and its `hold` word is the guard that keeps the update off until a window with a live frame has closed.
 
+WeightEMA (csrc/ema.hip) keeps an exponential moving average of the trainable weights in device memory: fused into DeviceSGD's update
+kernel (`DeviceSGD(..., ema=)`: the kernel holds the new weight in registers when it stores it), gated by the same skip word as the step,
+and exchanged with the live weights IN PLACE by a kernel, so that graphs captured on the parameters evaluate the averaged weights.
+
 There is no fallback: anything the kernel does not cover (dampening, Nesterov, maximize, non-fp32, sparse or non-contiguous tensors or
 gradients, a trainable parameter without a gradient, CPU tensors) is refused with an exception."""
+import contextlib
 import ctypes as C
 import math
 import struct
@@ -196,8 +201,228 @@ class GradAccumulator(object):
         return dict(zip(GA_STATE_KEYS, struct.unpack(GA_STATE_FORMAT, bytes(self._state.cpu().numpy()))))
 
 
+# the state block of csrc/ema.hip (frcnn_ema_state, include/frcnn_hip.h): the whole block for struct.pack / unpack
+EMA_STATE_BYTES, EMA_STATE_FORMAT, EMA_WARMUP = 64, "<dqfIiii28x", 1
+EMA_STATE_KEYS = ("decay", "num_updates", "w", "flags", "swapped", "skipped", "refused")
+
+
+def ema_weight(decay, warmup, n):
+    """The weight of update number n (n updates applied so far) in binary64, as csrc/ema.hip computes it on the device:
+    decay_t = min(decay, (1 + n) / (10 + n)) under warm-up, else decay; w = 1 - decay_t.  The caller narrows it to float32."""
+    return 1.0 - (min(decay, (1 + n) / (10 + n)) if warmup else decay)
+
+
+def _trainable(params):
+    """Tensors or torch-style parameter groups -> the trainable parameters in DeviceSGD's row order."""
+    out = []
+    for item in params:
+        for p in (item["params"] if isinstance(item, dict) else (item,)):
+            if torch.is_tensor(p) and p.requires_grad:
+                out.append(p)
+    return out
+
+
+class WeightEMA(object):
+    """WeightEMA(params, decay=0.9998, warmup=True, guard=None, shadow=None): an exponential moving average of the trainable parameters,
+    kept and updated in device memory (csrc/ema.hip), for evaluating and checkpointing.  The reference evaluates the raw weights and keeps
+    no average: defined by this project, pinned to torch -- one update is torch._foreach_lerp_([e], [p], w) on the CPU bit for bit, which is
+    what torch.optim.swa_utils.AveragedModel(multi_avg_fn=get_ema_multi_avg_fn(decay)) runs (tests/golden/ema.npz, docs/PARITY.md).
+
+        ema = WeightEMA(params, decay=0.9998)
+        opt = DeviceSGD(params, ..., ema=ema)       # the average rides in the update kernel and reads the step's skip word
+        gs = GraphStep(model, opt, ...); gs.capture()
+        ema.reset()                                 # capture()'s warm-up steps moved the weights AND the average
+        ... train ...
+        with ema.applied():                         # live <-> averaged, in place, by a kernel: every captured graph stays valid
+            evaluate(model)
+        save_checkpoint(path, epoch, model, opt, sched, ema=ema)
+
+    `params`: tensors or parameter groups; the trainable ones (requires_grad) are averaged, in DeviceSGD's row order.  Frozen parameters and
+    buffers are NOT averaged: in both mirrors the buffers are the frozen norms' statistics, which never change.  `decay`: a Python float,
+    0 <= decay < 1, fixed here.  `warmup`: the weight of update n (n updates applied so far) is 1 - min(decay, (1 + n) / (10 + n)), so the
+    average follows the weights closely at first; computed on the device, so replays follow it.  `guard`: a one-element int32 device tensor
+    read by update() (a fused step reads the optimizer's skip word instead).  `shadow`: a list of caller tensors to average into (dense
+    contiguous fp32, the parameters' shapes, overlapping nothing); by default one contiguous tensor per parameter is allocated.  Either way
+    the shadows start as copies of the parameters and never move: load_state_dict copies INTO them.
+
+    A step that is skipped -- the accumulator's hold, a FrameSlot's empty, a non-finite gradient -- is decided on the device; the average
+    reads the same word, does not move and counts it (`skipped`).  Between swap() and swap() the parameters hold the averaged weights:
+    an update() or a fused step then changes NOTHING, parameters included, and is counted (`refused`).  With GraphStep(accumulate=K) the
+    average moves once per closed live window; under data parallelism every rank applies identical updates.  There is no CPU fallback;
+    a non-fp32, sparse or non-contiguous parameter is refused, and so is a list without a trainable parameter."""
+
+    def __init__(self, params, decay=0.9998, warmup=True, guard=None, shadow=None):
+        if torch.is_tensor(decay) or isinstance(decay, bool) or not isinstance(decay, (int, float)) or not 0.0 <= float(decay) < 1.0:
+            raise ValueError("WeightEMA: invalid decay: %r (a Python number, 0 <= decay < 1)" % (decay,))
+        self._decay, self.warmup = float(decay), bool(warmup)
+        self._params = _trainable(params)
+        if not self._params:
+            raise ValueError("WeightEMA: no trainable parameter")
+        self.device = self._params[0].device
+        for k, p in enumerate(self._params):
+            _check_dense(p, "parameter %d" % k, self.device if k else None, "WeightEMA", "the weight average")
+        if guard is not None:
+            if not torch.is_tensor(guard) or guard.dtype != torch.int32 or guard.numel() != 1 or guard.device != self.device:
+                raise TypeError("WeightEMA: guard must be a one-element int32 tensor on %s" % self.device)
+        self.guard = guard
+        n = len(self._params)
+        with torch.no_grad():
+            if shadow is None:
+                shadow = [torch.empty_like(p, memory_format=torch.contiguous_format) for p in self._params]
+            else:
+                shadow = list(shadow)
+                if len(shadow) != n:
+                    raise ValueError("WeightEMA: %d shadow tensors for %d trainable parameters" % (len(shadow), n))
+                for k, (e, p) in enumerate(zip(shadow, self._params)):
+                    _check_dense(e, "shadow %d" % k, self.device, "WeightEMA", "the weight average")
+                    if e.shape != p.shape:
+                        raise RuntimeError("WeightEMA: shadow %d has shape %s, its parameter %s" % (k, tuple(e.shape), tuple(p.shape)))
+                    if e.requires_grad:
+                        raise RuntimeError("WeightEMA: shadow %d requires grad" % k)
+            self.shadow = shadow                                              # allocated once; the kernels and every graph hold these addresses
+            self._state = torch.zeros(EMA_STATE_BYTES, dtype=torch.uint8, device=self.device)
+        self._numel = (C.c_int64 * n)(*[p.numel() for p in self._params])
+        self._table_bytes = int(_lib.lib.frcnn_ema_table_bytes(n, self._numel))
+        if self._table_bytes == 0:
+            raise _lib.FrcnnError("WeightEMA: frcnn_ema_table_bytes refuses %d tensors of these sizes" % n)
+        with torch.no_grad():
+            self._table = torch.empty(self._table_bytes, dtype=torch.uint8, device=self.device)   # one address for good
+        self._n_chunks, self._key = 0, None
+        self.reset()
+
+    @property
+    def decay(self):
+        return self._decay
+
+    @decay.setter
+    def decay(self, value):
+        raise AttributeError("WeightEMA: decay is fixed at construction (the device block holds it; a decay that changes later is not built)")
+
+    # ---- the state block and the table
+    def _outside_graphs(self, what):
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("WeightEMA: %s writes the state block from the host side and the stream is capturing: call it outside graphs" % what)
+
+    def _write_state(self, n):
+        """decay, flags, num_updates = n and the weight for n; swapped and the counters zero.  Stream-ordered."""
+        blob = struct.pack(EMA_STATE_FORMAT, self._decay, int(n), ema_weight(self._decay, self.warmup, int(n)), EMA_WARMUP if self.warmup else 0, 0, 0, 0)
+        with torch.no_grad():
+            self._state.copy_(torch.frombuffer(bytearray(blob), dtype=torch.uint8))
+
+    def prepare(self):
+        """Builds and uploads the table for the current parameter addresses (a no-op when they have not moved).  update(), swap() and a
+        fused step call it; call it yourself before capturing a graph that no eager call preceded."""
+        key = tuple(p.data_ptr() for p in self._params) + tuple(e.data_ptr() for e in self.shadow)
+        if key == self._key:
+            return
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("WeightEMA: a parameter address changed and the stream is capturing: call prepare() before the capture")
+        n = len(self._params)
+        vp = C.c_void_p * n
+        spare = self._state.data_ptr()                                    # an empty tensor has no address; its row is legal but may not be NULL
+        host = torch.empty(self._table_bytes, dtype=torch.uint8).pin_memory()                 # a fresh staging block per build: the copy below is asynchronous
+        n_chunks = C.c_int32(0)
+        _lib.check(_lib.lib.frcnn_ema_table_build_host(n, vp(*[p.data_ptr() or spare for p in self._params]), vp(*[e.data_ptr() or spare for e in self.shadow]),
+                                                       self._numel, C.c_void_p(host.data_ptr()), self._table_bytes, C.byref(n_chunks)),
+                   "frcnn_ema_table_build_host")
+        self._table.copy_(host, non_blocking=True)
+        self._n_chunks, self._key = int(n_chunks.value), key
+
+    def _head(self):
+        return C.c_void_p(self._table.data_ptr()), self._table_bytes, len(self._params), self._n_chunks
+
+    def fused_arguments(self):
+        """(table, table bytes, state) for frcnn_sgd_step_ema: DeviceSGD.launch()."""
+        self.prepare()
+        return C.c_void_p(self._table.data_ptr()), self._table_bytes, C.c_void_p(self._state.data_ptr())
+
+    # ---- launches
+    def update(self):
+        """The stand-alone update behind ANY optimizer's step: frcnn_ema_update, two launches, no host synchronisation, capturable.  With
+        DeviceSGD(ema=) do not call it: the step already moved the average."""
+        self.prepare()
+        guard = C.c_void_p(self.guard.data_ptr()) if self.guard is not None else None
+        with torch.cuda.device(self.device):
+            stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            _lib.check(_lib.lib.frcnn_ema_update(*self._head(), C.c_void_p(self._state.data_ptr()), guard, stream), "frcnn_ema_update")
+
+    def swap(self):
+        """Live and averaged weights exchanged element for element IN PLACE (frcnn_ema_swap: one launch, no host synchronisation,
+        capturable); no data_ptr() changes.  Two swaps are the identity."""
+        self.prepare()
+        with torch.cuda.device(self.device):
+            stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            _lib.check(_lib.lib.frcnn_ema_swap(*self._head(), C.c_void_p(self._state.data_ptr()), stream), "frcnn_ema_swap")
+
+    @contextlib.contextmanager
+    def applied(self):
+        """with ema.applied(): the parameters hold the averaged weights inside the block (swap in, swap out)."""
+        self.swap()
+        try:
+            yield self
+        finally:
+            self.swap()
+
+    @torch.no_grad()
+    def copy_to(self):
+        """Copies the shadow tensors into the parameters (the live weights are lost; the average stays)."""
+        for p, e in zip(self._params, self.shadow):
+            p.copy_(e)
+
+    @torch.no_grad()
+    def reset(self):
+        """The average becomes a copy of what the parameters hold now; num_updates = 0, the weight for n = 0, swapped and the counters
+        cleared.  Call it after GraphStep.capture(), whose warm-up steps move the average on each rank's own frames.  Outside graphs only."""
+        self._outside_graphs("reset()")
+        for p, e in zip(self._params, self.shadow):
+            e.copy_(p)
+        self._write_state(0)
+
+    def stats(self):
+        """The state block as a dict: decay, num_updates, w, warmup, swapped, skipped, refused.  A device read-back: synchronises."""
+        d = dict(zip(EMA_STATE_KEYS, struct.unpack(EMA_STATE_FORMAT, bytes(self._state.cpu().numpy()))))
+        d["warmup"] = bool(d.pop("flags") & EMA_WARMUP)
+        return d
+
+    # ---- checkpoints
+    @torch.no_grad()
+    def averaged_state_dict(self, model):
+        """model.state_dict() with the averaged tensor (a copy) in place of every trainable parameter this object covers; frozen parameters
+        and buffers as the model holds them.  Call it outside applied()."""
+        by_id = dict((id(p), e) for p, e in zip(self._params, self.shadow))
+        out = model.state_dict()
+        for name, p in model.named_parameters(remove_duplicate=False):
+            if id(p) in by_id and name in out:
+                out[name] = by_id[id(p)].detach().clone()
+        return out
+
+    def state_dict(self):
+        """decay, warmup, num_updates (a device read-back: synchronises) and the shadow tensors themselves, in row order."""
+        return {"decay": self._decay, "warmup": self.warmup, "num_updates": self.stats()["num_updates"], "shadow": list(self.shadow)}
+
+    @torch.no_grad()
+    def load_state_dict(self, state_dict):
+        """Copies the saved shadows INTO the existing tensors (no address changes) and sets num_updates and its weight; swapped and the
+        counters are cleared.  decay and warmup are fixed at construction: a state dict that disagrees is refused.  Outside graphs only."""
+        self._outside_graphs("load_state_dict()")
+        if float(state_dict["decay"]) != self._decay or bool(state_dict["warmup"]) != self.warmup:
+            raise ValueError("WeightEMA: the state dict was written with decay %r, warmup %r; this average has decay %r, warmup %r (fixed at construction)"
+                             % (state_dict["decay"], state_dict["warmup"], self._decay, self.warmup))
+        saved, n = list(state_dict["shadow"]), int(state_dict["num_updates"])
+        if len(saved) != len(self.shadow):
+            raise ValueError("WeightEMA: the state dict holds %d shadow tensors, this average %d" % (len(saved), len(self.shadow)))
+        if n < 0:
+            raise ValueError("WeightEMA: invalid num_updates: %r" % (n,))
+        for k, (e, v) in enumerate(zip(self.shadow, saved)):
+            if tuple(v.shape) != tuple(e.shape):
+                raise ValueError("WeightEMA: saved shadow %d has shape %s, the parameter %s" % (k, tuple(v.shape), tuple(e.shape)))
+        for e, v in zip(self.shadow, saved):
+            e.copy_(v.to(device=self.device, dtype=torch.float32))
+        self._write_state(n)
+
+
 class DeviceSGD(torch.optim.Optimizer):
-    """DeviceSGD(params, lr, momentum=0, weight_decay=0, guard=None, max_grad_norm=None, skip_nonfinite=False).  `guard`: a device int32
+    """DeviceSGD(params, lr, momentum=0, weight_decay=0, guard=None, max_grad_norm=None, skip_nonfinite=False, ema=None).  `guard`: a device int32
     tensor of one element; while it is non-zero a step changes nothing (parameters, momentum, born words).  Parameters with
     requires_grad=False take no part.
 
@@ -208,10 +433,15 @@ class DeviceSGD(torch.optim.Optimizer):
     skip word and the counters back; grad_norm_tensor is the norm as a device scalar.
 
     The state dict stays torch.optim.SGD's, key for key: max_grad_norm and the counters (steps, skipped_steps) are NOT checkpointed --
-    pass max_grad_norm to the constructor again on resume; the counters restart at zero."""
+    pass max_grad_norm to the constructor again on resume; the counters restart at zero.
+
+    `ema`: a WeightEMA over exactly this optimizer's trainable parameters, in its row order; the average then rides in the update kernel
+    (frcnn_sgd_step_ema: the update, the born launch, the average's bookkeeping), reads the step's skip word, and while the averaged
+    weights are swapped in the whole step changes nothing.  The average has its own state dict.  With ema=None nothing changes: the same
+    two or four launches and no further allocation."""
 
     def __init__(self, params, lr=1e-3, momentum=0, weight_decay=0, dampening=0, nesterov=False, maximize=False, guard=None,
-                 max_grad_norm=None, skip_nonfinite=False, norm_type=2.0):
+                 max_grad_norm=None, skip_nonfinite=False, norm_type=2.0, ema=None):
         if torch.is_tensor(norm_type) or isinstance(norm_type, bool) or not isinstance(norm_type, (int, float)) or float(norm_type) != 2.0:
             raise ValueError("DeviceSGD: norm_type %r is not supported: the L2 norm only" % (norm_type,))
         self._clip, self._skip_nonfinite = max_grad_norm is not None, bool(skip_nonfinite)
@@ -232,6 +462,13 @@ class DeviceSGD(torch.optim.Optimizer):
             if not torch.is_tensor(guard) or guard.dtype != torch.int32 or guard.numel() != 1 or guard.device != self.device:
                 raise TypeError("DeviceSGD: guard must be a one-element int32 tensor on %s" % self.device)
         self.guard = guard
+        if ema is not None:
+            if not isinstance(ema, WeightEMA):
+                raise TypeError("DeviceSGD: ema must be a WeightEMA, got %s" % type(ema).__name__)
+            if len(ema._params) != len(self._rows) or any(a is not b for a, (b, _) in zip(ema._params, self._rows)):
+                raise ValueError("DeviceSGD: ema must cover exactly this optimizer's trainable parameters, in its row order (the fused kernel finds "
+                                 "a tensor's shadow under its row number)")
+        self.ema = ema
         n, G = len(self._rows), len(self.param_groups)
         with torch.no_grad():
             for p, _ in self._rows:                                       # allocated once; the kernel and every graph hold these addresses
@@ -308,6 +545,8 @@ class DeviceSGD(torch.optim.Optimizer):
     def prepare(self):
         """Builds and uploads the table for the current parameter / gradient addresses (a no-op when they have not moved).  step() calls it;
         call it yourself before capturing a graph that no eager step preceded."""
+        if self.ema is not None:
+            self.ema.prepare()
         gs = self._gradients()
         key = tuple(p.data_ptr() for p, _ in self._rows) + tuple(g.data_ptr() for g in gs)
         if key == self._key:
@@ -342,14 +581,21 @@ class DeviceSGD(torch.optim.Optimizer):
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         head = (C.c_void_p(self._table.data_ptr()), self._table_bytes, len(self._rows), self._n_chunks)
         tail = (C.c_void_p(self._hyper.data_ptr()), len(self.param_groups), C.c_void_p(self._born.data_ptr()))
+        ema = self.ema.fused_arguments() if self.ema is not None else None
         if not (self._clip or self._skip_nonfinite):
-            _lib.check(_lib.lib.frcnn_sgd_step(*head, *tail, guard, stream), "frcnn_sgd_step")
+            if ema is not None:
+                _lib.check(_lib.lib.frcnn_sgd_step_ema(*head, *tail, guard, None, *ema, stream), "frcnn_sgd_step_ema")
+            else:
+                _lib.check(_lib.lib.frcnn_sgd_step(*head, *tail, guard, stream), "frcnn_sgd_step")
             return
         state = self._gn_state.data_ptr()                                 # the guard goes INTO the state block's skip word
         _lib.check(_lib.lib.frcnn_grad_norm(*head, C.c_void_p(state), guard, C.c_void_p(self._gn_work.data_ptr()), self._gn_work_bytes, stream),
                    "frcnn_grad_norm")
         skip = C.c_void_p(state + GN_OFF_SKIP)
-        if self._clip:
+        if ema is not None:
+            _lib.check(_lib.lib.frcnn_sgd_step_ema(*head, *tail, skip, C.c_void_p(state + GN_OFF_COEF) if self._clip else None, *ema, stream),
+                       "frcnn_sgd_step_ema")
+        elif self._clip:
             _lib.check(_lib.lib.frcnn_sgd_step_scaled(*head, *tail, skip, C.c_void_p(state + GN_OFF_COEF), stream), "frcnn_sgd_step_scaled")
         else:
             _lib.check(_lib.lib.frcnn_sgd_step(*head, *tail, skip, stream), "frcnn_sgd_step")

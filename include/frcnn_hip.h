@@ -864,6 +864,62 @@ int frcnn_grad_accumulate(int n_tensors, const void *const *src_host, void *cons
                           const frcnn_grad_accum_state *state, const int32_t *frame_skip, void *stream);
 int frcnn_grad_accum_advance(frcnn_grad_accum_state *state, const int32_t *frame_skip, void *stream);
 
+/* ---- optimizer: exponential moving average of the weights, in device memory, fused into the SGD step, swappable in place ----------------
+ * The reference evaluates and checkpoints the raw weights (train.py:75-85) and keeps no average: this is defined by this project and
+ * pinned to torch.  Per element, p' the parameter after this update, e its average ("shadow"), w the float32 weight of this update:
+ *   d  = round(p' - e)
+ *   e' = |w| < 0.5 ? fma(w, d, e) : fma(round(w - 1), d, p')          every fma rounded once
+ * the bits of torch._foreach_lerp_([e], [p'], w) on the CPU, which torch.optim.swa_utils.get_ema_multi_avg_fn runs
+ * (tests/golden/ema.npz).  The weight follows a schedule evaluated in binary64, n the number of updates applied so far:
+ *   decay_t = warm-up ? min(decay, (1 + n) / (10 + n)) : decay          w = (float)(1.0 - decay_t)
+ * The caller writes w for n = 0; after every applied update the device computes the next one (one thread, binary64).
+ *
+ * The state block: 64 bytes of DEVICE memory, 16-byte aligned.  decay and flags are inputs, written once by the caller outside any graph,
+ * with num_updates and w for the starting n; the counters are zeroed by the caller.  The advance launch (one thread) is the only writer
+ * of num_updates, w, skipped and refused; frcnn_ema_swap (one thread of it) is the only writer of swapped. */
+typedef struct {
+    double decay;            /*  0  in   0 <= decay < 1 */
+    int64_t num_updates;     /*  8  i/o  n: updates applied so far */
+    float w;                 /* 16  i/o  the weight of the NEXT update: (float)(1.0 - decay_t(n)) */
+    uint32_t flags;          /* 20  in   FRCNN_EMA_WARMUP */
+    int32_t swapped;         /* 24  i/o  1 while the parameters hold the averaged weights (frcnn_ema_swap toggles it) */
+    int32_t skipped;         /* 28  i/o  updates left out because the skip word was set */
+    int32_t refused;         /* 32  i/o  updates (fused: whole steps) left out because swapped was set */
+    int32_t reserved[7];     /* 36       not touched */
+} frcnn_ema_state;
+#define FRCNN_EMA_WARMUP 1u
+/* The table: frcnn_ema_table_bytes(n_tensors, numel_host) bytes, filled on the HOST by frcnn_ema_table_build_host from arrays of DEVICE
+ * pointers (parameter, shadow) and element counts, then uploaded by the caller to 16-byte aligned device memory: one row per tensor, one
+ * map entry per 8192-element chunk -- for the same sizes entry for entry the SGD table's map.  Pointers need 4-byte alignment only; a
+ * row whose two pointers are 16-byte aligned is moved with 16-byte accesses, any other with dword accesses for its whole length.
+ * frcnn_ema_table_bytes: 0 for counts the builder refuses.  frcnn_ema_table_build_host, FRCNN_ERR_INVALID_ARG: a NULL array, n_tensors
+ * outside 1 .. 65536, a negative size or one above 2^40, a NULL pointer in a row or one that is not 4-byte aligned, any overlap among
+ * the parameter and shadow ranges (of one row or of two); FRCNN_ERR_WORKSPACE: a short table.
+ *
+ * frcnn_ema_update: the stand-alone form, behind any optimizer: two launches, no host synchronisation, capturable.  Every workgroup of
+ * the first reads w, swapped and *skip (NULL allowed); with neither set it applies the rule to its chunk; only e is written.  The
+ * second, one thread, is the bookkeeping:
+ *   swapped != 0:  refused += 1            else *skip != 0:  skipped += 1            else:  num_updates += 1, w = the weight for the new n
+ * frcnn_ema_swap: one launch, capturable, not gated by any skip word: p and e exchanged element for element in place, swapped toggled.
+ * No address changes: graphs captured on the parameters run on the averaged weights between two swaps.
+ * frcnn_sgd_step_ema: frcnn_sgd_step (grad_scale NULL) or frcnn_sgd_step_scaled (grad_scale given) with the average fused in: the update
+ * kernel loads e behind computing p', applies the rule and stores e' -- 28 B per element against 32 B in two passes; then the born
+ * launch, then the bookkeeping above: three launches.  It reads ONE skip word for all of it.  While swapped is set the WHOLE step changes
+ * nothing -- parameters, momentum, born words, average -- and is counted in refused: training on the averaged weights would corrupt both
+ * sets.  The EMA table must be built over the SGD table's parameters, in its row order; a row takes the 16-byte path only when the SGD
+ * row's three pointers and the shadow are 16-byte aligned; a workgroup whose two rows disagree on parameter or size touches nothing.
+ * FRCNN_ERR_INVALID_ARG before anything is launched: a NULL table or state, bad counts, a table or state that is not 16-byte aligned,
+ * a skip word that is not 4-byte aligned, and for the fused form frcnn_sgd_step's refusals; FRCNN_ERR_WORKSPACE: a short table. */
+size_t frcnn_ema_table_bytes(int n_tensors, const int64_t *numel_host);
+int frcnn_ema_table_build_host(int n_tensors, const void *const *params_host, const void *const *shadows_host, const int64_t *numel_host,
+                               void *table_host, size_t table_bytes, int32_t *n_chunks_host);
+int frcnn_ema_update(const void *table, size_t table_bytes, int n_tensors, int n_chunks, frcnn_ema_state *state, const int32_t *skip,
+                     void *stream);
+int frcnn_ema_swap(const void *table, size_t table_bytes, int n_tensors, int n_chunks, frcnn_ema_state *state, void *stream);
+int frcnn_sgd_step_ema(const void *table, size_t table_bytes, int n_tensors, int n_chunks, const float *hyper, int n_groups, int32_t *born,
+                       const int32_t *skip, const float *grad_scale, const void *ema_table, size_t ema_table_bytes, frcnn_ema_state *ema_state,
+                       void *stream);
+
 /* ---- in-library kernel timing (HIP events on the launch stream) -------------------------------------- */
 /* When enabled, every kernel launch made by this library is bracketed by two hipEventRecord on the
  * caller's stream.  frcnn_prof_collect() synchronises those events (call it after the stream is idle)
