@@ -19,6 +19,7 @@ OP_DETECT = 11
 OP_EVAL = 12
 OP_COCO_EVAL = 13
 OP_EVAL_MERGE = 14
+OP_COCO_EVAL_POOLED = 15
 EVAL_TP, EVAL_FP, EVAL_IGNORED = 1, 2, 3                     # a record's flags: 2 bits per threshold
 EVAL_ERR_UPSTREAM_ABORT, EVAL_ERR_GT_OVERFLOW, EVAL_ERR_COUNT_RANGE, EVAL_ERR_LABEL_RANGE = 1, 2, 4, 8
 EVAL_ERR_LEDGER_OVERFLOW = 16
@@ -98,6 +99,8 @@ SIGNATURES = {
     "frcnn_eval_average_precision": (_i, [_vp, _vp, _vp, _i64, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "frcnn_coco_eval_update": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
                                      _vp, _vp, _vp, _sz, _vp]),
+    "frcnn_coco_eval_update_pooled": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp,
+                                            _i64, _vp, _vp, _vp, _sz, _vp]),
     "frcnn_coco_eval_accumulate": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "frcnn_eval_ledger_append": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "frcnn_eval_merge": (_i, [_i, _i64, _i64, _i, _i64] + [_vp] * 11 + [_vp] * 5 + [_i64] + [_vp] * 3 + [_i64] + [_vp] * 6 + [_vp, _sz, _vp]),

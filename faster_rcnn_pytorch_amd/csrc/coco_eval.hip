@@ -21,7 +21,8 @@
 //      positive holds 0), a right-to-left running maximum as a second scan, and one lane per recall threshold that bisects for the
 //      first true positive k with k / npig >= recThr.  The float64 operations of accumulate and no others.
 //
-// Not built: the segm and keypoints IoU types, useCats = 0.
+// Not built: the segm and keypoints IoU types.  useCats = 0 (every category pooled) is coco_eval_pooled.hip, which feeds the same record store
+// and coco_accumulate_kernel with K = 1.
 //
 // The limits (EVAL_MAX_*, EVAL_THREADS, eval_supported), the error bits of a frame, eval_lower_bound and the (tp, fp) scan are those of
 // eval_dev.h, shared with eval.hip.

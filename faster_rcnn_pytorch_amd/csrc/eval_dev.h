@@ -1,4 +1,4 @@
-// eval_dev.h -- what the two evaluator translation units (eval.hip: the VOC protocol, coco_eval.hip: the COCO protocol) share: the bits
+// eval_dev.h -- what the evaluator translation units (eval.hip: the VOC protocol, coco_eval.hip and coco_eval_pooled.hip: the COCO protocol) share: the bits
 // of the device error word, the kernels' limits, the 256-byte aligned base of a caller's workspace, and on the device the order of fp32
 // scores as unsigned integers, the error bits of a frame's counts, the bisection for a class's segment of the sorted records and the
 // block-wide scan of the packed (tp, fp) counts.  A change to the error word, the limits or the scan is made here, once.

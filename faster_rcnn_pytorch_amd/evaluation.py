@@ -28,7 +28,16 @@ summarize, i.e. pycocotools' COCOeval for iouType "bbox" with useCats = 1) -- ru
 The evaluator takes the xyxy boxes of detect; the reference also passes predict's boxes through cxcy_to_xy (test.py:68), which is the
 caller's business.  Restated from the published algorithm and NOT pinned to pycocotools' own code, which is not available to this
 project's tests (docs/PARITY.md); tests/test_coco_crosscheck.py compares with it wherever it can be imported.
-Not built: the segm and keypoints IoU types, useCats = 0.
+Not built: the segm and keypoints IoU types.
+
+With every category pooled (COCOeval's useCats = 0) the same store measures the proposal path, the metric of the Faster R-CNN paper's RPN
+ablations (AR@100 / 300 / 1000), and class-agnostic detection AP:
+
+    pe = ProposalEvaluator(max_dets=(100, 300, 1000), device=dev)            # a CocoDetectionEvaluator(use_cats=False) underneath
+    dets, props = model.detect(x, 0.05, want_proposals=True)                 # one forward serves both; or props = model.proposals(x)
+    ev.update(dets, gt)
+    pe.update(props, gt)                                                      # DetectGraph(model, hw, evaluator=ev, gt=gt, proposal_evaluator=pe)
+    pe.summarize()["ar"]                                                      # AR@100, AR@300, AR@1000
 
 On N GPUs (the reference's test loop is distributed: test.py:60-128, evaluation/coco_eval.py:46-49, 161-190) every rank evaluates its shard
 with an evaluator built with image_capacity > 0, which keeps one ledger row per frame (image_id, the frame's record slots, its share of
@@ -187,7 +196,7 @@ class _RecordStore(object):
         setattr(self, "rec_" + self._COLUMN, self._rec_order)
         # bit pattern: 2 bits per threshold, one word per area range where the protocol has them
         self.rec_flags = torch.zeros(cap if self._FLAGS_WIDTH == 1 else (cap, self._FLAGS_WIDTH), dtype=torch.int32, device=dev)
-        self._counter = torch.zeros((self.num_classes - 1,) + self._COUNTER[1], dtype=torch.int64, device=dev)
+        self._counter = torch.zeros((self._counter_rows(),) + self._COUNTER[1], dtype=torch.int64, device=dev)
         setattr(self, self._COUNTER[0], self._counter)
         self.cursor = torch.zeros(1, dtype=torch.int64, device=dev)
         self.error = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -202,6 +211,9 @@ class _RecordStore(object):
             self.led_count = torch.zeros(1, dtype=torch.int64, device=dev)
             self._snap_cursor = torch.zeros(1, dtype=torch.int64, device=dev)
             self._snap_counter = torch.zeros(cw, dtype=torch.int64, device=dev)
+
+    def _counter_rows(self):
+        return self.num_classes - 1
 
     # ---- per frame ----------------------------------------------------------------------------------------------------------
     def _workspace(self, D, G):
@@ -472,9 +484,10 @@ class DetectionEvaluator(_RecordStore):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
-# the COCO protocol (bbox, useCats = 1)
+# the COCO protocol (bbox; useCats = 1, or every category pooled: useCats = 0)
 # ---------------------------------------------------------------------------------------------------------------------------------
 COCO_MAX_DET = 100
+COCO_MAX_DET_POOLED = 2048
 COCO_AREA_RANGES = ((0.0, 1e10), (0.0, 32.0 ** 2), (32.0 ** 2, 96.0 ** 2), (96.0 ** 2, 1e10))      # all, small, medium, large
 
 
@@ -501,46 +514,64 @@ class CocoGroundTruth(_FrameBuffer):
 
 
 class CocoDetectionEvaluator(_RecordStore):
-    """COCOeval (bbox, useCats = 1) over a record store in HBM.  update() is one HIP launch on the current stream and has no host sync;
-    summarize() runs the accumulate kernel, does the only device -> host copy and takes the 12 means with numpy as pycocotools does."""
+    """COCOeval (bbox) over a record store in HBM.  update() is one HIP launch on the current stream (two with use_cats=False) and has no
+    host sync; summarize() runs the accumulate kernel, does the only device -> host copy and takes the 12 means with numpy as pycocotools
+    does.
+
+    use_cats=False is COCOeval's useCats = 0: a frame's detections and ground truths are each ONE list in the order (label ascending,
+    position ascending), the detections are ranked by score descending with a stable sort over that order and cut to max_dets[-1] (up to
+    2048), and a detection may match a ground truth of any label; num_classes only bounds the labels.  There is one pooled category:
+    npig is [1, 4], precision [T, 101, 1, 4, 3], and the 12 stats have their usual meaning over the pooled set."""
     _COLUMN, _FLAGS_WIDTH, _COUNTER, _OP = "rank", 4, ("npig", (4,)), ("coco_eval_update", _lib.OP_COCO_EVAL)
     _GT, _CONFIG_WORDS = CocoGroundTruth, "classes, thresholds or maxDets"
 
     def __init__(self, num_classes, record_capacity=1 << 20, gt_capacity=128, device=None, iou_thresholds=None, max_dets=(1, 10, 100),
-                 image_capacity=0):
+                 image_capacity=0, use_cats=True):
         """image_capacity > 0 keeps an image ledger of that many frames (one further launch per update): what merge_shards() and
         synchronize_between_processes() need."""
         thr = np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True) if iou_thresholds is None \
             else np.array([float(t) for t in iou_thresholds], np.float64)
         md = tuple(int(v) for v in max_dets)
         super().__init__(num_classes, thr, record_capacity, gt_capacity, image_capacity)
-        if len(md) != 3 or list(md) != sorted(md) or md[0] < 1 or md[2] > COCO_MAX_DET:
-            raise ValueError("CocoDetectionEvaluator: max_dets must be three ascending values in 1 .. %d" % COCO_MAX_DET)
+        self.use_cats = bool(use_cats)
+        limit = COCO_MAX_DET if self.use_cats else COCO_MAX_DET_POOLED
+        if len(md) != 3 or list(md) != sorted(md) or md[0] < 1 or md[2] > limit:
+            raise ValueError("%s: max_dets must be three ascending values in 1 .. %d" % (type(self).__name__, limit))
         self.max_dets = md
+        if not self.use_cats:
+            self._OP = ("coco_eval_update_pooled", _lib.OP_COCO_EVAL_POOLED)
+            self._CONFIG_WORDS = "classes, thresholds, maxDets or use_cats"
         self._allocate(device)
         self.rec_thresholds_host = np.linspace(.0, 1.00, int(np.round((1.00 - .0) / .01)) + 1, endpoint=True)
         self.rec_thresholds = torch.from_numpy(self.rec_thresholds_host.copy()).to(self.device)
 
+    def _counter_rows(self):
+        return self.num_classes - 1 if self.use_cats else 1
+
     def _config(self):
-        return {"config": (self.iou_thresholds, self.num_classes, self.max_dets)}
+        if self.use_cats:
+            return {"config": (self.iou_thresholds, self.num_classes, self.max_dets)}
+        return {"config": (self.iou_thresholds, self.num_classes, self.max_dets, "pooled")}
 
     def update(self, dets, gt):
         """Scores one frame: dets = ops.Detections of the frame (rows in any order), gt = its CocoGroundTruth.  No sync; capturable
         into a graph with detect."""
         self._check_gt(gt)
-        ops.coco_eval_update(dets, gt.boxes, gt.area, gt.labels, gt.iscrowd, gt.n, gt.frame, self.thresholds, self.num_classes, self.max_dets[-1],
-                             self.npig, self.rec_score, self.rec_label, self.rec_image, self.rec_rank, self.rec_flags, self.cursor, self.error,
-                             workspace=self._workspace(dets.labels.numel(), gt.capacity))
+        (ops.coco_eval_update if self.use_cats else ops.coco_eval_update_pooled)(
+            dets, gt.boxes, gt.area, gt.labels, gt.iscrowd, gt.n, gt.frame, self.thresholds, self.num_classes, self.max_dets[-1], self.npig,
+            self.rec_score, self.rec_label, self.rec_image, self.rec_rank, self.rec_flags, self.cursor, self.error,
+            workspace=self._workspace(dets.labels.numel(), gt.capacity))
         self._ledger_append(gt)
 
     def summarize(self):
         """{"stats": float64 [12] (COCOeval.stats: AP, AP50, AP75, APs, APm, APl, AR@maxDets[0], AR@maxDets[1], AR@maxDets[2], ARs, ARm,
         ARl), "precision": float64 [T, 101, K, 4, 3], "recall": float64 [T, K, 4, 3] (-1 where npig == 0), "npig": int64 [K, 4],
-        "n_records"}.  Raises FrcnnError when a frame reported an error or records were dropped.  One device -> host copy."""
-        T, nc, R = len(self.iou_thresholds), self.num_classes - 1, self.rec_thresholds.numel()
+        "n_records"}; K = num_classes - 1, or 1 with use_cats=False.  Raises FrcnnError when a frame reported an error or records were
+        dropped.  One device -> host copy."""
+        T, nc, R = len(self.iou_thresholds), self._counter_rows(), self.rec_thresholds.numel()
         order, lab = self._sorted()
         precision, recall = ops.coco_eval_accumulate(lab, self.rec_rank[order].contiguous(), self.rec_flags[order].contiguous(), self.cursor,
-                                                     self.npig, self.rec_thresholds, T, self.num_classes, self.max_dets)
+                                                     self.npig, self.rec_thresholds, T, nc + 1, self.max_dets)
         host = torch.cat([precision.view(torch.int64).reshape(-1), recall.view(torch.int64).reshape(-1), self.npig.reshape(-1), self.cursor,
                           self.error.to(torch.int64)]).cpu().numpy()
         np_, nr = T * R * nc * 12, T * nc * 12
@@ -550,6 +581,28 @@ class CocoDetectionEvaluator(_RecordStore):
         rec = host[np_:np_ + nr].copy().view(np.float64).reshape(T, nc, 4, 3)
         return {"stats": coco_stats(prec, rec, np.array(self.iou_thresholds, np.float64)), "precision": prec, "recall": rec,
                 "npig": host[np_ + nr:np_ + nr + 4 * nc].reshape(nc, 4).copy(), "n_records": n_all}
+
+
+class ProposalEvaluator(CocoDetectionEvaluator):
+    """Proposal recall: COCO's "proposal" evaluation and the metric of the Faster R-CNN paper's RPN ablations -- AR at max_dets proposals
+    per image with every category pooled.  A CocoDetectionEvaluator(use_cats=False) fed with model.proposals(x) (or detect(...,
+    want_proposals=True)[1]), whose scores are a rank ramp: only the order within a frame is meaningful.
+
+    summarize() therefore returns only what a ramp supports: "ar" float64 [3] (AR@max_dets, area range "all"), "ar_small", "ar_medium",
+    "ar_large" (at max_dets[-1]), "recall" float64 [T, 4, 3] (threshold, area range, max_dets; -1 where npig == 0), "npig" int64 [4] and
+    "n_records".  The AP entries are left out on purpose: precision orders the records of ALL images by score, and the ramp's scores say
+    nothing across images.  num_classes only bounds the ground truths' labels (default: every label the kernels accept)."""
+
+    def __init__(self, max_dets=(100, 300, 1000), iou_thresholds=None, gt_capacity=128, image_capacity=0, record_capacity=1 << 20, device=None,
+                 num_classes=MAX_CLASSES):
+        super().__init__(num_classes, record_capacity=record_capacity, gt_capacity=gt_capacity, device=device, iou_thresholds=iou_thresholds,
+                         max_dets=max_dets, image_capacity=image_capacity, use_cats=False)
+
+    def summarize(self):
+        res = CocoDetectionEvaluator.summarize(self)
+        st = res["stats"]
+        return {"ar": st[6:9].copy(), "ar_small": float(st[9]), "ar_medium": float(st[10]), "ar_large": float(st[11]),
+                "recall": res["recall"][:, 0].copy(), "npig": res["npig"][0].copy(), "n_records": res["n_records"]}
 
 
 def coco_stats(precision, recall, iou_thresholds):

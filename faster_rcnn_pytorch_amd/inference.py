@@ -16,16 +16,27 @@ class DetectGraph(object):
     evaluation.CocoDetectionEvaluator with gt= an evaluation.CocoGroundTruth for the COCO one) adds the evaluator's per-frame update to the same
     graph: the reference's test loop (test.py:60: predict, then the evaluator) as one replay per frame with no host sync.  Write the
     frame's ground truth with gt.set(...) before the call (the warm-up and the capture score nothing).  Without them the captured
-    graph is detect alone."""
+    graph is detect alone.
 
-    def __init__(self, model, image_hw, threshold=0.05, device=None, warmup=2, evaluator=None, gt=None):
+    proposal_evaluator= (an evaluation.ProposalEvaluator, or any CocoDetectionEvaluator(use_cats=False), with gt= an
+    evaluation.CocoGroundTruth) also scores the frame's proposals -- the same forward's RoIs, model.detect(..., want_proposals=True) -- in
+    the same graph, with or without evaluator=.  self.proposals is then the graph's static proposal Detections."""
+
+    def __init__(self, model, image_hw, threshold=0.05, device=None, warmup=2, evaluator=None, gt=None, proposal_evaluator=None):
         m = getattr(model, "module", model)                     # a DDP-wrapped model: capture the module itself
         dev = torch.device(device) if device is not None else next(m.parameters()).device
         H, W = (int(v) for v in image_hw)
-        if (evaluator is None) != (gt is None):
+        if (evaluator is None and proposal_evaluator is None) != (gt is None):
             raise ValueError("DetectGraph: evaluator= and gt= go together")
         self.model = m
-        self.evaluator, self.gt = evaluator, gt
+        self.evaluator, self.gt, self.proposal_evaluator = evaluator, gt, proposal_evaluator
+        self.proposals = None
+        want = proposal_evaluator is not None
+
+        def detect():
+            if not want:
+                return m.detect(self.x, float(threshold), threshold_dev=self.threshold), None
+            return m.detect(self.x, float(threshold), threshold_dev=self.threshold, want_proposals=True)
         self.image_hw = (H, W)
         self.x = torch.zeros((1, 3, H, W), dtype=torch.float32, device=dev)
         self.threshold = torch.full((1,), float(threshold), dtype=torch.float32, device=dev)
@@ -34,15 +45,19 @@ class DetectGraph(object):
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
             for _ in range(max(int(warmup), 1)):
-                out = m.detect(self.x, float(threshold), threshold_dev=self.threshold)
+                out, props = detect()
             if evaluator is not None:
                 evaluator._workspace(out.labels.numel(), gt.capacity)         # the update's zeroed workspace: allocated outside the capture
+            if want:
+                proposal_evaluator._workspace(props.labels.numel(), gt.capacity)
         torch.cuda.current_stream(dev).wait_stream(side)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
-            self.out = m.detect(self.x, float(threshold), threshold_dev=self.threshold)
+            self.out, self.proposals = detect()
             if evaluator is not None:
                 evaluator.update(self.out, gt)
+            if want:
+                proposal_evaluator.update(self.proposals, gt)
 
     def set_threshold(self, t):
         """Writes the device threshold in place: the next replay uses it."""

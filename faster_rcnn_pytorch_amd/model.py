@@ -268,7 +268,7 @@ class RPNTargetMaker(nn.Module):
 
 class _Detector(nn.Module):
     """What the two FRCNN mirrors share, and the interface parallel.GraphStep / FrameSlot, inference.DetectGraph and bench.py rely on:
-    forward(x, boxes, labels, n_gt=, empty=), predict, detect, graph_stages(), check_device_status(), and the attributes num_classes,
+    forward(x, boxes, labels, n_gt=, empty=), predict, detect, proposals, graph_stages(), check_device_status(), and the attributes num_classes,
     sampler and last_proposal_count.  A mirror writes forward and graph_stages itself and gives predict / detect two hooks:
         _test_proposals(x)         -> (features, rois [P,4] fixed capacity, n_rois device int32[1]), test mode, no host sync
         _head(features, rois, x)   -> (head_cls [R,C], head_reg [R,4C])"""
@@ -308,16 +308,34 @@ class _Detector(nn.Module):
         head_cls, head_reg = self._head(features, rois, x)
         return self._suppress(*self._decode(rois, head_cls, head_reg), threshold)
 
+    @staticmethod
+    def _proposal_detections(rois, n_rois):
+        """The fixed-capacity RoIs as an ops.Detections for evaluation.ProposalEvaluator: labels 0, count = n_rois, and scores[i] =
+        float32(P - i) -- the proposals leave NMS in objectness order, so the exact, strictly descending ramp restates their rank; only the
+        order is used."""
+        P = rois.shape[0]
+        ramp = torch.arange(P, 0, -1, dtype=torch.float32, device=rois.device)
+        return ops.Detections(rois, torch.zeros(P, dtype=torch.int32, device=rois.device), ramp, n_rois, None, None, n_rois)
+
     @torch.no_grad()
-    def detect(self, x, opts_or_threshold, threshold_dev=None, want_prob=False):
+    def proposals(self, x):
+        """The test-mode proposals of _test_proposals as an ops.Detections (boxes = the fixed-capacity RoIs, labels = 0, scores = a rank
+        ramp, count = the device count), with no host sync: what evaluation.ProposalEvaluator.update takes."""
+        _, rois, n_rois = self._test_proposals(x)
+        return self._proposal_detections(rois, n_rois)
+
+    @torch.no_grad()
+    def detect(self, x, opts_or_threshold, threshold_dev=None, want_prob=False, want_proposals=False):
         """predict without a host sync (graph-capturable): the test-mode path with the fixed-capacity proposals and their device count,
         the head on all P rows, and the post-processing of models/model.py:368-402 / models/new_model.py:420-470 in
         ops.detect_postprocess.  threshold_dev (a device float32[1]) overrides the threshold when given.  Returns ops.Detections (its
-        n_rois is the proposal count); .to_host() gives what predict returns."""
+        n_rois is the proposal count); .to_host() gives what predict returns.  want_proposals=True returns (detections, proposals), the
+        second as proposals(x) gives them: one forward serves both evaluators."""
         threshold = float(getattr(opts_or_threshold, "thres", opts_or_threshold))
         features, rois, n_rois = self._test_proposals(x)
         head_cls, head_reg = self._head(features, rois, x)                        # rows >= n_rois: zero boxes, ignored below
-        return ops.detect_postprocess(head_cls, head_reg, rois, n_rois, threshold, 0.3, threshold_dev=threshold_dev, want_prob=want_prob)
+        dets = ops.detect_postprocess(head_cls, head_reg, rois, n_rois, threshold, 0.3, threshold_dev=threshold_dev, want_prob=want_prob)
+        return (dets, self._proposal_detections(rois, n_rois)) if want_proposals else dets
 
     def _suppress(self, raw_cls_bbox, raw_prob, threshold):
         """models/model.py:382-402 (per-class score mask + nms(0.3), class 0 = background skipped, results concatenated

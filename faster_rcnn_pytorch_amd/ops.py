@@ -10,7 +10,7 @@ Mirrors (file:line under the reference):
   torchvision AnchorGenerator    as called at models/new_model.py:23-25,46
   FRCNN.predict post-processing  models/model.py:368-402, models/new_model.py:420-470 (detect_postprocess)
   VOC AP evaluator               evaluation/voc_eval.py:67-225 (eval_update, eval_average_precision)
-  COCO evaluator (bbox)          evaluation/coco_eval.py, test.py:60-88,124-128 (coco_eval_update, coco_eval_accumulate)
+  COCO evaluator (bbox)          evaluation/coco_eval.py, test.py:60-88,124-128 (coco_eval_update, coco_eval_update_pooled, coco_eval_accumulate)
   distributed evaluation         evaluation/coco_eval.py:46-49,161-190 (eval_ledger_append, eval_merge)
 
 PyTorch is plumbing here (device memory, streams, autograd glue).  Every op requires contiguous
@@ -469,24 +469,44 @@ def coco_eval_update(dets, gt_boxes, gt_area, gt_labels, gt_iscrowd, n_gt, frame
     read when the kernel runs.  The record store: rec_score f32, rec_label / rec_image / rec_rank i32 [record_capacity], rec_flags i32
     [record_capacity, 4] (per area range 2 bits per threshold: _lib.EVAL_TP / EVAL_FP / EVAL_IGNORED); cursor i64[1]; error_word i32[1]
     (_lib.EVAL_ERR_*); npig i64[C-1, 4].  See include/frcnn_hip.h.  evaluation.CocoDetectionEvaluator owns these buffers."""
+    _coco_update("coco_eval_update", lib.frcnn_coco_eval_update, _lib.OP_COCO_EVAL, 4 * (num_classes - 1), dets, gt_boxes, gt_area, gt_labels,
+                 gt_iscrowd, n_gt, frame, thresholds, num_classes, max_det, npig, rec_score, rec_label, rec_image, rec_rank, rec_flags, cursor,
+                 error_word, workspace)
+
+
+def coco_eval_update_pooled(dets, gt_boxes, gt_area, gt_labels, gt_iscrowd, n_gt, frame, thresholds, num_classes, max_det, npig, rec_score,
+                            rec_label, rec_image, rec_rank, rec_flags, cursor, error_word, workspace=None):
+    """One frame of the COCO bbox protocol with every category pooled (COCOeval with useCats = 0: proposal recall, class-agnostic AP) in two
+    launches and no host sync.  The arguments are those of coco_eval_update, except npig i64[1, 4] and max_det <= 2048: the frame's
+    detections and ground truths are each one list in (label ascending, position ascending), the detections are ranked by score
+    descending, stable over that order, and cut to max_det; a detection may match a ground truth of any label (num_classes only bounds the
+    labels).  Every record gets label 0 and its pooled rank.  See include/frcnn_hip.h.  evaluation.CocoDetectionEvaluator(use_cats=False)
+    owns these buffers."""
+    _coco_update("coco_eval_update_pooled", lib.frcnn_coco_eval_update_pooled, _lib.OP_COCO_EVAL_POOLED, 4, dets, gt_boxes, gt_area, gt_labels,
+                 gt_iscrowd, n_gt, frame, thresholds, num_classes, max_det, npig, rec_score, rec_label, rec_image, rec_rank, rec_flags, cursor,
+                 error_word, workspace)
+
+
+def _coco_update(op, fn, op_code, counter_words, dets, gt_boxes, gt_area, gt_labels, gt_iscrowd, n_gt, frame, thresholds, num_classes, max_det,
+                 npig, rec_score, rec_label, rec_image, rec_rank, rec_flags, cursor, error_word, workspace):
+    """coco_eval_update and coco_eval_update_pooled: the same arguments and checks, another entry point, workspace and counter size."""
     gt_boxes = _req(gt_boxes, torch.float64, "gt_boxes")
     gt_area = _req(gt_area, torch.float64, "gt_area")
     gt_labels = _req(gt_labels, torch.int32, "gt_labels")
     gt_iscrowd = _req(gt_iscrowd, torch.uint8, "gt_iscrowd")
     boxes, labels, scores, count, n_gt, frame, thresholds, npig, recs, cursor, error_word = _eval_update_args(
-        "coco_eval_update", dets, n_gt, frame, thresholds, ("npig", npig, 4 * (num_classes - 1)), rec_score, rec_label, rec_image,
-        ("rec_rank", rec_rank), rec_flags, 4, cursor, error_word)
+        op, dets, n_gt, frame, thresholds, ("npig", npig, counter_words), rec_score, rec_label, rec_image, ("rec_rank", rec_rank), rec_flags, 4,
+        cursor, error_word)
     D, G, T, cap = labels.numel(), gt_labels.numel(), thresholds.numel(), rec_score.numel()
     if gt_boxes.numel() != 4 * G or gt_area.numel() != G or gt_iscrowd.numel() != G:
-        raise ValueError("coco_eval_update: shapes disagree")
+        raise ValueError("%s: shapes disagree" % op)
     dev = boxes.device
-    nb = _lib.workspace_bytes(_lib.OP_COCO_EVAL, D, G)
+    nb = _lib.workspace_bytes(op_code, D, G)
     ws = workspace if workspace is not None else _workspace(dev, nb)
     with torch.cuda.device(dev):
-        check(lib.frcnn_coco_eval_update(_ptr(boxes), _ptr(labels), _ptr(scores), _ptr(count), D, _ptr(gt_boxes), _ptr(gt_area), _ptr(gt_labels),
-                                         _ptr(gt_iscrowd), _ptr(n_gt), G, _ptr(frame), _ptr(thresholds), T, int(num_classes), int(max_det),
-                                         _ptr(npig), _ptr(recs[0]), _ptr(recs[1]), _ptr(recs[2]), _ptr(recs[3]), _ptr(recs[4]), cap, _ptr(cursor),
-                                         _ptr(error_word), _ptr(ws), ws.numel(), _stream()), "coco_eval_update")
+        check(fn(_ptr(boxes), _ptr(labels), _ptr(scores), _ptr(count), D, _ptr(gt_boxes), _ptr(gt_area), _ptr(gt_labels), _ptr(gt_iscrowd), _ptr(n_gt),
+                 G, _ptr(frame), _ptr(thresholds), T, int(num_classes), int(max_det), _ptr(npig), _ptr(recs[0]), _ptr(recs[1]), _ptr(recs[2]),
+                 _ptr(recs[3]), _ptr(recs[4]), cap, _ptr(cursor), _ptr(error_word), _ptr(ws), ws.numel(), _stream()), op)
 
 
 def coco_eval_accumulate(labels_sorted, ranks_sorted, flags_sorted, n_records, npig, rec_thresholds, n_thresholds, num_classes, max_dets):

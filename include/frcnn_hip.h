@@ -61,7 +61,8 @@ typedef enum {
     FRCNN_OP_DETECT = 11,         /* n1 = P RoI rows, n2 = C classes: frcnn_detect_postprocess (0 outside its limits) */
     FRCNN_OP_EVAL = 12,           /* n1 = detection capacity, n2 = ground-truth capacity: frcnn_eval_update (0 outside its limits) */
     FRCNN_OP_COCO_EVAL = 13,      /* n1 = detection capacity, n2 = ground-truth capacity: frcnn_coco_eval_update (0 outside its limits) */
-    FRCNN_OP_EVAL_MERGE = 14      /* n1 = W * shard record capacity, n2 = W * shard image capacity: frcnn_eval_merge (0 outside its limits) */
+    FRCNN_OP_EVAL_MERGE = 14,     /* n1 = W * shard record capacity, n2 = W * shard image capacity: frcnn_eval_merge (0 outside its limits) */
+    FRCNN_OP_COCO_EVAL_POOLED = 15 /* n1 = detection capacity, n2 = ground-truth capacity: frcnn_coco_eval_update_pooled (0 outside its limits) */
 } frcnn_op;
 
 /* FRCNN_ABI_VERSION, or FRCNN_ERR_UNSUPPORTED (message in frcnn_last_error) when the objects the library was linked from were compiled
@@ -587,6 +588,36 @@ int frcnn_coco_eval_accumulate(const int32_t *labels_sorted, const int32_t *rank
                                int64_t capacity, const int64_t *npig /*[C-1,4]*/, const double *rec_thresholds_dev /*[R]*/, int R, int T, int C,
                                int max_det_0, int max_det_1, int max_det_2, double *precision, double *recall, void *workspace,
                                size_t workspace_bytes, void *stream);
+/* The same frame with every category POOLED: COCOeval with useCats = 0 (proposal recall AR@100 / 300 / 1000, class-agnostic AP).  The
+ * arguments are those of frcnn_coco_eval_update; two launches whatever the data holds, no host sync (graph-capturable), no workgroup
+ * that waits on another.
+ *   Pooled lists: the frame's detections and its ground truths are each ONE list in the order (label ascending, original position
+ *   ascending) -- pycocotools' [_ for cId in catIds for _ in self._dts[img, cId]].  The detections are ranked by score descending with a
+ *   stable sort over that order (equal scores: label ascending, then position ascending) and cut to max_det.  Labels only order the lists
+ *   and are range-checked; a detection may match a ground truth of ANY label.
+ *   Pixel boxes, the float64 IoU (crowd: union = the detection's area), the area ranges and gtIg = crowd or area outside the range are
+ *   those of frcnn_coco_eval_update.  Matching is COCOeval.evaluateImg per (area range, threshold) over the pooled lists: the walk starts
+ *   from min(t, 1 - 1e-10); first the non-ignored ground truths in pooled order, then -- only if none of them matched -- the ignored ones;
+ *   matched non-crowd ground truths are skipped; >= keeps the LATER (in pooled order) of equal IoUs.  An unmatched detection whose area
+ *   lies outside the range is ignored.
+ * Effects: npig[0, a] += the frame's ground truths of all labels not ignored in range a (npig is [1,4]); *cursor += the kept detections
+ * (one atomic add; slots past record_capacity are counted, not written); records as frcnn_coco_eval_update writes them with label = 0
+ * for every record and rank = the pooled rank; the defined order of the set is (score descending, image_id ascending, rank ascending).
+ * frcnn_coco_eval_accumulate with C = 2 (K = 1) accumulates them for any three maxDets.  The error word is that of
+ * frcnn_coco_eval_update; a frame with any bit is not recorded.
+ * Limits (FRCNN_ERR_UNSUPPORTED otherwise): 2 <= C <= 256, 1 <= det_capacity <= (C-1) * 2048, 1 <= gt_capacity <= 1024, 1 <= T <= 16,
+ * 1 <= max_det <= 2048.  boxes 16-byte aligned, gt_boxes and gt_area 8-byte aligned.  workspace:
+ * frcnn_workspace_bytes(FRCNN_OP_COCO_EVAL_POOLED, det_capacity, gt_capacity) bytes, ANY content between calls (every word the second
+ * launch reads, and every flag word it ORs into, is written by the first launch of the same call), not shared with a call that may run at
+ * the same time. */
+int frcnn_coco_eval_update_pooled(const float *boxes /*[D,4]*/, const int32_t *labels /*[D]*/, const float *scores /*[D]*/,
+                                  const int32_t *count_dev, int64_t det_capacity, const double *gt_boxes /*[G,4] pixel xywh*/,
+                                  const double *gt_area /*[G]*/, const int32_t *gt_labels /*[G]*/, const uint8_t *gt_iscrowd /*[G]*/,
+                                  const int32_t *n_gt_dev, int64_t gt_capacity, const int32_t *frame_dev /*[3]: w, h, image_id*/,
+                                  const double *thresholds_dev /*[T]*/, int T, int C, int max_det, int64_t *npig /*[1,4]*/, float *rec_score,
+                                  int32_t *rec_label, int32_t *rec_image, int32_t *rec_rank, uint32_t *rec_flags /*[record_capacity,4]*/,
+                                  int64_t record_capacity, int64_t *cursor /*[1]*/, int32_t *error_word /*[1]*/, void *workspace,
+                                  size_t workspace_bytes, void *stream);
 
 /* ---- detection evaluators: the image ledger and the merge of shards across ranks (test.py:60-128, evaluation/coco_eval.py:46-49,161-190) -- */
 /* One ledger row per frame, in one launch on the stream of the update before it (frcnn_eval_update or frcnn_coco_eval_update), with no
