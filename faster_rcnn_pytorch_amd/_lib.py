@@ -128,6 +128,9 @@ SIGNATURES = {
     "frcnn_ema_update": (_i, [_vp, _sz, _i, _i, _vp, _vp, _vp]),
     "frcnn_ema_swap": (_i, [_vp, _sz, _i, _i, _vp, _vp]),
     "frcnn_sgd_step_ema": (_i, [_vp, _sz, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "frcnn_tensor_stats_workspace_bytes": (_sz, [_i, _i]),
+    "frcnn_tensor_stats": (_i, [_vp, _sz, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "frcnn_journal_append": (_i, [_i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "frcnn_diag_occupy": (_i, [_i, _i, _vp]),
     "frcnn_prof_enable": (_i, [_i]),
     "frcnn_prof_collect": (_i, []),

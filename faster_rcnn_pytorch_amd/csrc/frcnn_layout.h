@@ -12,6 +12,8 @@
 //   * EmaHeader / EmaRow (ema_dev.h): the weight average's table, BUILT in ema.hip and walked by the kernels of ema.hip and by sgd.hip's
 //     fused update; frcnn_ema_state (include/frcnn_hip.h): written by ema.hip's advance and swap kernels, its w and swapped words read by
 //     sgd.hip's kernels;
+//   * frcnn_tensor_stats_row / _state and frcnn_journal_totals / _state (include/frcnn_hip.h): written by telemetry.hip, read by the caller
+//     (telemetry.py) by offset;
 //   * the profiling table size and the ABI version.
 // Every object registers its stamp in a static initialiser; frcnn_layout_check() (api.cpp; also run by frcnn_abi_version()) compares
 // them all with api.cpp's own and names the object that disagrees -- the library then refuses to load (FRCNN_ERR_UNSUPPORTED) instead of
@@ -60,6 +62,13 @@ constexpr uint64_t frcnn_layout_stamp_value()
     LAY(sizeof(frcnn_ema_state)); LAY(offsetof(frcnn_ema_state, decay)); LAY(offsetof(frcnn_ema_state, num_updates)); LAY(offsetof(frcnn_ema_state, w));
     LAY(offsetof(frcnn_ema_state, flags)); LAY(offsetof(frcnn_ema_state, swapped)); LAY(offsetof(frcnn_ema_state, skipped));
     LAY(offsetof(frcnn_ema_state, refused));
+    LAY(sizeof(frcnn_tensor_stats_row)); LAY(offsetof(frcnn_tensor_stats_row, g_sumsq)); LAY(offsetof(frcnn_tensor_stats_row, p_sumsq));
+    LAY(offsetof(frcnn_tensor_stats_row, m_sumsq)); LAY(offsetof(frcnn_tensor_stats_row, g_absmax)); LAY(offsetof(frcnn_tensor_stats_row, p_absmax));
+    LAY(offsetof(frcnn_tensor_stats_row, g_nonfinite)); LAY(offsetof(frcnn_tensor_stats_row, p_nonfinite)); LAY(offsetof(frcnn_tensor_stats_row, m_read));
+    LAY(sizeof(frcnn_tensor_stats_state)); LAY(offsetof(frcnn_tensor_stats_state, every)); LAY(offsetof(frcnn_tensor_stats_state, tick));
+    LAY(offsetof(frcnn_tensor_stats_state, measured_tick)); LAY(offsetof(frcnn_tensor_stats_state, measures));
+    LAY(offsetof(frcnn_tensor_stats_state, first_nonfinite_g)); LAY(offsetof(frcnn_tensor_stats_state, first_nonfinite_p));
+    LAY(FRCNN_TENSOR_STATS_FINISH_THREADS); LAY(sizeof(frcnn_journal_totals)); LAY(sizeof(frcnn_journal_state)); LAY(FRCNN_JOURNAL_MAX_COLS);
 #ifdef FRCNN_LAYOUT_TEST_SKEW          // tests/test_cabi.py builds ONE object with this defined and expects the library to refuse to load
     LAY(FRCNN_LAYOUT_TEST_SKEW);
 #endif
@@ -89,6 +98,19 @@ static_assert(sizeof(frcnn_ema_state) == 64 && offsetof(frcnn_ema_state, decay) 
                   offsetof(frcnn_ema_state, w) == 16 && offsetof(frcnn_ema_state, flags) == 20 && offsetof(frcnn_ema_state, swapped) == 24 &&
                   offsetof(frcnn_ema_state, skipped) == 28 && offsetof(frcnn_ema_state, refused) == 32,
               "frcnn_ema_state: the offsets include/frcnn_hip.h documents (optim.py reads and writes the block by them)");
+static_assert(sizeof(frcnn_tensor_stats_row) == 64 && offsetof(frcnn_tensor_stats_row, p_sumsq) == 8 && offsetof(frcnn_tensor_stats_row, m_sumsq) == 16 &&
+                  offsetof(frcnn_tensor_stats_row, g_absmax) == 24 && offsetof(frcnn_tensor_stats_row, p_absmax) == 28 &&
+                  offsetof(frcnn_tensor_stats_row, g_nonfinite) == 32 && offsetof(frcnn_tensor_stats_row, p_nonfinite) == 36 &&
+                  offsetof(frcnn_tensor_stats_row, m_read) == 40,
+              "frcnn_tensor_stats_row: the offsets include/frcnn_hip.h documents (telemetry.py reads the rows by them)");
+static_assert(sizeof(frcnn_tensor_stats_state) == 64 && offsetof(frcnn_tensor_stats_state, every) == 0 && offsetof(frcnn_tensor_stats_state, tick) == 4 &&
+                  offsetof(frcnn_tensor_stats_state, measured_tick) == 8 && offsetof(frcnn_tensor_stats_state, measures) == 12 &&
+                  offsetof(frcnn_tensor_stats_state, first_nonfinite_g) == 16 && offsetof(frcnn_tensor_stats_state, first_nonfinite_p) == 20,
+              "frcnn_tensor_stats_state: the offsets include/frcnn_hip.h documents (telemetry.py reads and writes the block by them)");
+static_assert(sizeof(frcnn_journal_totals) == 40 && offsetof(frcnn_journal_totals, count) == 8 && offsetof(frcnn_journal_totals, max) == 16 &&
+                  offsetof(frcnn_journal_totals, min) == 24 && offsetof(frcnn_journal_totals, nonfinite) == 32 && sizeof(frcnn_journal_state) == 64 &&
+                  offsetof(frcnn_journal_state, cursor) == 0 && offsetof(frcnn_journal_state, capacity) == 8 && offsetof(frcnn_journal_state, n_cols) == 12,
+              "frcnn_journal_totals / frcnn_journal_state: the offsets include/frcnn_hip.h documents (telemetry.py reads and writes them)");
 
 void frcnn_layout_register(const char *object, uint64_t stamp);
 int frcnn_layout_check_impl(void);

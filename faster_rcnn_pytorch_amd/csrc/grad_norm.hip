@@ -10,7 +10,8 @@
 //
 // The order of the additions is the contract written down in include/frcnn_hip.h (and restated in tests/grad_norm_ref.py): it depends on
 // an element's position in its tensor only.  The square of a binary32 is exact in binary64, so fma(d, d, acc) and acc + d * d are the
-// same number and contraction cannot change a bit; every other addition below is written out.
+// same number and contraction cannot change a bit; every other addition below is written out.  The chunk body (element, chunk, wave)
+// lives in sumsq_dev.h, which telemetry.hip's per-tensor statistics run too.
 //
 // Loads: 16-byte when the chunk's GRADIENT pointer is 16-byte aligned (decided from g alone -- SgdRow.vec also covers p and m), dword
 // loads otherwise, with the same element-to-thread assignment.  Default cache policy: the update reads the same bytes next.
@@ -19,18 +20,11 @@
 #include "frcnn_internal.h"
 #include "frcnn_layout.h"
 #include "sgd_dev.h"
+#include "sumsq_dev.h"
 FRCNN_LAYOUT_STAMP(grad_norm);
 
 #define GN_FINISH_THREADS FRCNN_GRAD_NORM_FINISH_THREADS
 static_assert(GN_FINISH_THREADS % WAVE == 0 && GN_FINISH_THREADS <= 1024, "the finish kernel is one workgroup of whole waves");
-static_assert(SGD_THREADS == 4 * WAVE, "the partial kernel adds four waves in order");
-
-__device__ __forceinline__ void gn_take(float x, double &acc, int &bad)
-{
-    const double d = (double)x;
-    acc = __fma_rn(d, d, acc);
-    bad += ((__float_as_uint(x) >> 23) & 0xffu) == 0xffu;
-}
 
 __global__ __launch_bounds__(SGD_THREADS) void grad_norm_partial_kernel(const SgdRow *__restrict__ rows, const int2 *__restrict__ map, int n_tensors,
                                                                         double *__restrict__ partial, int32_t *__restrict__ bad_out)
@@ -48,53 +42,9 @@ __global__ __launch_bounds__(SGD_THREADS) void grad_norm_partial_kernel(const Sg
         }
     }
     const int tid = threadIdx.x;
-    const int n4 = n >> 2;
-    double a[4] = {0.0, 0.0, 0.0, 0.0};
-    int bad = 0;
-    if (((uintptr_t)g & 15) == 0) {
-        const sgd_f4 *g4 = (const sgd_f4 *)g;
-        for (int base = 0; base < n4; base += 4 * SGD_THREADS) {
-            sgd_f4 v[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int i = base + k * SGD_THREADS + tid;
-                if (i < n4) v[k] = g4[i];
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int i = base + k * SGD_THREADS + tid;
-                if (i < n4) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) gn_take(v[k][e], a[e], bad);
-                }
-            }
-        }
-    } else {
-        for (int base = 0; base < n4; base += 4 * SGD_THREADS) {
-            float v[4][4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int i = base + k * SGD_THREADS + tid;
-                if (i < n4) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[k][e] = g[4 * i + e];
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int i = base + k * SGD_THREADS + tid;
-                if (i < n4) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) gn_take(v[k][e], a[e], bad);
-                }
-            }
-        }
-    }
-    if (tid == (n4 & (SGD_THREADS - 1)))                                    // the n % 4 elements of the last, partial group of four: its owner's last
-        for (int e = 0; e < (n & 3); ++e) gn_take(g[4 * n4 + e], a[e], bad);
-    double s = wave_sum_xor(__dadd_rn(__dadd_rn(a[0], a[1]), __dadd_rn(a[2], a[3])));
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) bad += __shfl_xor(bad, d, WAVE);
+    int bad;
+    float unused;
+    const double s = sumsq_chunk_wave<false>(g, n, tid, bad, unused);      // element, chunk, wave of the contract: sumsq_dev.h
     __shared__ double ws[SGD_THREADS / WAVE];
     __shared__ int wb[SGD_THREADS / WAVE];
     if ((tid & (WAVE - 1)) == 0) {
@@ -103,7 +53,7 @@ __global__ __launch_bounds__(SGD_THREADS) void grad_norm_partial_kernel(const Sg
     }
     __syncthreads();
     if (tid == 0) {
-        partial[blockIdx.x] = __dadd_rn(__dadd_rn(__dadd_rn(ws[0], ws[1]), ws[2]), ws[3]);
+        partial[blockIdx.x] = sumsq_block4(ws);
         bad_out[blockIdx.x] = wb[0] + wb[1] + wb[2] + wb[3];
     }
 }

@@ -73,6 +73,7 @@ def _check_max_grad_norm(v):
 
 # the state block of csrc/grad_norm.hip (frcnn_grad_norm_state, include/frcnn_hip.h): byte offsets, and the whole block for struct.unpack
 GN_STATE_BYTES, GN_OFF_MAX_NORM, GN_OFF_FLAGS, GN_OFF_NORM, GN_OFF_COEF, GN_OFF_SKIP = 64, 0, 4, 16, 20, 24
+GN_OFF_NONFINITE = 28
 GN_STATE_FORMAT = "<fIdffiiii24x"
 GN_CLIP, GN_SKIP_NONFINITE = 1, 2
 
@@ -422,7 +423,8 @@ class WeightEMA(object):
 
 
 class DeviceSGD(torch.optim.Optimizer):
-    """DeviceSGD(params, lr, momentum=0, weight_decay=0, guard=None, max_grad_norm=None, skip_nonfinite=False, ema=None).  `guard`: a device int32
+    """DeviceSGD(params, lr, momentum=0, weight_decay=0, guard=None, max_grad_norm=None, skip_nonfinite=False, ema=None, tensor_stats=None,
+    after_step=None).  `guard`: a device int32
     tensor of one element; while it is non-zero a step changes nothing (parameters, momentum, born words).  Parameters with
     requires_grad=False take no part.
 
@@ -438,10 +440,16 @@ class DeviceSGD(torch.optim.Optimizer):
     `ema`: a WeightEMA over exactly this optimizer's trainable parameters, in its row order; the average then rides in the update kernel
     (frcnn_sgd_step_ema: the update, the born launch, the average's bookkeeping), reads the step's skip word, and while the averaged
     weights are swapped in the whole step changes nothing.  The average has its own state dict.  With ema=None nothing changes: the same
-    two or four launches and no further allocation."""
+    two or four launches and no further allocation.
+
+    `tensor_stats`: True, or a dict of telemetry.TensorStats' keyword arguments (names, every): the optimizer builds a TensorStats over
+    its own table (`opt.tensor_stats`) and launch() measures in front of frcnn_grad_norm and the update -- three more launches, gated
+    by no skip word.  `after_step`: a callable run at the end of launch(), inside whatever graph captures the step -- a
+    ScalarJournal.append of scalar_views() lands in GraphStep's optimizer graph.  With both None nothing changes: the same launches and
+    no further allocation."""
 
     def __init__(self, params, lr=1e-3, momentum=0, weight_decay=0, dampening=0, nesterov=False, maximize=False, guard=None,
-                 max_grad_norm=None, skip_nonfinite=False, norm_type=2.0, ema=None):
+                 max_grad_norm=None, skip_nonfinite=False, norm_type=2.0, ema=None, tensor_stats=None, after_step=None):
         if torch.is_tensor(norm_type) or isinstance(norm_type, bool) or not isinstance(norm_type, (int, float)) or float(norm_type) != 2.0:
             raise ValueError("DeviceSGD: norm_type %r is not supported: the L2 norm only" % (norm_type,))
         self._clip, self._skip_nonfinite = max_grad_norm is not None, bool(skip_nonfinite)
@@ -487,13 +495,25 @@ class DeviceSGD(torch.optim.Optimizer):
         self._gn_state = self._gn_work = None                             # allocated by the first prepare() when clipping or skipping is on
         self._gn_work_bytes = 0
         self._pushed_max_norm = None
+        if after_step is not None and not callable(after_step):
+            raise TypeError("DeviceSGD: after_step must be callable, got %s" % type(after_step).__name__)
+        self.after_step = after_step
+        self.tensor_stats = None
+        if tensor_stats is not None and tensor_stats is not False:
+            if tensor_stats is not True and not isinstance(tensor_stats, dict):
+                raise TypeError("DeviceSGD: tensor_stats must be True or a dict of TensorStats' keyword arguments (names, every), got %s"
+                                % type(tensor_stats).__name__)
+            from .telemetry import TensorStats
+            self.tensor_stats = TensorStats(self, **(tensor_stats if isinstance(tensor_stats, dict) else {}))
 
     # ---- hyper-parameters
     def push_hyper(self):
         """Writes the (lr, momentum, weight_decay) that changed since the last call into the device block: one stream-ordered fill per
         changed value, no host synchronisation.  Never part of a graph: under capture a pending change is an error.  max_grad_norm travels
-        the same way (into the state block, once prepare() has allocated it)."""
+        the same way (into the state block, once prepare() has allocated it), and so does tensor_stats.every."""
         self._push_max_norm()
+        if self.tensor_stats is not None:
+            self.tensor_stats.push()
         for gi, g in enumerate(self.param_groups):
             _check_group(g)
             now = (float(g["lr"]), float(g["momentum"]), float(g["weight_decay"]))
@@ -575,8 +595,17 @@ class DeviceSGD(torch.optim.Optimizer):
         self._n_chunks, self._key = int(n_chunks.value), key
 
     def launch(self):
-        """The library launch alone (what a graph records): no hyper-parameter write."""
+        """The library launches alone (what a graph records): no hyper-parameter write.  With tensor_stats its three launches come first
+        (they run whatever the skip word says); after_step() runs behind the update, inside whatever graph captures the step."""
         self.prepare()
+        if self.tensor_stats is not None:
+            self.tensor_stats.push()                                      # a pending `every` under capture is an error, as a pending lr
+            self.tensor_stats._launch()
+        self._launch_update()
+        if self.after_step is not None:
+            self.after_step()
+
+    def _launch_update(self):
         guard = C.c_void_p(self.guard.data_ptr()) if self.guard is not None else None
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         head = (C.c_void_p(self._table.data_ptr()), self._table_bytes, len(self._rows), self._n_chunks)
@@ -613,6 +642,18 @@ class DeviceSGD(torch.optim.Optimizer):
         for logging from inside a capture."""
         self._need_state()
         return self._gn_state[GN_OFF_NORM:GN_OFF_NORM + 4].view(torch.float32)[0]
+
+    def scalar_views(self):
+        """0-d device views (no copy, no synchronisation) of the update-level scalars, for a ScalarJournal appended from after_step:
+        "lr/<group>" per parameter group (float32, from the hyper block) and, where a gradient norm is measured, "grad_norm", "clip_coef"
+        (float32), "skip" and "nonfinite" (int32) of the state block (allocated by the first prepare())."""
+        views = {"lr/%d" % gi: self._hyper[gi, 0] for gi in range(len(self.param_groups))}
+        if self._clip or self._skip_nonfinite:
+            self._need_state()
+            f32 = lambda off: self._gn_state[off:off + 4].view(torch.float32)[0]          # noqa: E731
+            i32 = lambda off: self._gn_state[off:off + 4].view(torch.int32)[0]            # noqa: E731
+            views.update(grad_norm=f32(GN_OFF_NORM), clip_coef=f32(GN_OFF_COEF), skip=i32(GN_OFF_SKIP), nonfinite=i32(GN_OFF_NONFINITE))
+        return views
 
     def grad_stats(self):
         """The state block after the last step, as a dict: norm, coef, skip, nonfinite, steps, skipped_steps, sumsq (and max_norm as the

@@ -951,6 +951,104 @@ int frcnn_sgd_step_ema(const void *table, size_t table_bytes, int n_tensors, int
                        const int32_t *skip, const float *grad_scale, const void *ema_table, size_t ema_table_bytes, frcnn_ema_state *ema_state,
                        void *stream);
 
+/* ---- training telemetry: per-tensor statistics over an SGD table, and a journal of scalars, all in device memory -------------------------
+ * The reference's loop prints its losses and the lr every vis_step steps (train.py:39-72) from host floats (loss.item(): a sync per
+ * step).  A graph-replayed run keeps its record on the device instead: frcnn_tensor_stats measures every tensor of an SGD table (the table
+ * frcnn_sgd_table_build_host made: rows and chunk map reused as they are, born the optimizer's born words), frcnn_journal_append keeps one
+ * row of scalars per call in a ring.  Both are defined by this project; what the journal's totals reproduce of the reference's
+ * SmoothedValue (util/misc.py:27-86) is said below.  Gradients, parameters and momenta are only read.
+ *
+ * One row per tensor, 64 bytes, rows[n_tensors] in DEVICE memory, 16-byte aligned, rewritten by every MEASURING call: */
+typedef struct {
+    double g_sumsq;          /*  0  the sum of the squares of the gradient, binary64, in the order below */
+    double p_sumsq;          /*  8  ... of the parameter */
+    double m_sumsq;          /* 16  ... of the momentum; +0 when m_read == 0 */
+    float g_absmax;          /* 24  max |g|: the `>` comparison from +0, so a NaN never wins and an inf does; order-free */
+    float p_absmax;          /* 28  max |p| */
+    int32_t g_nonfinite;     /* 32  gradient elements whose exponent field is all ones (inf, NaN), saturating at INT32_MAX */
+    int32_t p_nonfinite;     /* 36  ... parameter elements */
+    int32_t m_read;          /* 40  1: born[tensor] != 0 and the tensor has elements, its momentum was read; 0: not one byte of it was loaded */
+    int32_t reserved[5];     /* 44  written as zero */
+} frcnn_tensor_stats_row;
+/* The state block: 64 bytes of DEVICE memory, 16-byte aligned.  every is an input, written by the caller outside any graph; the caller
+ * initialises tick = 0, measured_tick = -1, measures = 0, first_nonfinite_g = first_nonfinite_p = -1 once. */
+typedef struct {
+    int32_t every;             /*  0  in   N >= 1: the call measures when tick % N == 0 */
+    int32_t tick;              /*  4  i/o  calls so far; (tick + 1) & INT32_MAX per call */
+    int32_t measured_tick;     /*  8  out  the tick whose data the rows hold; the caller's -1 before the first */
+    int32_t measures;          /* 12  i/o  += 1 per measuring call */
+    int32_t first_nonfinite_g; /* 16  out  the lowest row index with g_nonfinite != 0 at the last measuring call, -1 if none */
+    int32_t first_nonfinite_p; /* 20  out  ... with p_nonfinite != 0 */
+    int32_t reserved[10];      /* 24       not touched */
+} frcnn_tensor_stats_state;
+#define FRCNN_TENSOR_STATS_FINISH_THREADS 256
+/* frcnn_tensor_stats: three launches whatever the tensors are, no host synchronisation, capturable, no atomics, no workgroup waits on
+ * another, plain stores only.  It does not read the optimizer's skip word: the step that is skipped is the one whose culprit is wanted.
+ *   partial  one workgroup of 256 threads per map entry.  It reads the chunk's g and p and, only if born[tensor] != 0, its m, and stores per
+ *            chunk: three binary64 sums of squares, each by exactly the chunk contract of frcnn_grad_norm above (element, chunk, wave,
+ *            block -- the same code, so the g partials are the bits frcnn_grad_norm leaves in its workspace; 0 for an unread m), max|g|
+ *            and max|p| (binary32), the int32 non-finite counts of g and p.  Each stream takes 16-byte loads when ITS pointer is 16-byte
+ *            aligned, dword loads otherwise; the element-to-thread assignment is the same.
+ *   finish   one workgroup of T = FRCNN_TENSOR_STATS_FINISH_THREADS threads per tensor over that tensor's k chunk partials, in chunk
+ *            order: thread t starts at +0 and adds partials t, t + T, t + 2T, ... in that order; then the xor butterfly inside each of
+ *            the 4 waves; then ((w0 + w1) + w2) + w3 -- for each of the three sums.  Counts: the same tree in int64, saturated to
+ *            INT32_MAX.  Maxima by max.  k == 0 (a tensor without elements): a row of zeros.  born[tensor] == 0: m_sumsq = +0, m_read = 0.
+ *   advance  one workgroup.  On a measuring call it reads the rows: measured_tick = tick, measures += 1, first_nonfinite_g / _p as above.
+ *            On every call tick = (tick + 1) & INT32_MAX.
+ * Decimation on the device: partial and finish read tick and every first and return before any other load when tick % every != 0;
+ * advance still moves tick.  A captured step therefore measures every Nth replay with one graph; rows, measured_tick and first_nonfinite_*
+ * keep the last measured values in between.  A state block that is not ours (every < 1 or tick < 0), a map entry outside the table, a tensor
+ * whose chunks are not where the map's order puts them: every kernel touches nothing.
+ * Finite values cannot overflow a sum (see frcnn_grad_norm).  tests/tensor_stats_ref.py restates all of it in numpy.
+ *
+ * frcnn_tensor_stats_workspace_bytes(n_tensors, n_chunks): bytes for the partials,
+ *   double g[n_chunks] | double p[n_chunks] | double m[n_chunks] | float gmax[n_chunks] | float pmax[n_chunks] | int32 gbad[n_chunks] |
+ *   int32 pbad[n_chunks]
+ * (at least 16); 0 for n_tensors outside 1 .. 65536 or a negative n_chunks.  16-byte aligned device memory, fully rewritten by a measuring
+ * call, not touched by any other.  FRCNN_ERR_INVALID_ARG before anything is launched: a NULL table / born / rows / state / workspace,
+ * n_tensors outside 1 .. 65536, a negative n_chunks, a table, rows, state or workspace that is not 16-byte aligned, a born that is not
+ * 4-byte aligned, rows, state and workspace that overlap one another; FRCNN_ERR_WORKSPACE: a table shorter than n_tensors and n_chunks
+ * need, a workspace shorter than frcnn_tensor_stats_workspace_bytes(n_tensors, n_chunks). */
+size_t frcnn_tensor_stats_workspace_bytes(int n_tensors, int n_chunks);
+int frcnn_tensor_stats(const void *table, size_t table_bytes, int n_tensors, int n_chunks, const int32_t *born, frcnn_tensor_stats_row *rows,
+                       frcnn_tensor_stats_state *state, void *workspace, size_t workspace_bytes, void *stream);
+
+/* The journal: ring[capacity][n_cols] binary64, marks[capacity] int32, totals[n_cols], one state block, all DEVICE memory.  The caller
+ * writes capacity and n_cols into the state block, zeroes the rest, and initialises every column's totals to
+ * {sum +0, count 0, max -inf, min +inf, nonfinite 0}, outside any graph. */
+typedef struct {
+    double sum;              /*  0  i/o  the sequential binary64 sum of the column's FINITE values, in append order, one rounding per append */
+    int64_t count;           /*  8  i/o  finite values appended */
+    double max;              /* 16  i/o  the largest finite value (`>` comparison); the caller's -inf before the first */
+    double min;              /* 24  i/o  the smallest finite value (`<` comparison); the caller's +inf before the first */
+    int64_t nonfinite;       /* 32  i/o  inf and NaN values appended: in the ring as they are, in none of sum, max, min */
+} frcnn_journal_totals;
+typedef struct {
+    int64_t cursor;          /*  0  i/o  appends so far; the next row goes to ring[cursor % capacity] */
+    int32_t capacity;        /*  8  in   must equal the capacity argument */
+    int32_t n_cols;          /* 12  in   must equal the n_cols argument */
+    int32_t reserved[12];    /* 16       not touched */
+} frcnn_journal_state;
+#define FRCNN_JOURNAL_MAX_COLS 64
+#define FRCNN_JOURNAL_F32 0
+#define FRCNN_JOURNAL_F64 1
+#define FRCNN_JOURNAL_I32 2
+#define FRCNN_JOURNAL_I64 3
+/* frcnn_journal_append: one launch of one wave, no host synchronisation, capturable, no atomics.  src_host / dtype_host are HOST arrays
+ * of n_cols device pointers and FRCNN_JOURNAL_* codes; the library hands them to its kernel BY VALUE in the kernel arguments, which a
+ * graph node stores (a loss tensor's address exists only inside the capture's pool).  Lane c < n_cols reads cursor and its source, widens
+ * the value to binary64 (fp32, int32: exact; int64: round to nearest even), stores ring[cursor % capacity][c], and updates totals[c]:
+ * finite: sum = sum + v (one rounding), count += 1, max, min; otherwise nonfinite += 1.  Behind a barrier lane 0 stores
+ * marks[cursor % capacity] = mark ? *mark : 0 and cursor + 1.  Appends on one stream are ordered, so sum is the sequential binary64 sum in
+ * append order: for a column of fp32 values the bits of SmoothedValue.total (util/misc.py:40-43, fed with loss.item(), the widened fp32),
+ * and sum / count those of its global_avg.  A state block that is not ours (capacity or n_cols differ from the arguments, a negative
+ * cursor): nothing is touched.  tests/journal_ref.py restates it.
+ * FRCNN_ERR_INVALID_ARG before anything is launched: n_cols outside 1 .. 64; capacity < 1; a NULL array, source, ring, marks, totals or
+ * state; a dtype code outside 0 .. 3; a source not aligned to its type; ring or totals not 8-byte aligned, marks or mark not 4-byte
+ * aligned, state not 16-byte aligned; a source (or mark) that overlaps ring, marks, totals or state. */
+int frcnn_journal_append(int n_cols, const void *const *src_host, const int32_t *dtype_host, int capacity, double *ring, int32_t *marks,
+                         frcnn_journal_totals *totals, frcnn_journal_state *state, const int32_t *mark, void *stream);
+
 /* ---- in-library kernel timing (HIP events on the launch stream) -------------------------------------- */
 /* When enabled, every kernel launch made by this library is bracketed by two hipEventRecord on the
  * caller's stream.  frcnn_prof_collect() synchronises those events (call it after the stream is idle)
