@@ -25,6 +25,7 @@ EVAL_ERR_UPSTREAM_ABORT, EVAL_ERR_GT_OVERFLOW, EVAL_ERR_COUNT_RANGE, EVAL_ERR_LA
 EVAL_ERR_LEDGER_OVERFLOW = 16
 EVAL_ERR_SHARD_TRUNCATED = 32
 EVAL_MERGE_MAX_SHARDS = 64
+SGD_CHUNK = 8192                                             # csrc/sgd_dev.h: elements per workgroup of the multi-tensor passes (part of the layout stamp)
 
 _vp, _i, _i64, _f, _u64, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_uint64, C.c_size_t
 
@@ -171,6 +172,11 @@ def check(rc, what=""):
     if rc != OK:
         msg = lib.frcnn_last_error()
         raise FrcnnError("%s failed with status %d: %s" % (what or "libfrcnn_hip", rc, msg.decode() if msg else ""))
+
+
+def sgd_chunks(numels):
+    """The chunks of an SGD or EMA table over tensors of these sizes: what the table builders return as n_chunks."""
+    return sum((int(v) + SGD_CHUNK - 1) // SGD_CHUNK for v in numels)
 
 
 def workspace_bytes(op, n1, n2=0):

@@ -24,22 +24,10 @@
 #include "frcnn_internal.h"
 #include "frcnn_layout.h"
 #include "ema_dev.h"
-#include <algorithm>
-#include <vector>
+#include "multi_tensor_dev.h"
 FRCNN_LAYOUT_STAMP(ema);
 
-// the chunk of this workgroup: false for a table that is not ours (touch nothing)
-__device__ __forceinline__ bool ema_chunk(const EmaRow *__restrict__ rows, const int2 *__restrict__ map, int n_tensors, EmaRow *r, int64_t *off, int *n)
-{
-    const int2 c = map[blockIdx.x];
-    if ((unsigned)c.x >= (unsigned)n_tensors || c.y < 0) return false;
-    *r = rows[c.x];
-    *off = (int64_t)c.y * SGD_CHUNK;
-    if (*off >= r->numel) return false;
-    const int64_t left = r->numel - *off;
-    *n = left < SGD_CHUNK ? (int)left : SGD_CHUNK;
-    return true;
-}
+template <class T> struct EmaRegs { T p, e; };      // one index of a sweep (multi_tensor_dev.h): T is sgd_f4 or float
 
 __global__ __launch_bounds__(SGD_THREADS) void ema_update_kernel(const EmaRow *__restrict__ rows, const int2 *__restrict__ map, int n_tensors,
                                                                  const frcnn_ema_state *__restrict__ st, const int32_t *__restrict__ skip)
@@ -48,57 +36,29 @@ __global__ __launch_bounds__(SGD_THREADS) void ema_update_kernel(const EmaRow *_
     if (st->swapped != 0) return;
     const float w = st->w, wm1 = __fsub_rn(w, 1.0f);
     const bool small = fabsf(w) < 0.5f;
-    EmaRow r;
-    int64_t off;
-    int n;
-    if (!ema_chunk(rows, map, n_tensors, &r, &off, &n)) return;
-    const float *p = r.p + off;
-    float *e = r.e + off;
-    const int tid = threadIdx.x;
-    int done = 0;
-    if (r.vec) {
-        const sgd_f4 *p4 = (const sgd_f4 *)p;
-        sgd_f4 *e4 = (sgd_f4 *)e;
-        const int n4 = n >> 2;
-        for (int base = 0; base < n4; base += 4 * SGD_THREADS) {
-            sgd_f4 vp[4], ve[4];
+    MtChunk<EmaRow> c;
+    if (!mt_chunk(rows, map, n_tensors, &c)) return;                        // a table that is not ours: touch nothing
+    const float *p = c.row.p + c.off;
+    float *e = c.row.e + c.off;
+    const sgd_f4 *p4 = (const sgd_f4 *)p;
+    sgd_f4 *e4 = (sgd_f4 *)e;
+    mt_chunk_sweep<EmaRegs<sgd_f4>, EmaRegs<float>>(
+        c.n, c.row.vec != 0,
+        [&](EmaRegs<sgd_f4> &r, int i) {
+            r.p = p4[i];
+            r.e = e4[i];
+        },
+        [&](EmaRegs<sgd_f4> &r, int i) {
+            sgd_f4 q;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int i = base + k * SGD_THREADS + tid;
-                if (i < n4) {
-                    vp[k] = p4[i];
-                    ve[k] = e4[i];
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int i = base + k * SGD_THREADS + tid;
-                if (i < n4) {
-                    sgd_f4 q;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) q[j] = ema_one(vp[k][j], ve[k][j], w, wm1, small);
-                    e4[i] = q;
-                }
-            }
-        }
-        done = n4 << 2;
-    }
-    for (int base = done; base < n; base += 4 * SGD_THREADS) {              // the tail of an aligned row; all of a misaligned one
-        float vp[4], ve[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int i = base + k * SGD_THREADS + tid;
-            if (i < n) {
-                vp[k] = p[i];
-                ve[k] = e[i];
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int i = base + k * SGD_THREADS + tid;
-            if (i < n) e[i] = ema_one(vp[k], ve[k], w, wm1, small);
-        }
-    }
+            for (int j = 0; j < 4; ++j) q[j] = ema_one(r.p[j], r.e[j], w, wm1, small);
+            e4[i] = q;
+        },
+        [&](EmaRegs<float> &r, int i) {                                     // the tail of an aligned row; all of a misaligned one
+            r.p = p[i];
+            r.e = e[i];
+        },
+        [&](EmaRegs<float> &r, int i) { e[i] = ema_one(r.p, r.e, w, wm1, small); });
 }
 
 // p <-> e, element for element.  Not gated: the way back must always be open.  Workgroup 0's first thread toggles the swapped word; no
@@ -106,58 +66,30 @@ __global__ __launch_bounds__(SGD_THREADS) void ema_update_kernel(const EmaRow *_
 __global__ __launch_bounds__(SGD_THREADS) void ema_swap_kernel(const EmaRow *__restrict__ rows, const int2 *__restrict__ map, int n_tensors, int n_chunks,
                                                                frcnn_ema_state *__restrict__ st)
 {
-    const int tid = threadIdx.x;
-    if (blockIdx.x == 0 && tid == 0) st->swapped = st->swapped == 0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) st->swapped = st->swapped == 0;
     if ((int)blockIdx.x >= n_chunks) return;
-    EmaRow r;
-    int64_t off;
-    int n;
-    if (!ema_chunk(rows, map, n_tensors, &r, &off, &n)) return;
-    float *p = r.p + off, *e = r.e + off;
-    int done = 0;
-    if (r.vec) {
-        sgd_f4 *p4 = (sgd_f4 *)p, *e4 = (sgd_f4 *)e;
-        const int n4 = n >> 2;
-        for (int base = 0; base < n4; base += 4 * SGD_THREADS) {
-            sgd_f4 vp[4], ve[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int i = base + k * SGD_THREADS + tid;
-                if (i < n4) {
-                    vp[k] = p4[i];
-                    ve[k] = e4[i];
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int i = base + k * SGD_THREADS + tid;
-                if (i < n4) {
-                    p4[i] = ve[k];
-                    e4[i] = vp[k];
-                }
-            }
-        }
-        done = n4 << 2;
-    }
-    for (int base = done; base < n; base += 4 * SGD_THREADS) {
-        float vp[4], ve[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int i = base + k * SGD_THREADS + tid;
-            if (i < n) {
-                vp[k] = p[i];
-                ve[k] = e[i];
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int i = base + k * SGD_THREADS + tid;
-            if (i < n) {
-                p[i] = ve[k];
-                e[i] = vp[k];
-            }
-        }
-    }
+    MtChunk<EmaRow> c;
+    if (!mt_chunk(rows, map, n_tensors, &c)) return;                        // a table that is not ours: touch nothing
+    float *p = c.row.p + c.off, *e = c.row.e + c.off;
+    sgd_f4 *p4 = (sgd_f4 *)p, *e4 = (sgd_f4 *)e;
+    mt_chunk_sweep<EmaRegs<sgd_f4>, EmaRegs<float>>(
+        c.n, c.row.vec != 0,
+        [&](EmaRegs<sgd_f4> &r, int i) {
+            r.p = p4[i];
+            r.e = e4[i];
+        },
+        [&](EmaRegs<sgd_f4> &r, int i) {
+            p4[i] = r.e;
+            e4[i] = r.p;
+        },
+        [&](EmaRegs<float> &r, int i) {
+            r.p = p[i];
+            r.e = e[i];
+        },
+        [&](EmaRegs<float> &r, int i) {
+            p[i] = r.e;
+            e[i] = r.p;
+        });
 }
 
 // behind an update, one thread, the only writer of these words.  The next weight in binary64, as the host computes it for n = 0.
@@ -184,19 +116,12 @@ __global__ __launch_bounds__(WAVE) void ema_advance_kernel(frcnn_ema_state *__re
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------
-static int64_t ema_chunks_of(int64_t numel) { return (numel + SGD_CHUNK - 1) / SGD_CHUNK; }
-
 // Bytes of the table for these tensor sizes; 0 for what the builder refuses.
 FRCNN_EXPORT size_t frcnn_ema_table_bytes(int n_tensors, const int64_t *numel_host)
 {
     if (n_tensors < 1 || n_tensors > SGD_MAX_TENSORS || !numel_host) return 0;
-    int64_t chunks = 0;
-    for (int t = 0; t < n_tensors; ++t) {
-        if (numel_host[t] < 0 || numel_host[t] > ((int64_t)1 << 40)) return 0;
-        chunks += ema_chunks_of(numel_host[t]);
-    }
-    if (chunks > 0x7fffffff) return 0;
-    return ema_table_bytes(n_tensors, chunks);
+    const int64_t chunks = mt_table_chunks(n_tensors, numel_host);
+    return chunks < 0 ? 0 : ema_table_bytes(n_tensors, chunks);
 }
 
 // Fills the caller's HOST buffer; the caller uploads table_bytes bytes to 16-byte aligned device memory.
@@ -205,33 +130,20 @@ FRCNN_EXPORT int frcnn_ema_table_build_host(int n_tensors, const void *const *pa
 {
     FRCNN_REQUIRE(params_host && shadows_host && numel_host && table_host && n_chunks_host, "ema_table_build: NULL argument");
     FRCNN_REQUIRE(n_tensors >= 1 && n_tensors <= SGD_MAX_TENSORS, "ema_table_build: n_tensors %d outside 1 .. %d", n_tensors, SGD_MAX_TENSORS);
-    for (int t = 0; t < n_tensors; ++t) {
-        FRCNN_REQUIRE(numel_host[t] >= 0, "ema_table_build: tensor %d has a negative size %lld", t, (long long)numel_host[t]);
-        FRCNN_REQUIRE(numel_host[t] <= ((int64_t)1 << 40), "ema_table_build: tensor %d is too large (%lld elements)", t, (long long)numel_host[t]);
-        FRCNN_REQUIRE(params_host[t] && shadows_host[t], "ema_table_build: NULL pointer in row %d", t);
-        FRCNN_REQUIRE((((uintptr_t)params_host[t] | (uintptr_t)shadows_host[t]) & 3) == 0, "ema_table_build: row %d has a pointer that is not 4-byte aligned", t);
-    }
+    const int rc = mt_check_rows("ema_table_build", n_tensors, numel_host, {params_host, shadows_host});
+    if (rc != FRCNN_OK) return rc;
     const size_t need = frcnn_ema_table_bytes(n_tensors, numel_host);
     FRCNN_REQUIRE(need != 0, "ema_table_build: more than 2^31 - 1 chunks");
     if (table_bytes < need) return frcnn_set_error(FRCNN_ERR_WORKSPACE, "ema_table_build: short table, %zu < %zu bytes", table_bytes, need);
     // both are written (the shadow by the update, both by the swap): no two ranges may overlap, of one row or of two
-    struct Span { uintptr_t lo, hi; int row; char kind; };
     std::vector<Span> w;
-    w.reserve(2 * (size_t)n_tensors);
     for (int t = 0; t < n_tensors; ++t) {
-        const size_t b = (size_t)numel_host[t] * 4;
-        if (b == 0) continue;
-        w.push_back({(uintptr_t)params_host[t], (uintptr_t)params_host[t] + b, t, 'p'});
-        w.push_back({(uintptr_t)shadows_host[t], (uintptr_t)shadows_host[t] + b, t, 'e'});
+        mt_add_span(w, params_host[t], numel_host[t], t, 'p');
+        mt_add_span(w, shadows_host[t], numel_host[t], t, 'e');
     }
-    std::sort(w.begin(), w.end(), [](const Span &a, const Span &b) { return a.lo < b.lo; });
-    for (size_t i = 1; i < w.size(); ++i)
-        FRCNN_REQUIRE(w[i].lo >= w[i - 1].hi, "ema_table_build: overlapping parameter and shadow (%c of row %d and %c of row %d)", w[i - 1].kind,
-                      w[i - 1].row, w[i].kind, w[i].row);
-    char *base = (char *)table_host;
-    EmaHeader *hd = (EmaHeader *)base;
-    EmaRow *rows = (EmaRow *)(base + sizeof(EmaHeader));
-    int2 *map = (int2 *)(base + sizeof(EmaHeader) + (size_t)n_tensors * sizeof(EmaRow));
+    const MtOverlap o = mt_overlap(w, {});
+    FRCNN_REQUIRE(o.what == 0, "ema_table_build: overlapping parameter and shadow (%c of row %d and %c of row %d)", o.a.kind, o.a.row, o.b.kind, o.b.row);
+    const auto [rows, map] = mt_table<EmaHeader, EmaRow>(table_host, n_tensors);
     int64_t c = 0;
     for (int t = 0; t < n_tensors; ++t) {
         rows[t].p = (float *)params_host[t];
@@ -239,10 +151,10 @@ FRCNN_EXPORT int frcnn_ema_table_build_host(int n_tensors, const void *const *pa
         rows[t].numel = numel_host[t];
         rows[t].vec = (((uintptr_t)params_host[t] | (uintptr_t)shadows_host[t]) & 15) == 0;
         rows[t].pad = 0;
-        const int64_t k = ema_chunks_of(numel_host[t]);
+        const int64_t k = mt_chunks_of(numel_host[t]);
         for (int64_t j = 0; j < k; ++j) map[c++] = make_int2(t, (int)j);
     }
-    *hd = EmaHeader{EMA_MAGIC, n_tensors, (int32_t)c, SGD_CHUNK, {0, 0, 0, 0}, sizeof(EmaHeader), sizeof(EmaHeader) + (size_t)n_tensors * sizeof(EmaRow), need, 0};
+    *(EmaHeader *)table_host = EmaHeader{EMA_MAGIC, n_tensors, (int32_t)c, SGD_CHUNK, {0, 0, 0, 0}, sizeof(EmaHeader), sizeof(EmaHeader) + (size_t)n_tensors * sizeof(EmaRow), need, 0};
     *n_chunks_host = (int32_t)c;
     return FRCNN_OK;
 }
@@ -270,8 +182,7 @@ FRCNN_EXPORT int frcnn_ema_update(const void *table, size_t table_bytes, int n_t
 {
     const int rc = ema_check("ema_update", table, table_bytes, n_tensors, n_chunks, state, skip);
     if (rc != FRCNN_OK) return rc;
-    const EmaRow *rows = (const EmaRow *)((const char *)table + sizeof(EmaHeader));
-    const int2 *map = (const int2 *)((const char *)table + sizeof(EmaHeader) + (size_t)n_tensors * sizeof(EmaRow));
+    const auto [rows, map] = mt_table<EmaHeader, EmaRow>(table, n_tensors);
     hipStream_t s = (hipStream_t)stream;
     if (n_chunks > 0)                                                       // every tensor empty: the bookkeeping alone
         FRCNN_LAUNCH(ema_update_kernel, dim3((unsigned)n_chunks), dim3(SGD_THREADS), 0, s, rows, map, n_tensors, (const frcnn_ema_state *)state, skip);
@@ -283,8 +194,7 @@ FRCNN_EXPORT int frcnn_ema_swap(const void *table, size_t table_bytes, int n_ten
 {
     const int rc = ema_check("ema_swap", table, table_bytes, n_tensors, n_chunks, state, nullptr);
     if (rc != FRCNN_OK) return rc;
-    const EmaRow *rows = (const EmaRow *)((const char *)table + sizeof(EmaHeader));
-    const int2 *map = (const int2 *)((const char *)table + sizeof(EmaHeader) + (size_t)n_tensors * sizeof(EmaRow));
+    const auto [rows, map] = mt_table<EmaHeader, EmaRow>(table, n_tensors);
     FRCNN_LAUNCH(ema_swap_kernel, dim3((unsigned)std::max(n_chunks, 1)), dim3(SGD_THREADS), 0, (hipStream_t)stream, rows, map, n_tensors, n_chunks, state);
     FRCNN_CHECK_LAUNCH("ema_swap_kernel");
     return FRCNN_OK;

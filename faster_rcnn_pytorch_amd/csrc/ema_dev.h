@@ -3,6 +3,7 @@
 //   EmaHeader | EmaRow[n_tensors] {parameter, shadow, numel, vec} | int2 map[n_chunks] {tensor, chunk in tensor}
 // Chunked with SGD_CHUNK / SGD_THREADS: for the same tensor sizes the map is entry for entry the SGD table's map, so the fused kernel
 // finds its EMA row under the tensor number of its SGD map entry.  Sizes and offsets are part of the layout stamp (frcnn_layout.h).
+// This header keeps the layout and the rule (ema_one); chunk lookup, sweep and the builder's checks are multi_tensor_dev.h's.
 #pragma once
 #include "frcnn_common.h"
 #include "sgd_dev.h"

@@ -5,8 +5,9 @@
 //     prologue's sampling workgroups (boxes.hip) and READ by topk_partition / topk_bucket (topk.hip), each from its own copy of the
 //     header: two objects compiled against two versions of it disagree about where the splitters, counts and barrier words lie and
 //     how large a bucket can get (round 3, 14:49: DESIGN.md section 7);
-//   * SgdHeader / SgdRow + SGD_CHUNK / SGD_THREADS (sgd_dev.h): the optimizer's table, BUILT in sgd.hip and walked by the kernels of sgd.hip
-//     and grad_norm.hip; frcnn_grad_norm_state (include/frcnn_hip.h): written by grad_norm.hip, its coef and skip words read by sgd.hip's
+//   * SgdHeader / SgdRow + SGD_CHUNK / SGD_THREADS (sgd_dev.h): the optimizer's table, BUILT in sgd.hip and walked by the kernels of sgd.hip,
+//     grad_norm.hip and telemetry.hip, each through multi_tensor_dev.h's chunk lookup (that header holds code, no layout: nothing of it is
+//     stamped); frcnn_grad_norm_state (include/frcnn_hip.h): written by grad_norm.hip, its coef and skip words read by sgd.hip's
 //     kernels through pointers the caller derives from the same struct; frcnn_grad_accum_state (include/frcnn_hip.h): written by
 //     grad_accum.hip, its hold word read by the same kernels as their skip word or user guard;
 //   * EmaHeader / EmaRow (ema_dev.h): the weight average's table, BUILT in ema.hip and walked by the kernels of ema.hip and by sgd.hip's

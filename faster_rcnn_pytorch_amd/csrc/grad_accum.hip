@@ -15,12 +15,12 @@
 //
 // The sources are autograd's gradient tensors: their addresses exist only inside the capture, where no table can be uploaded.  The
 // metadata therefore travels BY VALUE in the kernel arguments, which a graph node stores: GaArgs, GA_ROWS rows of {src, acc, numel, first
-// chunk, both-16-byte-aligned bit}, 2.7 KB of the 4 KB argument segment.  One workgroup of GA_THREADS threads per GA_CHUNK elements of
+// chunk, both-16-byte-aligned bit}, 2.7 KB of the 4 KB argument segment.  One workgroup of SGD_THREADS threads per SGD_CHUNK elements of
 // one row; it finds its row by a binary search over the rows' first-chunk numbers -- uniform, so the compiler keeps it in scalar
 // registers and reads the argument segment with scalar loads.
 //
 // Memory: the copy moves 8 B per element, the add 12 B, nothing reused: a streaming kernel.  16-byte accesses when both pointers of a
-// row are 16-byte aligned (GA_CHUNK is a multiple of 4, so every chunk of such a row starts aligned), four independent float4 pairs in
+// row are 16-byte aligned (SGD_CHUNK is a multiple of 4, so every chunk of such a row starts aligned), four independent float4 pairs in
 // flight per thread, the source loaded non-temporally (it is read once).  Any other row -- the flat gradient buffers' views start at
 // arbitrary element offsets -- takes the dword path for its whole length, four loads in flight per thread.  No atomics, no LDS, no
 // workgroup waits on another.  The library is built with -ffp-contract=off; the add is written out (__fadd_rn).
@@ -28,15 +28,11 @@
 #include "frcnn_internal.h"
 #include "frcnn_layout.h"
 #include "sgd_dev.h"
-#include <algorithm>
-#include <vector>
+#include "multi_tensor_dev.h"
 FRCNN_LAYOUT_STAMP(grad_accum);
 
 #define GA_ROWS FRCNN_GRAD_ACCUM_ROWS
-#define GA_CHUNK SGD_CHUNK
-#define GA_THREADS SGD_THREADS
 static_assert(GA_ROWS % 32 == 0, "one aligned-bit word per 32 rows");
-static_assert(GA_CHUNK % (4 * GA_THREADS) == 0, "a chunk is a whole number of float4 sweeps");
 
 struct GaArgs {
     const float *src[GA_ROWS];
@@ -50,56 +46,49 @@ static_assert(sizeof(GaArgs) <= 3072, "GaArgs and the three other arguments must
 
 enum { GA_COPY = 0, GA_ZERO = 1, GA_ADD = 2 };
 
-template <int MODE>
-__device__ __forceinline__ void ga_chunk(const float *__restrict__ src, float *__restrict__ acc, int n, bool vec, int tid)
+// one index of a sweep (multi_tensor_dev.h): T is sgd_f4 or float.  src and acc are loaded only where the mode reads them.  Zeroed, so that
+// no mode reads an undefined register.  In the ISA the zeroing also moves the waits: every slot is written at the head of a sweep, the
+// compiler waits there once and issues the sweep's loads back to back; left undefined it puts a wait for the sweep before in front of the
+// second and third load.  Both forms were timed once against the parent (profiles/multi_tensor_refactor.json, "ga_regs_zeroed_or_undefined").
+template <class T> struct GaRegs { T s = T(0.0f), a = T(0.0f); };
+
+__device__ __forceinline__ float ga_add(float acc, float src) { return __fadd_rn(acc, src); }
+
+__device__ __forceinline__ sgd_f4 ga_add(sgd_f4 acc, sgd_f4 src)
 {
-    int done = 0;
-    if (vec) {
-        sgd_f4 *a4 = (sgd_f4 *)acc;
-        const sgd_f4 *s4 = (const sgd_f4 *)src;
-        const int n4 = n >> 2;
-        for (int base = 0; base < n4; base += 4 * GA_THREADS) {
-            sgd_f4 vs[4], va[4];
+    sgd_f4 q;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int i = base + k * GA_THREADS + tid;
-                if (i < n4) {
-                    if (MODE != GA_ZERO) vs[k] = __builtin_nontemporal_load(&s4[i]);
-                    if (MODE == GA_ADD) va[k] = a4[i];
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int i = base + k * GA_THREADS + tid;
-                if (i < n4) {
-                    sgd_f4 q;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) q[e] = MODE == GA_ZERO ? 0.0f : MODE == GA_COPY ? vs[k][e] : __fadd_rn(va[k][e], vs[k][e]);
-                    a4[i] = q;
-                }
-            }
-        }
-        done = n4 << 2;
-    }
-    for (int base = done; base < n; base += 4 * GA_THREADS) {               // the tail of an aligned row; all of a misaligned one
-        float vs[4], va[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int i = base + k * GA_THREADS + tid;
-            if (i < n) {
-                if (MODE != GA_ZERO) vs[k] = __builtin_nontemporal_load(&src[i]);
-                if (MODE == GA_ADD) va[k] = acc[i];
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int i = base + k * GA_THREADS + tid;
-            if (i < n) acc[i] = MODE == GA_ZERO ? 0.0f : MODE == GA_COPY ? vs[k] : __fadd_rn(va[k], vs[k]);
-        }
-    }
+    for (int j = 0; j < 4; ++j) q[j] = __fadd_rn(acc[j], src[j]);
+    return q;
 }
 
-__global__ __launch_bounds__(GA_THREADS) void grad_accum_kernel(const GaArgs a, const frcnn_grad_accum_state *__restrict__ st,
+// the table of the file comment: reads of r only what the mode loaded
+template <int MODE, class T> __device__ __forceinline__ T ga_value(const GaRegs<T> &r)
+{
+    if (MODE == GA_ZERO) return T(0.0f);
+    if (MODE == GA_COPY) return r.s;
+    return ga_add(r.a, r.s);
+}
+
+template <int MODE> __device__ __forceinline__ void ga_chunk(const float *__restrict__ src, float *__restrict__ acc, int n, bool vec)
+{
+    sgd_f4 *a4 = (sgd_f4 *)acc;
+    const sgd_f4 *s4 = (const sgd_f4 *)src;
+    mt_chunk_sweep<GaRegs<sgd_f4>, GaRegs<float>>(
+        n, vec,
+        [&](GaRegs<sgd_f4> &r, int i) {
+            if (MODE != GA_ZERO) r.s = __builtin_nontemporal_load(&s4[i]);
+            if (MODE == GA_ADD) r.a = a4[i];
+        },
+        [&](GaRegs<sgd_f4> &r, int i) { a4[i] = ga_value<MODE>(r); },
+        [&](GaRegs<float> &r, int i) {                                      // the tail of an aligned row; all of a misaligned one
+            if (MODE != GA_ZERO) r.s = __builtin_nontemporal_load(&src[i]);
+            if (MODE == GA_ADD) r.a = acc[i];
+        },
+        [&](GaRegs<float> &r, int i) { acc[i] = ga_value<MODE>(r); });
+}
+
+__global__ __launch_bounds__(SGD_THREADS) void grad_accum_kernel(const GaArgs a, const frcnn_grad_accum_state *__restrict__ st,
                                                                 const int32_t *__restrict__ frame_skip)
 {
     const int p = st->phase, w = st->window;
@@ -114,18 +103,17 @@ __global__ __launch_bounds__(GA_THREADS) void grad_accum_kernel(const GaArgs a, 
         if (a.first[mid] <= c) lo = mid;
         else hi = mid;
     }
-    const int64_t off = (int64_t)(c - a.first[lo]) * GA_CHUNK;
+    const int64_t off = (int64_t)(c - a.first[lo]) * SGD_CHUNK;
     const int64_t numel = a.numel[lo];
     if (off < 0 || off >= numel) return;
     const int64_t left = numel - off;
-    const int n = left < GA_CHUNK ? (int)left : GA_CHUNK;
+    const int n = left < SGD_CHUNK ? (int)left : SGD_CHUNK;
     const float *src = a.src[lo] + off;
     float *acc = a.acc[lo] + off;
     const bool vec = (a.vec[lo >> 5] >> (lo & 31)) & 1u;
-    const int tid = threadIdx.x;
-    if (p > 0) ga_chunk<GA_ADD>(src, acc, n, vec, tid);
-    else if (s != 0) ga_chunk<GA_ZERO>(src, acc, n, vec, tid);
-    else ga_chunk<GA_COPY>(src, acc, n, vec, tid);
+    if (p > 0) ga_chunk<GA_ADD>(src, acc, n, vec);
+    else if (s != 0) ga_chunk<GA_ZERO>(src, acc, n, vec);
+    else ga_chunk<GA_COPY>(src, acc, n, vec);
 }
 
 __global__ __launch_bounds__(WAVE) void grad_accum_advance_kernel(frcnn_grad_accum_state *__restrict__ st, const int32_t *__restrict__ frame_skip)
@@ -161,34 +149,20 @@ FRCNN_EXPORT int frcnn_grad_accumulate(int n_tensors, const void *const *src_hos
     FRCNN_REQUIRE(n_tensors >= 1 && n_tensors <= SGD_MAX_TENSORS, "grad_accumulate: n_tensors %d outside 1 .. %d", n_tensors, SGD_MAX_TENSORS);
     FRCNN_REQUIRE(((uintptr_t)state & 15) == 0 && ((uintptr_t)frame_skip & 3) == 0,
                   "grad_accumulate: state must be 16-byte aligned, frame_skip 4-byte aligned");
+    const int rc = mt_check_rows("grad_accumulate", n_tensors, numel_host, {src_host, (const void *const *)acc_host});
+    if (rc != FRCNN_OK) return rc;
+    // written: the acc ranges; read only: the src ranges
+    std::vector<Span> w, ro;
     for (int t = 0; t < n_tensors; ++t) {
-        FRCNN_REQUIRE(numel_host[t] >= 0, "grad_accumulate: tensor %d has a negative size %lld", t, (long long)numel_host[t]);
-        FRCNN_REQUIRE(numel_host[t] <= ((int64_t)1 << 40), "grad_accumulate: tensor %d is too large (%lld elements)", t, (long long)numel_host[t]);
-        FRCNN_REQUIRE(src_host[t] && acc_host[t], "grad_accumulate: NULL pointer in row %d", t);
-        FRCNN_REQUIRE((((uintptr_t)src_host[t] | (uintptr_t)acc_host[t]) & 3) == 0, "grad_accumulate: row %d has a pointer that is not 4-byte aligned", t);
+        mt_add_span(w, acc_host[t], numel_host[t], t, 'a');
+        mt_add_span(ro, src_host[t], numel_host[t], t, 's');
     }
-    // nothing that is written may overlap anything else: acc ranges pairwise, a src range with none of them
-    struct Span { uintptr_t lo, hi; int row; };
-    std::vector<Span> w;
-    w.reserve((size_t)n_tensors);
-    for (int t = 0; t < n_tensors; ++t) {
-        const size_t b = (size_t)numel_host[t] * 4;
-        if (b != 0) w.push_back({(uintptr_t)acc_host[t], (uintptr_t)acc_host[t] + b, t});
-    }
-    std::sort(w.begin(), w.end(), [](const Span &a, const Span &b) { return a.lo < b.lo; });
-    for (size_t i = 1; i < w.size(); ++i)
-        FRCNN_REQUIRE(w[i].lo >= w[i - 1].hi, "grad_accumulate: overlapping acc ranges (rows %d and %d)", w[i - 1].row, w[i].row);
-    for (int t = 0; t < n_tensors; ++t) {
-        const size_t b = (size_t)numel_host[t] * 4;
-        if (b == 0) continue;
-        const uintptr_t lo = (uintptr_t)src_host[t], hi = lo + b;
-        auto it = std::upper_bound(w.begin(), w.end(), lo, [](uintptr_t v, const Span &s) { return v < s.lo; });
-        const bool hit = (it != w.end() && it->lo < hi) || (it != w.begin() && (it - 1)->hi > lo);
-        FRCNN_REQUIRE(!hit, "grad_accumulate: the src of row %d overlaps an acc range", t);
-    }
+    const MtOverlap o = mt_overlap(w, ro);
+    FRCNN_REQUIRE(o.what != 1, "grad_accumulate: overlapping acc ranges (rows %d and %d)", o.a.row, o.b.row);
+    FRCNN_REQUIRE(o.what != 2, "grad_accumulate: the src of row %d overlaps an acc range", o.a.row);
     for (int t0 = 0; t0 < n_tensors; t0 += GA_ROWS) {                       // every launch's chunk count, before the first launch
         int64_t chunks = 0;
-        for (int t = t0; t < n_tensors && t < t0 + GA_ROWS; ++t) chunks += (numel_host[t] + GA_CHUNK - 1) / GA_CHUNK;
+        for (int t = t0; t < n_tensors && t < t0 + GA_ROWS; ++t) chunks += mt_chunks_of(numel_host[t]);
         FRCNN_REQUIRE(chunks <= 0x7fffffff, "grad_accumulate: rows %d .. hold more than 2^31 - 1 chunks", t0);
     }
     hipStream_t s = (hipStream_t)stream;
@@ -204,11 +178,11 @@ FRCNN_EXPORT int frcnn_grad_accumulate(int n_tensors, const void *const *src_hos
             a.numel[r] = numel_host[t];
             a.first[r] = (int32_t)chunks;
             if ((((uintptr_t)src_host[t] | (uintptr_t)acc_host[t]) & 15) == 0) a.vec[r >> 5] |= 1u << (r & 31);
-            chunks += (numel_host[t] + GA_CHUNK - 1) / GA_CHUNK;
+            chunks += mt_chunks_of(numel_host[t]);
         }
         a.n_rows = rows;
         if (chunks == 0) continue;                                          // every tensor of this launch is empty
-        FRCNN_LAUNCH(grad_accum_kernel, dim3((unsigned)chunks), dim3(GA_THREADS), 0, s, a, state, frame_skip);
+        FRCNN_LAUNCH(grad_accum_kernel, dim3((unsigned)chunks), dim3(SGD_THREADS), 0, s, a, state, frame_skip);
         launched = true;
     }
     if (!launched) return FRCNN_OK;                                         // every tensor is empty: the runtime is not touched

@@ -20,6 +20,7 @@
 #include "frcnn_internal.h"
 #include "frcnn_layout.h"
 #include "sgd_dev.h"
+#include "multi_tensor_dev.h"
 #include "sumsq_dev.h"
 FRCNN_LAYOUT_STAMP(grad_norm);
 
@@ -29,22 +30,12 @@ static_assert(GN_FINISH_THREADS % WAVE == 0 && GN_FINISH_THREADS <= 1024, "the f
 __global__ __launch_bounds__(SGD_THREADS) void grad_norm_partial_kernel(const SgdRow *__restrict__ rows, const int2 *__restrict__ map, int n_tensors,
                                                                         double *__restrict__ partial, int32_t *__restrict__ bad_out)
 {
-    const int2 c = map[blockIdx.x];
-    const float *g = nullptr;
-    int n = 0;                                                              // a table that is not ours: a zero partial, nothing read
-    if ((unsigned)c.x < (unsigned)n_tensors && c.y >= 0) {
-        const SgdRow r = rows[c.x];
-        const int64_t off = (int64_t)c.y * SGD_CHUNK;
-        if (off < r.numel) {
-            const int64_t left = r.numel - off;
-            n = left < SGD_CHUNK ? (int)left : SGD_CHUNK;
-            g = r.g + off;
-        }
-    }
+    MtChunk<SgdRow> c = {};                                                 // a table that is not ours: c stays zeroed -- a zero partial, nothing read
+    mt_chunk(rows, map, n_tensors, &c);
     const int tid = threadIdx.x;
     int bad;
     float unused;
-    const double s = sumsq_chunk_wave<false>(g, n, tid, bad, unused);      // element, chunk, wave of the contract: sumsq_dev.h
+    const double s = sumsq_chunk_wave<false>(c.row.g + c.off, c.n, tid, bad, unused);   // element, chunk, wave of the contract: sumsq_dev.h
     __shared__ double ws[SGD_THREADS / WAVE];
     __shared__ int wb[SGD_THREADS / WAVE];
     if ((tid & (WAVE - 1)) == 0) {
@@ -124,8 +115,7 @@ FRCNN_EXPORT int frcnn_grad_norm(const void *table, size_t table_bytes, int n_te
     if (table_bytes < need) return frcnn_set_error(FRCNN_ERR_WORKSPACE, "grad_norm: short table, %zu < %zu bytes", table_bytes, need);
     const size_t ws_need = frcnn_grad_norm_workspace_bytes(n_chunks);
     if (workspace_bytes < ws_need) return frcnn_set_error(FRCNN_ERR_WORKSPACE, "grad_norm: short workspace, %zu < %zu bytes", workspace_bytes, ws_need);
-    const SgdRow *rows = (const SgdRow *)((const char *)table + sizeof(SgdHeader));
-    const int2 *map = (const int2 *)((const char *)table + sizeof(SgdHeader) + (size_t)n_tensors * sizeof(SgdRow));
+    const auto [rows, map] = mt_table<SgdHeader, SgdRow>(table, n_tensors);
     double *partial = (double *)workspace;
     int32_t *bad = (int32_t *)((char *)workspace + (size_t)n_chunks * sizeof(double));
     hipStream_t s = (hipStream_t)stream;

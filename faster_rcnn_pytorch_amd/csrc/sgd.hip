@@ -20,14 +20,13 @@
 // Memory: 12 B read + 8 B written per element, nothing reused: a streaming kernel.  16-byte accesses when a tensor's three pointers are
 // 16-byte aligned (SGD_CHUNK is a multiple of 4, so every chunk of such a tensor starts aligned), four independent float4 triples in flight
 // per thread; the gradient is read once and loaded non-temporally.  Any other tensor (a view at an odd storage offset) takes the
-// dword path for its whole length -- its three pointers need not share a misalignment, so there is no common peel.
+// dword path for its whole length, four dwords per array in flight.  The chunk lookup and the sweep are multi_tensor_dev.h's.
 #include "frcnn_common.h"
 #include "frcnn_internal.h"
 #include "frcnn_layout.h"
 #include "sgd_dev.h"
 #include "ema_dev.h"
-#include <algorithm>
-#include <vector>
+#include "multi_tensor_dev.h"
 FRCNN_LAYOUT_STAMP(sgd);
 
 __device__ __forceinline__ float sgd_one(float p, float g, float *m, float neg_lr, float mu, float wd, bool use_wd, bool keep, bool first)
@@ -40,6 +39,9 @@ __device__ __forceinline__ float sgd_one(float p, float g, float *m, float neg_l
     }
     return __fmaf_rn(neg_lr, mn, p);
 }
+
+// one index of a sweep (multi_tensor_dev.h): T is sgd_f4 or float.  m and e are loaded only where the rule reads them.
+template <class T> struct SgdRegs { T p, g, m = T(0.0f), e = T(0.0f); };
 
 // SCALE = false: the rule above on the gradient as it is.  SCALE = true: every gradient element is first multiplied by the device float
 // *grad_scale (one rounding, __fmul_rn) -- the bits of torch's in-place g.mul_(coef) followed by torch.optim.SGD; the gradient itself is
@@ -67,81 +69,62 @@ __global__ __launch_bounds__(SGD_THREADS) void sgd_update_kernel(const SgdRow *_
     }
     float gs = 1.0f;
     if (SCALE) gs = *grad_scale;
-    const int2 c = map[blockIdx.x];
-    if ((unsigned)c.x >= (unsigned)n_tensors || c.y < 0) return;           // a table that is not ours: touch nothing
-    const SgdRow r = rows[c.x];
+    MtChunk<SgdRow> c;
+    if (!mt_chunk(rows, map, n_tensors, &c)) return;                        // a table that is not ours: touch nothing
+    const SgdRow &r = c.row;
     if ((unsigned)r.group >= (unsigned)n_groups) return;
-    const int64_t off = (int64_t)c.y * SGD_CHUNK;
-    if (off >= r.numel) return;
-    const int64_t left = r.numel - off;
-    const int n = left < SGD_CHUNK ? (int)left : SGD_CHUNK;
     const float4 h = hyper[r.group];
     const float neg_lr = -h.x, mu = h.y, wd = h.z;
-    const bool use_wd = wd != 0.0f, keep = mu != 0.0f, first = born[c.x] == 0;
-    float *p = r.p + off, *m = r.m + off;
-    const float *g = r.g + off;
+    const bool use_wd = wd != 0.0f, keep = mu != 0.0f, first = born[c.tensor] == 0;
+    float *p = r.p + c.off, *m = r.m + c.off;
+    const float *g = r.g + c.off;
     float *e = nullptr;
     bool vec = r.vec != 0;
     if (EMA) {
-        const EmaRow er = erows[c.x];
+        const EmaRow er = erows[c.tensor];
         if (er.p != r.p || er.numel != r.numel) return;                    // an EMA table that is not this table's: touch nothing
-        e = er.e + off;
+        e = er.e + c.off;
         vec = vec && er.vec != 0;
     }
-    const int tid = threadIdx.x;
-    int done = 0;
-    if (vec) {
-        sgd_f4 *p4 = (sgd_f4 *)p, *m4 = (sgd_f4 *)m, *e4 = (sgd_f4 *)e;
-        const sgd_f4 *g4 = (const sgd_f4 *)g;
-        const int n4 = n >> 2;
-        for (int base = 0; base < n4; base += 4 * SGD_THREADS) {
-            sgd_f4 vp[4], vg[4], vm[4], ve[4];
+    sgd_f4 *p4 = (sgd_f4 *)p, *m4 = (sgd_f4 *)m, *e4 = (sgd_f4 *)e;
+    const sgd_f4 *g4 = (const sgd_f4 *)g;
+    mt_chunk_sweep<SgdRegs<sgd_f4>, SgdRegs<float>>(
+        c.n, vec,
+        [&](SgdRegs<sgd_f4> &v, int i) {
+            v.p = p4[i];
+            v.g = __builtin_nontemporal_load(&g4[i]);
+            if (keep && !first) v.m = m4[i];
+            if (EMA) v.e = e4[i];
+        },
+        [&](SgdRegs<sgd_f4> &v, int i) {
+            sgd_f4 q;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int i = base + k * SGD_THREADS + tid;
-                if (i < n4) {
-                    vp[k] = p4[i];
-                    vg[k] = __builtin_nontemporal_load(&g4[i]);
-                    if (keep && !first) vm[k] = m4[i];
-                    if (EMA) ve[k] = e4[i];
-                }
+            for (int j = 0; j < 4; ++j) {
+                float mj = v.m[j];
+                q[j] = sgd_one(v.p[j], SCALE ? __fmul_rn(v.g[j], gs) : v.g[j], &mj, neg_lr, mu, wd, use_wd, keep, first);
+                v.m[j] = mj;
             }
+            if (keep) m4[i] = v.m;
+            p4[i] = q;
+            if (EMA) {
+                sgd_f4 a;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int i = base + k * SGD_THREADS + tid;
-                if (i < n4) {
-                    sgd_f4 q, mv = vm[k];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float me = mv[e];
-                        const float ge = SCALE ? __fmul_rn(vg[k][e], gs) : vg[k][e];
-                        q[e] = sgd_one(vp[k][e], ge, &me, neg_lr, mu, wd, use_wd, keep, first);
-                        mv[e] = me;
-                    }
-                    if (keep) m4[i] = mv;
-                    p4[i] = q;
-                    if (EMA) {
-                        sgd_f4 a;
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) a[j] = ema_one(q[j], ve[k][j], w, wm1, small);
-                        e4[i] = a;
-                    }
-                }
+                for (int j = 0; j < 4; ++j) a[j] = ema_one(q[j], v.e[j], w, wm1, small);
+                e4[i] = a;
             }
-        }
-        done = n4 << 2;
-    }
-    for (int i = done + tid; i < n; i += SGD_THREADS) {                     // the tail of an aligned tensor; all of a misaligned one
-        float mv = 0.0f;
-        if (keep && !first) mv = m[i];
-        float ev = 0.0f;
-        if (EMA) ev = e[i];
-        const float ge = SCALE ? __fmul_rn(g[i], gs) : g[i];
-        const float q = sgd_one(p[i], ge, &mv, neg_lr, mu, wd, use_wd, keep, first);
-        if (keep) m[i] = mv;
-        p[i] = q;
-        if (EMA) e[i] = ema_one(q, ev, w, wm1, small);
-    }
+        },
+        [&](SgdRegs<float> &v, int i) {                                     // the tail of an aligned tensor; all of a misaligned one
+            v.p = p[i];
+            v.g = g[i];
+            if (keep && !first) v.m = m[i];
+            if (EMA) v.e = e[i];
+        },
+        [&](SgdRegs<float> &v, int i) {
+            const float q = sgd_one(v.p, SCALE ? __fmul_rn(v.g, gs) : v.g, &v.m, neg_lr, mu, wd, use_wd, keep, first);
+            if (keep) m[i] = v.m;
+            p[i] = q;
+            if (EMA) e[i] = ema_one(q, v.e, w, wm1, small);
+        });
 }
 
 // after the update: a tensor whose group keeps momentum has one now
@@ -160,19 +143,12 @@ __global__ __launch_bounds__(SGD_THREADS) void sgd_born_kernel(const SgdRow *__r
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------
-static int64_t sgd_chunks_of(int64_t numel) { return (numel + SGD_CHUNK - 1) / SGD_CHUNK; }
-
 // main.py:58-61 / train.py:35-37.  Bytes of the table for these tensor sizes; 0 for what the builder refuses.
 FRCNN_EXPORT size_t frcnn_sgd_table_bytes(int n_tensors, const int64_t *numel_host)
 {
     if (n_tensors < 1 || n_tensors > SGD_MAX_TENSORS || !numel_host) return 0;
-    int64_t chunks = 0;
-    for (int t = 0; t < n_tensors; ++t) {
-        if (numel_host[t] < 0 || numel_host[t] > ((int64_t)1 << 40)) return 0;
-        chunks += sgd_chunks_of(numel_host[t]);
-    }
-    if (chunks > 0x7fffffff) return 0;
-    return sgd_table_bytes(n_tensors, chunks);
+    const int64_t chunks = mt_table_chunks(n_tensors, numel_host);
+    return chunks < 0 ? 0 : sgd_table_bytes(n_tensors, chunks);
 }
 
 // main.py:58-61 / train.py:35-37.  Fills the caller's HOST buffer; the caller uploads table_bytes bytes to 16-byte aligned device memory.
@@ -183,43 +159,24 @@ FRCNN_EXPORT int frcnn_sgd_table_build_host(int n_tensors, const void *const *pa
     FRCNN_REQUIRE(params_host && grads_host && moms_host && numel_host && group_host && table_host && n_chunks_host, "sgd_table_build: NULL argument");
     FRCNN_REQUIRE(n_tensors >= 1 && n_tensors <= SGD_MAX_TENSORS, "sgd_table_build: n_tensors %d outside 1 .. %d", n_tensors, SGD_MAX_TENSORS);
     FRCNN_REQUIRE(n_groups >= 1 && n_groups <= SGD_MAX_GROUPS, "sgd_table_build: n_groups %d outside 1 .. %d", n_groups, SGD_MAX_GROUPS);
-    for (int t = 0; t < n_tensors; ++t) {
-        FRCNN_REQUIRE(numel_host[t] >= 0, "sgd_table_build: tensor %d has a negative size %lld", t, (long long)numel_host[t]);
-        FRCNN_REQUIRE(numel_host[t] <= ((int64_t)1 << 40), "sgd_table_build: tensor %d is too large (%lld elements)", t, (long long)numel_host[t]);
-        FRCNN_REQUIRE(params_host[t] && grads_host[t] && moms_host[t], "sgd_table_build: NULL pointer in row %d", t);
+    const int rc = mt_check_rows("sgd_table_build", n_tensors, numel_host, {params_host, grads_host, moms_host});
+    if (rc != FRCNN_OK) return rc;
+    for (int t = 0; t < n_tensors; ++t)
         FRCNN_REQUIRE(group_host[t] >= 0 && group_host[t] < n_groups, "sgd_table_build: row %d names group %d outside 0 .. %d", t, group_host[t], n_groups - 1);
-        FRCNN_REQUIRE((((uintptr_t)params_host[t] | (uintptr_t)grads_host[t] | (uintptr_t)moms_host[t]) & 3) == 0,
-                      "sgd_table_build: row %d has a pointer that is not 4-byte aligned", t);
-    }
     const size_t need = frcnn_sgd_table_bytes(n_tensors, numel_host);
     FRCNN_REQUIRE(need != 0, "sgd_table_build: more than 2^31 - 1 chunks");
     if (table_bytes < need) return frcnn_set_error(FRCNN_ERR_WORKSPACE, "sgd_table_build: short table, %zu < %zu bytes", table_bytes, need);
-    // nothing that is written may overlap anything else: parameter and momentum ranges pairwise (all rows), a gradient with neither
-    struct Span { uintptr_t lo, hi; int row; char kind; };
-    std::vector<Span> w;
-    w.reserve(2 * (size_t)n_tensors);
+    // written: parameter and momentum ranges (all rows); read only: the gradients
+    std::vector<Span> w, ro;
     for (int t = 0; t < n_tensors; ++t) {
-        const size_t b = (size_t)numel_host[t] * 4;
-        if (b == 0) continue;
-        w.push_back({(uintptr_t)params_host[t], (uintptr_t)params_host[t] + b, t, 'p'});
-        w.push_back({(uintptr_t)moms_host[t], (uintptr_t)moms_host[t] + b, t, 'm'});
+        mt_add_span(w, params_host[t], numel_host[t], t, 'p');
+        mt_add_span(w, moms_host[t], numel_host[t], t, 'm');
+        mt_add_span(ro, grads_host[t], numel_host[t], t, 'g');
     }
-    std::sort(w.begin(), w.end(), [](const Span &a, const Span &b) { return a.lo < b.lo; });
-    for (size_t i = 1; i < w.size(); ++i)
-        FRCNN_REQUIRE(w[i].lo >= w[i - 1].hi, "sgd_table_build: overlapping parameter and momentum (%c of row %d and %c of row %d)",
-                      w[i - 1].kind, w[i - 1].row, w[i].kind, w[i].row);
-    for (int t = 0; t < n_tensors; ++t) {
-        const size_t b = (size_t)numel_host[t] * 4;
-        if (b == 0) continue;
-        const uintptr_t lo = (uintptr_t)grads_host[t], hi = lo + b;
-        auto it = std::upper_bound(w.begin(), w.end(), lo, [](uintptr_t v, const Span &s) { return v < s.lo; });
-        const bool hit = (it != w.end() && it->lo < hi) || (it != w.begin() && (it - 1)->hi > lo);
-        FRCNN_REQUIRE(!hit, "sgd_table_build: the gradient of row %d overlaps a parameter or a momentum", t);
-    }
-    char *base = (char *)table_host;
-    SgdHeader *hd = (SgdHeader *)base;
-    SgdRow *rows = (SgdRow *)(base + sizeof(SgdHeader));
-    int2 *map = (int2 *)(base + sizeof(SgdHeader) + (size_t)n_tensors * sizeof(SgdRow));
+    const MtOverlap o = mt_overlap(w, ro);
+    FRCNN_REQUIRE(o.what != 1, "sgd_table_build: overlapping parameter and momentum (%c of row %d and %c of row %d)", o.a.kind, o.a.row, o.b.kind, o.b.row);
+    FRCNN_REQUIRE(o.what != 2, "sgd_table_build: the gradient of row %d overlaps a parameter or a momentum", o.a.row);
+    const auto [rows, map] = mt_table<SgdHeader, SgdRow>(table_host, n_tensors);
     int64_t c = 0;
     for (int t = 0; t < n_tensors; ++t) {
         const uintptr_t all = (uintptr_t)params_host[t] | (uintptr_t)grads_host[t] | (uintptr_t)moms_host[t];
@@ -230,11 +187,11 @@ FRCNN_EXPORT int frcnn_sgd_table_build_host(int n_tensors, const void *const *pa
         rows[t].group = group_host[t];
         rows[t].vec = (all & 15) == 0;
         rows[t].pad[0] = rows[t].pad[1] = 0;
-        const int64_t k = sgd_chunks_of(numel_host[t]);
+        const int64_t k = mt_chunks_of(numel_host[t]);
         for (int64_t j = 0; j < k; ++j) map[c++] = make_int2(t, (int)j);
     }
-    *hd = SgdHeader{SGD_MAGIC, n_tensors, n_groups, (int32_t)c, SGD_CHUNK, {0, 0, 0}, sizeof(SgdHeader),
-                    sizeof(SgdHeader) + (size_t)n_tensors * sizeof(SgdRow), need, 0};
+    *(SgdHeader *)table_host = SgdHeader{SGD_MAGIC, n_tensors, n_groups, (int32_t)c, SGD_CHUNK, {0, 0, 0}, sizeof(SgdHeader),
+                      sizeof(SgdHeader) + (size_t)n_tensors * sizeof(SgdRow), need, 0};
     *n_chunks_host = (int32_t)c;
     return FRCNN_OK;
 }
@@ -256,9 +213,8 @@ static int sgd_step_launch(const char *who, const void *table, size_t table_byte
         return frcnn_set_error(FRCNN_ERR_WORKSPACE, "%s: short EMA table, %zu < %zu bytes", who, ema_bytes, ema_table_bytes(n_tensors, n_chunks));
     hipStream_t s = (hipStream_t)stream;
     if (n_chunks == 0) return ema ? ema_advance_launch(ema_state, skip, s) : FRCNN_OK;      // every tensor is empty
-    const SgdRow *rows = (const SgdRow *)((const char *)table + sizeof(SgdHeader));
-    const int2 *map = (const int2 *)((const char *)table + sizeof(SgdHeader) + (size_t)n_tensors * sizeof(SgdRow));
-    const EmaRow *erows = ema ? (const EmaRow *)((const char *)ema_table + sizeof(EmaHeader)) : nullptr;
+    const auto [rows, map] = mt_table<SgdHeader, SgdRow>(table, n_tensors);
+    const EmaRow *erows = ema ? mt_table<EmaHeader, EmaRow>(ema_table, n_tensors).rows : nullptr;
     const frcnn_ema_state *est = ema ? ema_state : nullptr;
     const float *gs = scaled ? grad_scale : nullptr;
 #define SGD_UPDATE(S, E)                                                                                                                            \

@@ -1,5 +1,6 @@
-// sgd_dev.h -- the multi-tensor table of the optimizer (built in sgd.hip), shared by layout between sgd.hip (the update) and grad_norm.hip
-// (the gradient norm in front of it):
+// sgd_dev.h -- the multi-tensor table of the optimizer (built in sgd.hip), shared by layout between sgd.hip (the update), grad_norm.hip
+// (the gradient norm in front of it) and telemetry.hip (the per-tensor statistics); grad_accum.hip takes the two constants.  The code these
+// files share -- chunk lookup, sweep, host-side checks -- is multi_tensor_dev.h's, the chunk body of the sums of squares sumsq_dev.h's.
 //   SgdHeader | SgdRow[n_tensors] {parameter, gradient, momentum, numel, group, vec} | int2 map[n_chunks] {tensor, chunk in tensor}
 // One workgroup of SGD_THREADS threads per map entry, SGD_CHUNK elements of one tensor.  Sizes, offsets and the two constants are part of
 // the layout stamp (frcnn_layout.h).

@@ -22,6 +22,7 @@
 #include "frcnn_internal.h"
 #include "frcnn_layout.h"
 #include "sgd_dev.h"
+#include "multi_tensor_dev.h"
 #include "sumsq_dev.h"
 FRCNN_LAYOUT_STAMP(telemetry);
 
@@ -56,20 +57,11 @@ __global__ __launch_bounds__(SGD_THREADS) void tensor_stats_partial_kernel(const
                                                                            const TsWork w)
 {
     if (!ts_measures(st)) return;                                           // before any other load
-    const int2 c = map[blockIdx.x];
-    const float *g = nullptr, *p = nullptr, *m = nullptr;
-    int n = 0;                                                              // a table that is not ours: zero partials, nothing read
-    if ((unsigned)c.x < (unsigned)n_tensors && c.y >= 0) {
-        const SgdRow r = rows[c.x];
-        const int64_t off = (int64_t)c.y * SGD_CHUNK;
-        if (off < r.numel) {
-            const int64_t left = r.numel - off;
-            n = left < SGD_CHUNK ? (int)left : SGD_CHUNK;
-            g = r.g + off;
-            p = r.p + off;
-            if (born[c.x] != 0) m = r.m + off;                              // an unborn momentum is never loaded
-        }
-    }
+    MtChunk<SgdRow> c = {};                                                 // a table that is not ours: c stays zeroed -- zero partials, nothing read
+    mt_chunk(rows, map, n_tensors, &c);
+    const int n = c.n;
+    const float *g = c.row.g + c.off, *p = c.row.p + c.off;
+    const float *m = (n != 0 && born[c.tensor] != 0) ? c.row.m + c.off : nullptr;      // an unborn momentum is never loaded
     const int tid = threadIdx.x;
     int gbad, pbad, unused_bad;
     float gmax, pmax, unused_max;
@@ -115,7 +107,7 @@ __global__ __launch_bounds__(TS_FINISH_THREADS) void tensor_stats_finish_kernel(
     if (t >= n_tensors) return;
     const int64_t numel = rows[t].numel;
     if (numel < 0) return;
-    const int64_t k64 = (numel + SGD_CHUNK - 1) / SGD_CHUNK;
+    const int64_t k64 = mt_chunks_of(numel);
     int lo = 0, hi = n_chunks;                                              // the first map entry of a tensor >= t: uniform, scalar loads
     while (lo < hi) {
         const int mid = lo + ((hi - lo) >> 1);
@@ -289,8 +281,7 @@ FRCNN_EXPORT int frcnn_tensor_stats(const void *table, size_t table_bytes, int n
     FRCNN_REQUIRE(!tm_overlap(rows, rows_bytes, state, sizeof(*state)) && !tm_overlap(rows, rows_bytes, workspace, ws_need) &&
                       !tm_overlap(state, sizeof(*state), workspace, ws_need),
                   "tensor_stats: rows, state and workspace overlap");
-    const SgdRow *trows = (const SgdRow *)((const char *)table + sizeof(SgdHeader));
-    const int2 *map = (const int2 *)((const char *)table + sizeof(SgdHeader) + (size_t)n_tensors * sizeof(SgdRow));
+    const auto [trows, map] = mt_table<SgdHeader, SgdRow>(table, n_tensors);
     const TsWork w = ts_carve(workspace, n_chunks);
     hipStream_t s = (hipStream_t)stream;
     if (n_chunks > 0)

@@ -213,6 +213,16 @@ def ema_weight(decay, warmup, n):
     return 1.0 - (min(decay, (1 + n) / (10 + n)) if warmup else decay)
 
 
+def _build_table(builder, table, *rows):
+    """One table build for prepare(): `builder` (frcnn_sgd_table_build_host or frcnn_ema_table_build_host) fills a pinned host block from
+    `rows`, its leading arguments, and the block is uploaded into the device tensor `table` asynchronously.  Returns n_chunks."""
+    host = torch.empty(table.numel(), dtype=torch.uint8).pin_memory()     # a fresh staging block per build: the copy below is asynchronous
+    n_chunks = C.c_int32(0)
+    _lib.check(getattr(_lib.lib, builder)(*rows, C.c_void_p(host.data_ptr()), table.numel(), C.byref(n_chunks)), builder)
+    table.copy_(host, non_blocking=True)
+    return int(n_chunks.value)
+
+
 def _trainable(params):
     """Tensors or torch-style parameter groups -> the trainable parameters in DeviceSGD's row order."""
     out = []
@@ -321,13 +331,9 @@ class WeightEMA(object):
         n = len(self._params)
         vp = C.c_void_p * n
         spare = self._state.data_ptr()                                    # an empty tensor has no address; its row is legal but may not be NULL
-        host = torch.empty(self._table_bytes, dtype=torch.uint8).pin_memory()                 # a fresh staging block per build: the copy below is asynchronous
-        n_chunks = C.c_int32(0)
-        _lib.check(_lib.lib.frcnn_ema_table_build_host(n, vp(*[p.data_ptr() or spare for p in self._params]), vp(*[e.data_ptr() or spare for e in self.shadow]),
-                                                       self._numel, C.c_void_p(host.data_ptr()), self._table_bytes, C.byref(n_chunks)),
-                   "frcnn_ema_table_build_host")
-        self._table.copy_(host, non_blocking=True)
-        self._n_chunks, self._key = int(n_chunks.value), key
+        self._n_chunks = _build_table("frcnn_ema_table_build_host", self._table, n, vp(*[p.data_ptr() or spare for p in self._params]),
+                                      vp(*[e.data_ptr() or spare for e in self.shadow]), self._numel)
+        self._key = key
 
     def _head(self):
         return C.c_void_p(self._table.data_ptr()), self._table_bytes, len(self._params), self._n_chunks
@@ -576,7 +582,7 @@ class DeviceSGD(torch.optim.Optimizer):
                                "prepare()) on the final gradient tensors before the capture")
         n = len(self._rows)
         if (self._clip or self._skip_nonfinite) and self._gn_state is None:   # once; the kernels and every graph hold these addresses
-            chunks = sum((int(v) + 8191) // 8192 for v in self._numel)
+            chunks = _lib.sgd_chunks(self._numel)
             self._gn_work_bytes = int(_lib.lib.frcnn_grad_norm_workspace_bytes(chunks))
             with torch.no_grad():
                 self._gn_work = torch.empty(self._gn_work_bytes, dtype=torch.uint8, device=self.device)
@@ -585,14 +591,10 @@ class DeviceSGD(torch.optim.Optimizer):
                                                                                     (GN_SKIP_NONFINITE if self._skip_nonfinite else 0))
             self._push_max_norm()
         vp = C.c_void_p * n
-        host = torch.empty(self._table_bytes, dtype=torch.uint8).pin_memory()                 # a fresh staging block per build: the copy below is asynchronous
-        n_chunks = C.c_int32(0)
-        _lib.check(_lib.lib.frcnn_sgd_table_build_host(
-            n, vp(*[p.data_ptr() for p, _ in self._rows]), vp(*[g.data_ptr() for g in gs]),
-            vp(*[self.state[p]["momentum_buffer"].data_ptr() for p, _ in self._rows]), self._numel, self._group, len(self.param_groups),
-            C.c_void_p(host.data_ptr()), self._table_bytes, C.byref(n_chunks)), "frcnn_sgd_table_build_host")
-        self._table.copy_(host, non_blocking=True)
-        self._n_chunks, self._key = int(n_chunks.value), key
+        self._n_chunks = _build_table("frcnn_sgd_table_build_host", self._table, n, vp(*[p.data_ptr() for p, _ in self._rows]),
+                                      vp(*[g.data_ptr() for g in gs]), vp(*[self.state[p]["momentum_buffer"].data_ptr() for p, _ in self._rows]),
+                                      self._numel, self._group, len(self.param_groups))
+        self._key = key
 
     def launch(self):
         """The library launches alone (what a graph records): no hyper-parameter write.  With tensor_stats its three launches come first

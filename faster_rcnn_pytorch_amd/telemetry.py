@@ -86,7 +86,7 @@ class TensorStats(object):
         self.optimizer, self.names, self.every = optimizer, names, _check_every(every)
         self.device = optimizer.device
         self._n = n
-        self._chunks = sum((int(v) + 8191) // 8192 for v in optimizer._numel)
+        self._chunks = _lib.sgd_chunks(optimizer._numel)
         self._work_bytes = int(_lib.lib.frcnn_tensor_stats_workspace_bytes(n, self._chunks))
         if self._work_bytes == 0:
             raise _lib.FrcnnError("TensorStats: frcnn_tensor_stats_workspace_bytes refuses %d tensors in %d chunks" % (n, self._chunks))

@@ -13,7 +13,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 import sgd_ref  # noqa: E402
 
-CHUNK = 8192                                     # csrc/sgd.hip: SGD_CHUNK
+CHUNK = 8192                                     # csrc/sgd_dev.h: SGD_CHUNK
+SWEEP1, SWEEP4 = 1024, 4096                      # csrc/multi_tensor_dev.h: the elements of one dword sweep and of one 16-byte sweep
 LENS = [1, 3, 4, 5, 63, 64, 65, 255, 256, 257]
 KEEP_INPUTS_BELOW = 4096
 KEEP_FINAL_BELOW = 20000
@@ -96,15 +97,18 @@ def main():
     kinds["two groups"] = 2
 
     # E: one length on either side of the kernel's chunk, and the chunk itself      F: 300 tensors      G: ~1 M elements, many chunks
+    # H: the lengths around one dword sweep and one 16-byte sweep of the kernel (and 4100: a whole sweep, one more group of four)
     seeded = [("chunk_edges", [CHUNK - 1, CHUNK, CHUNK + 1], [0, 0, 0], hyper_table(3, [(2e-3, 0.9, 5e-4)]), 11),
               ("three_hundred_tensors", [LENS[i % 10] if i < 100 else LENS[i % 7] for i in range(300)], [i % 2 for i in range(300)],
                hyper_table(3, [(2e-3, 0.9, 5e-4), (1e-3, 0.9, 1e-4)]), 12),
-              ("long_tensor", [1000003], [0], hyper_table(3, [[(2e-3, 0.9, 5e-4), (2e-3, 0.9, 5e-4), (2e-4, 0.9, 5e-4)]]), 13)]
+              ("long_tensor", [1000003], [0], hyper_table(3, [[(2e-3, 0.9, 5e-4), (2e-3, 0.9, 5e-4), (2e-4, 0.9, 5e-4)]]), 13),
+              ("sweep_seams", [SWEEP1 - 1, SWEEP1, SWEEP1 + 1, SWEEP4 - 1, SWEEP4, SWEEP4 + 1, SWEEP4 + 4], [0] * 7, hyper_table(3, [(2e-3, 0.9, 5e-4)]), 14)]
     for name, lens, group, hyper, seed in seeded:
         p0, g = sgd_ref.seeded_inputs(seed, sum(lens), hyper.shape[0])
         cases.append((name, lens, group, hyper, p0, g, seed))
     kinds["lengths around the chunk"] = 2
     kinds["300 tensors"] = len(seeded[1][1])
+    kinds["lengths around the sweeps"] = len(seeded[3][1])
     kinds["elements of the long tensor"] = seeded[2][1][0]
 
     out = {"n_cases": np.int64(len(cases))}

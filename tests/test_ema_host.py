@@ -138,6 +138,7 @@ def test_table_builder_layout_refusals_and_the_sgd_map(L):
         (dict(shadows=es[:4] + [ps[4] + 4 * 19999]), "overlapping parameter and shadow"),        # e of row 4 on the last element of its own p
         (dict(params=ps[:4] + [ps[1]]), "overlapping parameter and shadow"),                     # two p
         (dict(shadows=es[:4] + [es[2] + 4 * 8192]), "overlapping parameter and shadow"),         # two e, one element shared
+        (dict(shadows=[es[0], ps[2] - 4 * 8191] + es[2:]), "overlapping parameter and shadow (e of row 1 and p of row 2)"),     # the last of e, the first of p
     ]
     for change, text in bad:
         kw = dict(params=ps, shadows=es, numel=numel)
@@ -145,6 +146,7 @@ def test_table_builder_layout_refusals_and_the_sgd_map(L):
         rc, msg, _, _, _ = _build(L, **kw)
         assert rc == -1 and text in msg, (change, rc, msg)
     assert _build(L, ps, es[:4] + [es[2] + 4 * 8193], numel)[0] == 0       # touching ranges are no overlap
+    assert _build(L, ps, [es[0], ps[2] - 4 * 8192] + es[2:], numel)[0] == 0  # nor an e that ends where a p begins
     rc, msg, _, need, _ = _build(L, ps, es, numel, table_bytes=need - 8)
     assert rc == -3 and "short table" in msg
     assert L.lib.frcnn_ema_table_build_host(5, None, None, None, None, 0, None) == -1 and b"NULL argument" in L.lib.frcnn_last_error()

@@ -23,9 +23,11 @@ import sgd_ref
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-SIZES = [0, 1, 3, 4, 5, 1023, 1024, 1025, 8191, 8192, 8193, 2 * 8192 + 1025]
-P_OFF = [0, 1, 2, 3, 0, 0, 1, 2, 3, 0, 0, 1]           # elements past a 16-byte boundary
-E_OFF = [0, 0, 1, 2, 3, 1, 0, 3, 2, 2, 0, 1]           # index 4, 5, 9: the shadow misaligned under an aligned parameter; 10: both aligned; 11: both off by one
+SEAMS = [4095, 4096, 4097, 4100]                       # around one 16-byte sweep of 4096 elements; the dword sweep's 1023, 1024, 1025 stand below
+SIZES = [0, 1, 3, 4, 5, 1023, 1024, 1025, 8191, 8192, 8193, 2 * 8192 + 1025] + SEAMS + SEAMS
+P_OFF = [0, 1, 2, 3, 0, 0, 1, 2, 3, 0, 0, 1] + [0, 0, 0, 0] + [0, 1, 0, 1]           # elements past a 16-byte boundary
+E_OFF = [0, 0, 1, 2, 3, 1, 0, 3, 2, 2, 0, 1] + [0, 0, 0, 0] + [1, 0, 1, 0]           # index 4, 5, 9: the shadow misaligned under an aligned parameter; 10: both aligned; 11: both off by one
+G_OFF = [0, 0, 2, 1, 3, 0, 2, 1, 3, 0, 0, 1] + [0, 0, 0, 0] + [0, 0, 0, 0]           # 12-15: every pointer of the row aligned; 16-19: exactly one off by one element
 SPECIALS = [np.inf, -np.inf, np.nan, -0.0, 1e-40]
 EDGES = (0, 8191, 8192, 2 * 8192 - 1, 2 * 8192)
 
@@ -121,9 +123,8 @@ class _Set(object):
     def __init__(self, fused, variant, hyper, sizes=SIZES[1:], place=None):
         from faster_rcnn_pytorch_amd import optim
         rs = np.random.RandomState(22)
-        n = len(sizes)
         self.ps = _params(_values(rs, sizes), P_OFF[1:], place)
-        self.gs = [_view(np.zeros(s, np.float32), o, place) for s, o in zip(sizes, ([0, 2, 1, 3, 0, 2, 1, 3, 0, 0, 1] * n)[:n])]
+        self.gs = [_view(np.zeros(s, np.float32), o, place) for s, o in zip(sizes, G_OFF[1:])]
         self.es = [_view(np.zeros(s, np.float32), o, place) for s, o in zip(sizes, E_OFF[1:])]
         for p, g in zip(self.ps, self.gs):
             p.grad = g
@@ -180,7 +181,7 @@ def test_fused_step_equals_device_sgd_step_then_update(variant, hyper):
     skipped = 1 + int("skip_nonfinite" in VARIANTS[variant])
     assert moved[0] == 1 and moved[1] == 1 and moved[-1] == 5 - skipped and sa["ema"]["skipped"] == skipped and sa["ema"]["refused"] == 0
     assert not _same(np.concatenate(sa["e"]), np.concatenate(start["e"])) and _slack_untouched(a.ps + a.gs + a.es)
-    assert sa["born"] == [int(GROUP_HYPER[hyper][0][0] != 0)] * 6 + [int(GROUP_HYPER[hyper][1][0] != 0)] * 5
+    assert sa["born"] == [int(GROUP_HYPER[hyper][0][0] != 0)] * 10 + [int(GROUP_HYPER[hyper][1][0] != 0)] * 9
 
 
 # ------------------------------------------------------------------------------------------------- 3. skipping, against the fixture

@@ -29,7 +29,8 @@ SENTINEL = -12345.5
 def _sizes():
     from faster_rcnn_pytorch_amd import _lib
     R = int(_lib.lib.frcnn_grad_accum_rows_per_launch())
-    return [0, 1, 3, 4, 5, 8191, 8192, 8193, 2 * 8192 + 5] + [7] * (R + 1)     # the R + 1 small ones cross a launch boundary
+    seams = [1023, 1024, 1025, 4095, 4096, 4097, 4100]                      # around one dword sweep (1024) and one 16-byte sweep (4096)
+    return [0, 1, 3, 4, 5] + seams + [8191, 8192, 8193, 2 * 8192 + 5] + [7] * (R + 1)     # the R + 1 small ones cross a launch boundary
 
 
 def _sources(sizes):

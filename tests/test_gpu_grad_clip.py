@@ -239,6 +239,7 @@ class _Pair(object):
 
 
 SHAPES = [(3, 5), (64,), (17, 33), (1,), (9000,), (4, 3, 3, 3)]
+SEAMS = [(1023,), (1024,), (1025,), (4095,), (4096,), (4097,), (4100,)]      # around one dword sweep (1024) and one 16-byte sweep (4096) of the update
 
 
 def _two_groups(ps):
@@ -250,7 +251,9 @@ def _one_group(ps):
 
 
 def test_five_clipped_steps_two_groups_equal_torch_on_the_cpu_and_leave_the_gradients_alone():
-    pair = _Pair(SHAPES, 21, _two_groups, p_offs=[0, 1, 0, 2, 0, 3], g_offs=[1, 0, 0, 3, 2, 0], max_grad_norm=5.0)
+    # the seam sizes once with every pointer of the row 16-byte aligned, once with exactly one of them off by one element
+    pair = _Pair(SHAPES + SEAMS + SEAMS, 21, _two_groups, p_offs=[0, 1, 0, 2, 0, 3] + [0] * 7 + [1, 0, 1, 0, 1, 0, 1],
+                 g_offs=[1, 0, 0, 3, 2, 0] + [0] * 7 + [0, 1, 0, 1, 0, 1, 0], max_grad_norm=5.0)
     coefs = []
     for s in range(5):
         if s == 3:

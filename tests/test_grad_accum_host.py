@@ -102,6 +102,13 @@ def test_accumulate_refuses_bad_arguments_before_touching_the_device(L):
                              ([0x100000, 0x300000 + 396], [0x300000, 0x400000], "src of row 1 overlaps"),
                              ([0x400000 - 396, 0x200000], [0x300000, 0x400000], "src of row 0 overlaps")):
         refused((2,) + _arrays(srcs, accs, [100, 200]) + ok[4:], text)
+    # ranges that only touch do not overlap: 18 rows of 2^40 elements, every acc and every src beginning where the one before ends, pass the
+    # overlap check and are refused by the one behind it (no accepted call may follow: it would launch on these made-up addresses)
+    big, step = 2 ** 40, 2 ** 42
+    refused((18,) + _arrays([0x1000 + (18 + t) * step for t in range(18)], [0x1000 + t * step for t in range(18)], [big] * 18) + ok[4:],
+            "more than 2^31 - 1 chunks")
+    refused((18,) + _arrays([0x1000 + (18 + t) * step - 4 for t in range(18)], [0x1000 + t * step for t in range(18)], [big] * 18) + ok[4:],
+            "src of row 0 overlaps")                                        # the same, every src one element lower: its first is the last of an acc
     # the NULL and alignment checks come for empty rows too; overlap is about bytes, so an empty row overlaps nothing
     refused((2,) + _arrays([0, 0x200000], [0x300000, 0x400000], [0, 200]) + ok[4:], "NULL pointer")
     assert f(2, *_arrays([0x300000, 0x300000], [0x300000, 0x300000], [0, 0]), S, None, None) == 0      # every tensor empty: nothing is launched

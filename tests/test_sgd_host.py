@@ -25,10 +25,11 @@ def cases():
 
 def test_golden_file_holds_every_kind_of_case(cases):
     names = [c.name for c in cases]
-    assert names == ["lengths_five_steps", "wd0_inf_parameter", "momentum_zero", "two_groups", "chunk_edges", "three_hundred_tensors", "long_tensor"]
+    assert names == ["lengths_five_steps", "wd0_inf_parameter", "momentum_zero", "two_groups", "chunk_edges", "three_hundred_tensors", "long_tensor", "sweep_seams"]
     by = dict(zip(names, cases))
     assert by["lengths_five_steps"].lens.tolist() == [1, 3, 4, 5, 63, 64, 65, 255, 256, 257] and by["lengths_five_steps"].steps == 5
     assert by["chunk_edges"].lens.tolist() == [8191, 8192, 8193]
+    assert by["sweep_seams"].lens.tolist() == [1023, 1024, 1025, 4095, 4096, 4097, 4100]
     assert len(by["three_hundred_tensors"].lens) == 300 and by["long_tensor"].total > 1000000
     a = by["lengths_five_steps"]
     assert a.hyper[1, 0, 0] != a.hyper[2, 0, 0] and np.isnan(a.g).sum() == 1 and (np.signbit(a.g) & (a.g == 0)).sum() >= 4
@@ -112,6 +113,10 @@ def test_table_builder_layout_and_refusals(L):
         (dict(moms=ms[:4] + [ps[4] + 4 * 19999]), "overlapping parameter and momentum"),
         (dict(params=ps[:4] + [ps[1]]), "overlapping parameter and momentum"),
         (dict(grads=[gs[0], ps[1] + 4] + gs[2:]), "gradient of row 1 overlaps"),
+        # the shared disjointness check (csrc/multi_tensor_dev.h), branch by branch: rows 1 and 2 hold 8192 and 8193 elements
+        (dict(moms=[ms[0], ms[2] - 4 * 8191] + ms[2:]), "overlapping parameter and momentum (m of row 1 and m of row 2)"),      # one element shared
+        (dict(grads=[gs[0], ps[2] + 4 * 8192] + gs[2:]), "gradient of row 1 overlaps"),          # its first element is the last of p of row 2
+        (dict(grads=[gs[0], ps[2] - 4 * 8191] + gs[2:]), "gradient of row 1 overlaps"),          # its last element is the first of p of row 2
         (dict(group=[0, 1, 2, 0, 0]), "names group 2 outside 0 .. 1"),
         (dict(group=[0, -1, 0, 0, 0]), "names group -1"),
         (dict(params=[ps[0] + 2] + ps[1:]), "not 4-byte aligned"),
@@ -122,6 +127,11 @@ def test_table_builder_layout_and_refusals(L):
         kw.update(change)
         rc, msg, _, _, _ = _build(L, **kw)
         assert rc == -1 and text in msg, (change, rc, msg)
+    for change in (dict(moms=[ms[0], ms[2] - 4 * 8192] + ms[2:]), dict(grads=[gs[0], ps[2] - 4 * 8192] + gs[2:]),
+                   dict(grads=[gs[0], ps[2] + 4 * 8193] + gs[2:])):                              # ranges that only touch do not overlap
+        kw = dict(params=ps, grads=gs, moms=ms, numel=numel, group=[0, 1, 0, 1, 1], n_groups=2)
+        kw.update(change)
+        assert _build(L, **kw)[0] == 0, change
     rc, msg, _, need, _ = _build(L, ps, gs, ms, numel, [0, 1, 0, 1, 1], 2, table_bytes=need - 8)
     assert rc == -3 and "short table" in msg
     assert L.lib.frcnn_sgd_table_build_host(5, None, None, None, None, None, 2, None, 0, None) == -1 and b"NULL argument" in L.lib.frcnn_last_error()
