@@ -20,6 +20,9 @@ OP_EVAL = 12
 OP_COCO_EVAL = 13
 OP_EVAL_MERGE = 14
 OP_COCO_EVAL_POOLED = 15
+OP_DETECT_MERGE = 16
+MERGE_COUNT_CLIPPED, MERGE_UPSTREAM_ABORT, MERGE_LABEL_RANGE, MERGE_CLASS_OVERFLOW, MERGE_OUTPUT_OVERFLOW = 1, 2, 4, 8, 16   # frcnn_detect_merge's status bits
+MERGE_MAX_SETS, MERGE_MAX_CANDIDATES = 8, 2048
 EVAL_TP, EVAL_FP, EVAL_IGNORED = 1, 2, 3                     # a record's flags: 2 bits per threshold
 EVAL_ERR_UPSTREAM_ABORT, EVAL_ERR_GT_OVERFLOW, EVAL_ERR_COUNT_RANGE, EVAL_ERR_LABEL_RANGE = 1, 2, 4, 8
 EVAL_ERR_LEDGER_OVERFLOW = 16
@@ -95,6 +98,7 @@ SIGNATURES = {
     "frcnn_ms_roi_align_bwd_workspace": (_sz, [_vp, _vp, _i, _i, _i64]),
     "frcnn_detection_loss": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "frcnn_detect_postprocess": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _f, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "frcnn_detect_merge": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _sz, _vp]),
     "frcnn_eval_update": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
                                 _vp, _sz, _vp]),
     "frcnn_eval_average_precision": (_i, [_vp, _vp, _vp, _i64, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -18,13 +18,14 @@
 #include "frcnn_dev.h"
 #include "frcnn_layout.h"
 #include "nms_dev.h"
+#include "detect_dev.h"
 FRCNN_LAYOUT_STAMP(detect);
 
 #define DET_MAX_P 2048
 #define DET_MAX_C 256
 #define DET_THREADS 256
 
-typedef unsigned long long u64;
+typedef det_u64 u64;
 
 static bool det_supported(int64_t P, int64_t C) { return P >= 1 && P <= DET_MAX_P && C >= 2 && C <= DET_MAX_C; }
 
@@ -96,15 +97,6 @@ __global__ __launch_bounds__(DET_THREADS) void detect_decode_kernel(const float 
     }
 }
 
-// (score descending, row ascending) as one ascending 64-bit key; scores here are > thr, hence not NaN.  -0 is folded onto +0: the
-// reference's sort sees them as equal.
-__device__ __forceinline__ u64 det_key(float score, int r)
-{
-    uint32_t u = __float_as_uint(score == 0.0f ? 0.0f : score);
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);               // monotone in the float's value
-    return ((u64)(~u) << 32) | (uint32_t)r;
-}
-
 __global__ __launch_bounds__(DET_THREADS) void detect_nms_kernel(const float4 *__restrict__ ws_box, const float *__restrict__ ws_score,
                                                                  const int32_t *__restrict__ n_dev, int P, float thr_val,
                                                                  const float *__restrict__ thr_dev, float nms_thr, int32_t *__restrict__ ws_kept,
@@ -126,7 +118,7 @@ __global__ __launch_bounds__(DET_THREADS) void detect_nms_kernel(const float4 *_
     // candidates (model.py:391): the slot order is arbitrary, the sort below makes the result deterministic
     for (int r = tid; r < n; r += DET_THREADS) {
         const float sc = ws_score[base + r];
-        if (sc > thr) s_key[atomicAdd(&s_m, 1)] = det_key(sc, r);
+        if (sc > thr) s_key[atomicAdd(&s_m, 1)] = det_key(sc, (uint32_t)r);
     }
     __syncthreads();
     const int m = s_m;
@@ -134,17 +126,7 @@ __global__ __launch_bounds__(DET_THREADS) void detect_nms_kernel(const float4 *_
     while (M < m) M <<= 1;
     for (int i = m + tid; i < M; i += DET_THREADS) s_key[i] = ~0ull;
     __syncthreads();
-    // bitonic sort of M keys, ascending
-    for (int k = 2; k <= M; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < (M >> 1); t += DET_THREADS) {
-                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-                const int l = i + j;
-                const u64 a = s_key[i], b = s_key[l];
-                if ((a > b) == ((i & k) == 0)) { s_key[i] = b; s_key[l] = a; }
-            }
-            __syncthreads();
-        }
+    det_bitonic_sort<DET_THREADS>(s_key, M, tid);                 // ascending: (score desc, row asc), detect_dev.h
     for (int p = tid; p < m; p += DET_THREADS) {
         const float4 b = ws_box[base + (uint32_t)s_key[p]];
         s_box[p] = b;

@@ -16,4 +16,13 @@ __device__ __forceinline__ bool nms_suppress_exact(float4 a, float area_a, float
     const float inter = w * h;
     return inter / (area_a + area_b - inter) > thr;
 }
+
+// the quotient nms_suppress_exact compares, by the same instructions: for a caller that tests it another way (detect_merge.hip's voters, >=)
+__device__ __forceinline__ float nms_iou_exact(float4 a, float area_a, float4 b, float area_b)
+{
+    const float w = vmaxf(vminf(a.z, b.z) - vmaxf(a.x, b.x), 0.0f);
+    const float h = vmaxf(vminf(a.w, b.w) - vmaxf(a.y, b.y), 0.0f);
+    const float inter = w * h;
+    return inter / (area_a + area_b - inter);
+}
 #endif  // __HIPCC__

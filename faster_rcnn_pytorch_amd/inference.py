@@ -69,3 +69,65 @@ class DetectGraph(object):
         self.x.copy_(x)
         self.graph.replay()
         return self.out
+
+
+class TTADetectGraph(object):
+    """model.detect_tta at fixed input sizes, captured into one torch.cuda.graph: one static [1, 3, H, W] input per entry of view_hws, the
+    mirrored copy of each (hflip=True) made inside the graph, detect on every view one after the other on the capture stream -- no side
+    streams, so the graph is one chain -- the merge of the views' detections (ops.merge_detections; vote_threshold=None leaves box voting
+    off) and, with evaluator= and gt= as in DetectGraph, the evaluator's update on the MERGED set.
+
+    __call__(xs) takes one frame per size (a single tensor when there is one size), copies each into its static buffer, replays, and
+    returns the graph's static ops.MergedDetections: overwritten by the next call.  set_threshold() works as in DetectGraph: the views'
+    score threshold is a device tensor read at replay time."""
+
+    def __init__(self, model, view_hws, hflip=True, threshold=0.05, nms_threshold=0.3, vote_threshold=None, evaluator=None, gt=None, device=None,
+                 warmup=2):
+        m = getattr(model, "module", model)                     # a DDP-wrapped model: capture the module itself
+        dev = torch.device(device) if device is not None else next(m.parameters()).device
+        view_hws = list(view_hws)
+        if view_hws and isinstance(view_hws[0], int):            # one (H, W)
+            view_hws = [tuple(view_hws)]
+        self.view_hws = [(int(h), int(w)) for h, w in view_hws]
+        if not self.view_hws:
+            raise ValueError("TTADetectGraph: no view size")
+        if (evaluator is None) != (gt is None):
+            raise ValueError("TTADetectGraph: evaluator= and gt= go together")
+        self.model, self.evaluator, self.gt, self.hflip = m, evaluator, gt, bool(hflip)
+        self.xs = [torch.zeros((1, 3, h, w), dtype=torch.float32, device=dev) for h, w in self.view_hws]
+        self.threshold = torch.full((1,), float(threshold), dtype=torch.float32, device=dev)
+
+        def detect():
+            views = []
+            for x in self.xs:
+                views.append((x, False))
+                if self.hflip:
+                    views.append((x.flip(-1), True))
+            return m.detect_tta(views, float(threshold), threshold_dev=self.threshold, nms_threshold=nms_threshold, vote_threshold=vote_threshold)
+        # eager warm-up on a side stream, as DetectGraph: lazy allocations, cached constants and anchor grids, workspaces
+        side = torch.cuda.Stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            for _ in range(max(int(warmup), 1)):
+                out = detect()
+            if evaluator is not None:
+                evaluator._workspace(out.labels.numel(), gt.capacity)             # the update's zeroed workspace: allocated outside the capture
+        torch.cuda.current_stream(dev).wait_stream(side)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            self.out = detect()
+            if evaluator is not None:
+                evaluator.update(self.out, gt)
+
+    def set_threshold(self, t):
+        """Writes the device threshold in place: the next replay uses it."""
+        self.threshold.fill_(float(t))
+
+    def __call__(self, xs):
+        xs = [xs] if isinstance(xs, torch.Tensor) else list(xs)
+        if len(xs) != len(self.xs) or any(tuple(x.shape) != tuple(b.shape) for x, b in zip(xs, self.xs)):
+            raise ValueError("TTADetectGraph: captured for inputs %s, got %s" % ([tuple(b.shape) for b in self.xs], [tuple(x.shape) for x in xs]))
+        for x, b in zip(xs, self.xs):
+            b.copy_(x)
+        self.graph.replay()
+        return self.out

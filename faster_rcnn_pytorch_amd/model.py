@@ -337,6 +337,21 @@ class _Detector(nn.Module):
         dets = ops.detect_postprocess(head_cls, head_reg, rois, n_rois, threshold, 0.3, threshold_dev=threshold_dev, want_prob=want_prob)
         return (dets, self._proposal_detections(rois, n_rois)) if want_proposals else dets
 
+    @torch.no_grad()
+    def detect_tta(self, views, threshold, threshold_dev=None, nms_threshold=0.3, vote_threshold=None):
+        """Test-time augmentation without a host sync (graph-capturable): detect on every view, one after the other on the current
+        stream, then ops.merge_detections.  views: one tensor x, which stands for the two views x and x.flip(-1), or a list of
+        (x_k, mirrored) pairs of any input size each -- mirrored=True says x_k is the frame flipped horizontally, so its boxes are
+        mirrored back; normalised boxes need nothing else across scales.  The merge takes every detection of the views (their scores
+        passed `threshold` already), suppresses per class at nms_threshold and, with vote_threshold, replaces every kept box by the
+        score-weighted mean of the candidates that overlap it that much.  Returns ops.MergedDetections."""
+        if isinstance(views, torch.Tensor):
+            views = [(views, False), (views.flip(-1), True)]
+        views = list(views)
+        sets = [self.detect(x, threshold, threshold_dev=threshold_dev) for x, _ in views]
+        return ops.merge_detections(sets, hflip=[bool(f) for _, f in views], num_classes=self.num_classes, min_score=float("-inf"),
+                                    nms_threshold=nms_threshold, vote_threshold=vote_threshold)
+
     def _suppress(self, raw_cls_bbox, raw_prob, threshold):
         """models/model.py:382-402 (per-class score mask + nms(0.3), class 0 = background skipped, results concatenated
         class by class) as ONE class-aware NMS: 2 host syncs in total instead of 2 per class."""

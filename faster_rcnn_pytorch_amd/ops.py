@@ -379,6 +379,82 @@ def detect_postprocess(head_cls, head_reg, rois, n_rois, threshold, nms_threshol
     return Detections(boxes, labels, scores, count, class_counts, prob, n_rois)
 
 
+class MergedDetections(Detections):
+    """The Detections of merge_detections: the same tuple (prob is None, n_rois the first set's), and `status`, a device int32[1] of
+    _lib.MERGE_* bits (0 = nothing to report).  count = -1 after an upstream abort, more than 2048 candidates in a class, or a kept total
+    above the capacity: to_host() raises then, and the evaluators flag the frame."""
+
+    def __new__(cls, boxes, labels, scores, count, class_counts, prob, n_rois, status):
+        self = super().__new__(cls, boxes, labels, scores, count, class_counts, prob, n_rois)
+        self.status = status
+        return self
+
+    def to_host(self):
+        n = host_count(self.count, "merge_detections")
+        return self.boxes[:n].cpu(), self.labels[:n].cpu(), self.scores[:n].cpu()
+
+
+def describe_merge_status(bits):
+    """Names of the _lib.MERGE_* bits set in a MergedDetections.status word."""
+    names = ((_lib.MERGE_COUNT_CLIPPED, "a set's count exceeded its capacity"), (_lib.MERGE_UPSTREAM_ABORT, "a set's count was negative (an aborted scan upstream)"),
+             (_lib.MERGE_LABEL_RANGE, "a live row's label lay outside 0 .. C-2"),
+             (_lib.MERGE_CLASS_OVERFLOW, "a class held more than %d candidates" % _lib.MERGE_MAX_CANDIDATES),
+             (_lib.MERGE_OUTPUT_OVERFLOW, "the kept total exceeded the output capacity"))
+    return [n for b, n in names if bits & b]
+
+
+def merge_detections(sets, hflip=None, vflip=None, num_classes=None, min_score=0.0, nms_threshold=0.3, vote_threshold=None, capacity=None):
+    """Merges K <= 8 Detections of one frame -- the views of test-time augmentation, the results of two weight sets -- into one, in two
+    launches and no host sync (frcnn_detect_merge, include/frcnn_hip.h): per class the live rows of every set with score > min_score, in
+    (score descending, set ascending, row ascending) order, greedy nms(nms_threshold), class-major concatenation.  hflip / vflip: one bool
+    per set, True where the view was mirrored (its boxes are mirrored back: 1 - x, 1 - y on normalised coordinates).  vote_threshold (None
+    = off): box voting, every kept box becomes the score-weighted mean of the class's candidates with IoU >= vote_threshold.  The rows may
+    come in any order and class_counts is not read, so the proposal Detections merge as well.  capacity: the output's rows, by default
+    min(the sets' capacities summed, (num_classes - 1) * 2048).  Returns MergedDetections."""
+    sets = list(sets)
+    K = len(sets)
+    if not 1 <= K <= _lib.MERGE_MAX_SETS:
+        raise ValueError("merge_detections: %d sets, 1 .. %d are supported" % (K, _lib.MERGE_MAX_SETS))
+    if num_classes is None:
+        raise ValueError("merge_detections: num_classes= is required")
+    C_ = int(num_classes)
+    hflip = [False] * K if hflip is None else [bool(v) for v in hflip]
+    vflip = [False] * K if vflip is None else [bool(v) for v in vflip]
+    if len(hflip) != K or len(vflip) != K:
+        raise ValueError("merge_detections: hflip / vflip need one entry per set")
+    boxes, labels, scores, counts = [], [], [], []
+    for k, d in enumerate(sets):
+        boxes.append(_req(d.boxes, name="sets[%d].boxes" % k).reshape(-1, 4))
+        labels.append(_req(d.labels, torch.int32, "sets[%d].labels" % k).reshape(-1))
+        scores.append(_req(d.scores, name="sets[%d].scores" % k).reshape(-1))
+        counts.append(_req(d.count, torch.int32, "sets[%d].count" % k).reshape(-1))
+        if labels[k].numel() != boxes[k].shape[0] or scores[k].numel() != boxes[k].shape[0] or counts[k].numel() < 1:
+            raise ValueError("merge_detections: set %d: boxes %s, labels %s, scores %s disagree" % (k, tuple(d.boxes.shape), tuple(d.labels.shape), tuple(d.scores.shape)))
+        if boxes[k].device != boxes[0].device:
+            raise ValueError("merge_detections: the sets lie on different devices")
+    caps = [int(b.shape[0]) for b in boxes]
+    dev = boxes[0].device
+    cap = min(sum(caps), max(C_ - 1, 1) * _lib.MERGE_MAX_CANDIDATES) if capacity is None else int(capacity)
+    n = max(cap, 1)
+    out_boxes = torch.empty((n, 4), dtype=torch.float32, device=dev)
+    out_labels = torch.empty((n,), dtype=torch.int32, device=dev)
+    out_scores = torch.empty((n,), dtype=torch.float32, device=dev)
+    count = torch.empty((1,), dtype=torch.int32, device=dev)
+    class_counts = torch.empty((max(C_ - 1, 1),), dtype=torch.int32, device=dev)
+    status = torch.empty((1,), dtype=torch.int32, device=dev)
+    nb = _lib.workspace_bytes(_lib.OP_DETECT_MERGE, max(cap, 0), C_)
+    ws = _workspace(dev, nb)
+    vp = C.c_void_p * K
+    with torch.cuda.device(dev):
+        check(lib.frcnn_detect_merge(K, vp(*[t.data_ptr() for t in boxes]), vp(*[t.data_ptr() for t in labels]), vp(*[t.data_ptr() for t in scores]),
+                                     vp(*[t.data_ptr() for t in counts]), (C.c_int64 * K)(*caps),
+                                     (C.c_uint32 * K)(*[int(h) | (int(v) << 1) for h, v in zip(hflip, vflip)]), C_, float(min_score),
+                                     float(nms_threshold), -1.0 if vote_threshold is None else float(vote_threshold), _ptr(out_boxes),
+                                     _ptr(out_labels), _ptr(out_scores), _ptr(count), _ptr(class_counts), _ptr(status), cap, _ptr(ws), nb, _stream()),
+              "detect_merge")
+    return MergedDetections(out_boxes, out_labels, out_scores, count, class_counts, None, sets[0].n_rois, status)
+
+
 def _eval_update_args(op, dets, n_gt, frame, thresholds, counter, rec_score, rec_label, rec_image, rec_order, rec_flags, flags_width,
                       cursor, error_word):
     """What eval_update and coco_eval_update check alike: the Detections' fields, n_gt, frame, thresholds, the counter = (name, tensor,

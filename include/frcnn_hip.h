@@ -62,7 +62,8 @@ typedef enum {
     FRCNN_OP_EVAL = 12,           /* n1 = detection capacity, n2 = ground-truth capacity: frcnn_eval_update (0 outside its limits) */
     FRCNN_OP_COCO_EVAL = 13,      /* n1 = detection capacity, n2 = ground-truth capacity: frcnn_coco_eval_update (0 outside its limits) */
     FRCNN_OP_EVAL_MERGE = 14,     /* n1 = W * shard record capacity, n2 = W * shard image capacity: frcnn_eval_merge (0 outside its limits) */
-    FRCNN_OP_COCO_EVAL_POOLED = 15 /* n1 = detection capacity, n2 = ground-truth capacity: frcnn_coco_eval_update_pooled (0 outside its limits) */
+    FRCNN_OP_COCO_EVAL_POOLED = 15, /* n1 = detection capacity, n2 = ground-truth capacity: frcnn_coco_eval_update_pooled (0 outside its limits) */
+    FRCNN_OP_DETECT_MERGE = 16    /* n1 = out_capacity, n2 = C classes: frcnn_detect_merge (0 outside its limits) */
 } frcnn_op;
 
 /* FRCNN_ABI_VERSION, or FRCNN_ERR_UNSUPPORTED (message in frcnn_last_error) when the objects the library was linked from were compiled
@@ -508,6 +509,51 @@ int frcnn_detect_postprocess(const float *head_cls /*[P,C] logits*/, const float
                              int32_t *out_count /*[1]*/, int32_t *out_class_counts /*[C-1] or NULL*/,
                              float *out_prob /*[P,C] or NULL*/,
                              void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- merge of detection sets (test-time augmentation; defined by this project, docs/PARITY.md) --------------------- */
+/* Bits of *out_status (0 = nothing to report).  ABORT, CLASS_OVERFLOW and OUTPUT_OVERFLOW also give *out_count = -1. */
+#define FRCNN_MERGE_COUNT_CLIPPED 1u     /* a set's count exceeded its capacity: the capacity was used */
+#define FRCNN_MERGE_UPSTREAM_ABORT 2u    /* a set's count was negative (an aborted scan upstream): the set contributes nothing */
+#define FRCNN_MERGE_LABEL_RANGE 4u       /* a live row's label lay outside 0 .. C-2: the row was skipped */
+#define FRCNN_MERGE_CLASS_OVERFLOW 8u    /* a class held more than FRCNN_MERGE_MAX_CANDIDATES candidates: the class comes out empty */
+#define FRCNN_MERGE_OUTPUT_OVERFLOW 16u  /* the kept total exceeded out_capacity: the rows past it were not written */
+#define FRCNN_MERGE_MAX_SETS 8
+#define FRCNN_MERGE_MAX_CANDIDATES 2048
+/* K fixed-capacity detection sets with device counts -> one set of the same shape, in two launches whatever the data holds and no host
+ * sync (graph-capturable).  The six per-set arrays are HOST arrays of K entries; their values travel by value in the kernel arguments,
+ * so nothing host-side is read when a captured graph replays.  Everything below is device data.
+ * Transform: set k's live rows are 0 .. *counts[k]-1; a count above caps[k] uses caps[k] (COUNT_CLIPPED); a negative count makes the set
+ *   contribute nothing and gives *out_count = -1 (UPSTREAM_ABORT).  flags[k] bit 0: the view was mirrored horizontally, the box becomes
+ *   (1.0f - x2, y1, 1.0f - x1, y2), one fp32 subtraction each; bit 1: the same for y.  No other transform.  Areas are
+ *   (x2 - x1) * (y2 - y1) in fp32 on the transformed box.
+ * Candidates: one workgroup per class c in 0 .. C-2 (labels are 0-based) takes every live row of every set with label c and
+ *   score > min_score (strict: NaN, and with min_score = 0 non-positive scores, drop out), whatever the order of the rows.  A live row
+ *   whose label lies outside 0 .. C-2 is skipped, whatever its score (LABEL_RANGE).  More than 2048 candidates in a class: the class
+ *   comes out empty and *out_count = -1 (CLASS_OVERFLOW).
+ * Order: score descending (-0 counts as +0), then set index ascending, then row ascending.
+ * Suppression: greedy in that order with frcnn_nms_classed's IoU decision (> nms_threshold, strict; a NaN or zero-area box is never
+ *   suppressed and suppresses nothing).  With K = 1, no flip and voting off, a set that left frcnn_detect_postprocess with the same
+ *   nms_threshold comes back bit for bit.
+ * Box voting (vote_threshold >= 0; < 0 or NaN = off), Detectron's box_voting in its ID scoring mode: the voters of kept box i are i
+ *   itself, always, and every candidate j of the class, suppressed or not, with IoU(i, j) >= vote_threshold -- the quotient of the
+ *   suppression's fp32 expression.  Scores, labels and order are unchanged; coordinate x of box i becomes
+ *   float32(sum_j s_j x_j / sum_j s_j), the five sums in binary64 in this order: lane l of the box's wave adds the voters at sorted
+ *   positions p = l (mod 64) in ascending p onto +0.0, each term the exact product (double)s_j * (double)x_j (for the weight sum,
+ *   (double)s_j); the 64 partials are combined by an xor butterfly, offsets 32, 16, 8, 4, 2, 1 (every lane adds its partner's value to its
+ *   own); then one binary64 division and one rounding to fp32.  The box keeps its original bits when i is its only voter, when any of the
+ *   five sums is not finite, or when the weight sum is not > 0.  For vote_threshold > 0 a NaN or zero-area box is its own only voter.
+ * Emit: class-major concatenation, suppression order inside a class; *out_count = the kept total, out_class_counts[c] (optional) the
+ *   per-class counts, *out_status (optional) the bits above.  A kept total above out_capacity gives *out_count = -1 (OUTPUT_OVERFLOW);
+ *   nothing is written past out_capacity.  Rows at and above the count are left as they were.
+ * Limits: 1 <= K <= 8, 0 <= caps[k] <= 2^28, 2 <= C <= 256 (FRCNN_ERR_UNSUPPORTED otherwise for C and caps above 2^28;
+ * FRCNN_ERR_INVALID_ARG for NULL pointers, K, negative capacities, boxes or out_boxes not 16-byte aligned).
+ * workspace: frcnn_workspace_bytes(FRCNN_OP_DETECT_MERGE, out_capacity, C) bytes, any content. */
+int frcnn_detect_merge(int K, const float *const *boxes /*[caps[k],4] xyxy*/, const int32_t *const *labels /*[caps[k]]*/,
+                       const float *const *scores /*[caps[k]]*/, const int32_t *const *counts /*[1]*/, const int64_t *caps,
+                       const uint32_t *flags, int C, float min_score, float nms_threshold, float vote_threshold,
+                       float *out_boxes /*[out_capacity,4]*/, int32_t *out_labels /*[out_capacity]*/, float *out_scores /*[out_capacity]*/,
+                       int32_t *out_count /*[1]*/, int32_t *out_class_counts /*[C-1] or NULL*/, int32_t *out_status /*[1] or NULL*/,
+                       int64_t out_capacity, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- detection evaluator: the VOC AP protocol (evaluation/voc_eval.py:67-112,115-135,138-225) ------------------------ */
 /* Flags of a record: 2 bits per threshold t (bits 2t, 2t+1). */
