@@ -465,36 +465,79 @@ __global__ __launch_bounds__(64 * NW) void roi_pool_bwd_priv_kernel(const float 
     RP_T(1, 6);
 }
 
-template <typename AT>
-static int roi_pool_fwd_launch(const float *feat, int C, int H, int W, const float *rois, int64_t R, int PH, int PW, float spatial_scale,
-                               float *out, AT *argmax, hipStream_t s)
+// ------------------------------------------------------------------------------------------------
+// The host's choices: which kernel a shape takes and with what launch geometry.  The entry points below launch from these, and
+// frcnn_roi_pool_plan reports them: one copy of every rule.
+// ------------------------------------------------------------------------------------------------
+struct RoiFwdPlan { int form; int S, RB; int exclusive; int64_t lds; };      // form: FRCNN_ROI_FWD_* or -1 (the entry point refuses the shape)
+struct RoiBwdPlan { int form; int64_t lds; };                                // form: FRCNN_ROI_BWD_* or -1
+
+// R >= 1
+static RoiFwdPlan roi_pool_fwd_plan(int C, int H, int W, int64_t R, int PH, int PW, bool a16)
 {
+    RoiFwdPlan p = {FRCNN_ROI_FWD_GENERIC, 0, 0, 0, 0};
+    const bool lds_fits = PH == 7 && PW == 7 && (int64_t)4 * H * W * 4 <= 48 * 1024 && R < (1 << 24);
+    if (a16 && !((int64_t)H * W < 65535 && lds_fits)) { p.form = -1; return p; }                 // the 16-bit pair has no generic form
+    if (!lds_fits) return p;
+    p.form = FRCNN_ROI_FWD_LDS;
     const int ncg = (C + 3) / 4;
     int S = (ROI_FWD_WGS + ncg - 1) / ncg;                                   // RoI slices: ~one workgroup per CU ...
     S = (int)std::min<int64_t>(std::max<int64_t>(S, (R + ROI_FWD_RB_MAX - 1) / ROI_FWD_RB_MAX), R);   // ... of at most ROI_FWD_RB_MAX RoIs
     const int RB = (int)((R + S - 1) / S);
     S = (int)((R + RB - 1) / RB);
-    size_t shmem = (size_t)4 * H * W * 4 + (size_t)RB * (7 + 7) * 4;
+    p.S = S; p.RB = RB;
+    p.lds = (int64_t)4 * H * W * 4 + (int64_t)RB * (7 + 7) * 4;
 #if ROI_FWD_EXCLUSIVE
     // one workgroup per CU: two of these 1024-thread workgroups fit a CU, and the dispatcher does pair them up while other CUs stay empty (trace:
     // median workgroup done at 10.1 us, the last at 14.6); asking for more than half of the CU's LDS makes every workgroup take a CU of its own
-    if ((int64_t)ncg * S <= 256 && shmem < 84 * 1024) {
-        shmem = 84 * 1024;
-        if (hipFuncSetAttribute((const void *)roi_pool_fwd_lds_kernel<7, 7, AT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem) != hipSuccess)
-            return frcnn_set_error(FRCNN_ERR_LAUNCH, "roi_pool_fwd: cannot opt in to %zu bytes of LDS", shmem);
-    }
+    if ((int64_t)ncg * S <= 256 && p.lds < 84 * 1024) { p.lds = 84 * 1024; p.exclusive = 1; }
 #endif
-    FRCNN_LAUNCH((roi_pool_fwd_lds_kernel<7, 7, AT>), dim3(ncg, S), dim3(ROI_FWD_BS), shmem, s, feat, C, H, W, (const float4 *)rois, (int)R, RB,
+    return p;
+}
+
+static RoiBwdPlan roi_pool_bwd_plan(int C, int64_t HW, int PH, int PW, bool a16)
+{
+    RoiBwdPlan p = {-1, 0};
+    const bool shared_fits = HW * 4 * ROI_BWD_CB <= 64 * 1024;
+    if (a16) {
+        if (!(PH == 7 && PW == 7 && HW < 65535 && shared_fits)) return p;
+        // the 16-bit pair (7 x 7 bins): wave-private planes (bit-reproducible, non-atomic adds) wherever C is even, two planes stay below 32768
+        // pixels (16-bit keys) and at least four copies of the two planes fit the CU's 160 KB of LDS; the shared-plane form (LDS atomics, arrival order) otherwise
+        const int64_t copy_bytes = (((2 * HW + 3) & ~(int64_t)3) + 64) * 4;
+        if (getenv("FRCNN_ROI_BWD_SHARED") == nullptr && (C & 1) == 0 && 2 * HW < 0x8000) {
+            if (8 * copy_bytes <= 160 * 1024) { p.form = FRCNN_ROI_BWD_PRIVATE8; p.lds = 8 * copy_bytes; return p; }
+            if (4 * copy_bytes <= 160 * 1024) { p.form = FRCNN_ROI_BWD_PRIVATE4; p.lds = 4 * copy_bytes; return p; }
+        }
+        p.form = FRCNN_ROI_BWD_SHARED_CB; p.lds = HW * 4 * ROI_BWD_CB;
+        return p;
+    }
+    // the CB-channel LDS kernel maps a thread to (RoI slot, element of the CB * bins run): it needs at least one whole run per pass of
+    // its 512 threads; larger bin grids (e.g. 17 x 17) take the one-channel kernel, which strides over any run length
+    if (shared_fits && (int64_t)PH * PW * ROI_BWD_CB <= 512) { p.form = FRCNN_ROI_BWD_SHARED_CB; p.lds = HW * 4 * ROI_BWD_CB; }
+    else if (HW * 4 <= 64 * 1024) { p.form = FRCNN_ROI_BWD_ONE_CHANNEL; p.lds = HW * 4; }
+    else p.form = FRCNN_ROI_BWD_GLOBAL_ATOMIC;                               // memset + global fp32 atomics
+    return p;
+}
+
+template <typename AT>
+static int roi_pool_fwd_launch(const RoiFwdPlan &p, const float *feat, int C, int H, int W, const float *rois, int64_t R, float spatial_scale,
+                               float *out, AT *argmax, hipStream_t s)
+{
+    const int ncg = (C + 3) / 4;
+    const size_t shmem = (size_t)p.lds;
+    if (p.exclusive && hipFuncSetAttribute((const void *)roi_pool_fwd_lds_kernel<7, 7, AT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem) != hipSuccess)
+        return frcnn_set_error(FRCNN_ERR_LAUNCH, "roi_pool_fwd: cannot opt in to %zu bytes of LDS", shmem);
+    FRCNN_LAUNCH((roi_pool_fwd_lds_kernel<7, 7, AT>), dim3(ncg, p.S), dim3(ROI_FWD_BS), shmem, s, feat, C, H, W, (const float4 *)rois, (int)R, p.RB,
                  spatial_scale, out, argmax);
     FRCNN_CHECK_LAUNCH("roi_pool_fwd_lds_kernel");
     return FRCNN_OK;
 }
 
 template <int NW>
-static int roi_pool_bwd_priv_launch(const float *grad_out, const uint16_t *argmax, const float *rois, float scale, int64_t R, int C, int64_t HW,
-                                    int PH, int PW, float *grad_feat, hipStream_t s)
+static int roi_pool_bwd_priv_launch(const RoiBwdPlan &p, const float *grad_out, const uint16_t *argmax, const float *rois, float scale, int64_t R, int C,
+                                    int64_t HW, int PH, int PW, float *grad_feat, hipStream_t s)
 {
-    const size_t shmem = (size_t)NW * (((2 * HW + 3) & ~(int64_t)3) + 64) * 4;
+    const size_t shmem = (size_t)p.lds;
     auto kern = roi_pool_bwd_priv_kernel<NW>;
     if (shmem > 64 * 1024 && hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem) != hipSuccess)
         return frcnn_set_error(FRCNN_ERR_LAUNCH, "roi_pool_bwd: cannot opt in to %zu bytes of LDS", shmem);
@@ -504,22 +547,17 @@ static int roi_pool_bwd_priv_launch(const float *grad_out, const uint16_t *argma
     return FRCNN_OK;
 }
 
-// `rois` / `scale`: the boxes the forward pooled (NULL = not known)
+// `rois` / `scale`: the boxes the forward pooled (NULL = not known); p.form = one of the LDS forms
 template <typename AT>
-static int roi_pool_bwd_launch(const float *grad_out, const AT *argmax, const float *rois, float scale, int64_t R, int C, int64_t HW, int PH, int PW,
-                               float *grad_feat, hipStream_t s)
+static int roi_pool_bwd_launch(const RoiBwdPlan &p, const float *grad_out, const AT *argmax, const float *rois, float scale, int64_t R, int C, int64_t HW,
+                               int PH, int PW, float *grad_feat, hipStream_t s)
 {
     const int bins = PH * PW;
     if constexpr (sizeof(AT) == 2) {
-        // the 16-bit pair (7 x 7 bins): wave-private planes (bit-reproducible, non-atomic adds) wherever C is even, two planes stay below 32768
-        // pixels (16-bit keys) and at least four copies of the two planes fit the CU's 160 KB of LDS; the shared-plane form (LDS atomics, arrival order) otherwise
-        const int64_t copy_bytes = (((2 * HW + 3) & ~(int64_t)3) + 64) * 4;
-        if (getenv("FRCNN_ROI_BWD_SHARED") == nullptr && (C & 1) == 0 && PW == 7 && PH == 7 && 2 * HW < 0x8000) {
-            if (8 * copy_bytes <= 160 * 1024) return roi_pool_bwd_priv_launch<8>(grad_out, argmax, rois, scale, R, C, HW, PH, PW, grad_feat, s);
-            if (4 * copy_bytes <= 160 * 1024) return roi_pool_bwd_priv_launch<4>(grad_out, argmax, rois, scale, R, C, HW, PH, PW, grad_feat, s);
-        }
+        if (p.form == FRCNN_ROI_BWD_PRIVATE8) return roi_pool_bwd_priv_launch<8>(p, grad_out, argmax, rois, scale, R, C, HW, PH, PW, grad_feat, s);
+        if (p.form == FRCNN_ROI_BWD_PRIVATE4) return roi_pool_bwd_priv_launch<4>(p, grad_out, argmax, rois, scale, R, C, HW, PH, PW, grad_feat, s);
     }
-    FRCNN_LAUNCH((roi_pool_bwd_lds_kernel<ROI_BWD_CB, AT>), dim3((C + ROI_BWD_CB - 1) / ROI_BWD_CB), dim3(512), (size_t)HW * 4 * ROI_BWD_CB, s,
+    FRCNN_LAUNCH((roi_pool_bwd_lds_kernel<ROI_BWD_CB, AT>), dim3((C + ROI_BWD_CB - 1) / ROI_BWD_CB), dim3(512), (size_t)p.lds, s,
                  grad_out, argmax, (int)R, C, (int)HW, bins, grad_feat);
     FRCNN_CHECK_LAUNCH("roi_pool_bwd_lds_kernel");
     return FRCNN_OK;
@@ -532,9 +570,9 @@ FRCNN_EXPORT int frcnn_roi_pool_fwd_a16(const float *feat, int C, int H, int W, 
     FRCNN_REQUIRE(C > 0 && H > 0 && W > 0 && R >= 0, "roi_pool_fwd_a16: bad shape");
     if (R == 0) return FRCNN_OK;
     FRCNN_REQUIRE(feat && rois && out && argmax16, "roi_pool_fwd_a16: NULL pointer");
-    FRCNN_REQUIRE((int64_t)H * W < 65535 && (size_t)4 * H * W * 4 <= 48 * 1024 && R < (1 << 24),
-                  "roi_pool_fwd_a16: plane %dx%d does not fit the 16-bit argmax / LDS path (use frcnn_roi_pool_fwd)", H, W);
-    return roi_pool_fwd_launch<uint16_t>(feat, C, H, W, rois, R, 7, 7, spatial_scale, out, argmax16, (hipStream_t)stream);
+    const RoiFwdPlan p = roi_pool_fwd_plan(C, H, W, R, 7, 7, true);
+    FRCNN_REQUIRE(p.form == FRCNN_ROI_FWD_LDS, "roi_pool_fwd_a16: plane %dx%d does not fit the 16-bit argmax / LDS path (use frcnn_roi_pool_fwd)", H, W);
+    return roi_pool_fwd_launch<uint16_t>(p, feat, C, H, W, rois, R, spatial_scale, out, argmax16, (hipStream_t)stream);
 }
 
 FRCNN_EXPORT int frcnn_roi_pool_bwd_a16(const float *grad_out, const uint16_t *argmax16, const float *rois, float spatial_scale, int64_t R, int C,
@@ -544,14 +582,15 @@ FRCNN_EXPORT int frcnn_roi_pool_bwd_a16(const float *grad_out, const uint16_t *a
     FRCNN_REQUIRE(grad_feat, "roi_pool_bwd_a16: NULL grad_feat");
     hipStream_t s = (hipStream_t)stream;
     const int64_t HW = (int64_t)H * W;
-    FRCNN_REQUIRE(HW < 65535 && HW * 4 * ROI_BWD_CB <= 64 * 1024, "roi_pool_bwd_a16: plane does not fit the 16-bit argmax / LDS path");
+    const RoiBwdPlan p = roi_pool_bwd_plan(C, HW, 7, 7, true);
+    FRCNN_REQUIRE(p.form >= 0, "roi_pool_bwd_a16: plane does not fit the 16-bit argmax / LDS path");
     if (R == 0) {
         if (hipMemsetAsync(grad_feat, 0, (size_t)C * HW * 4, s) != hipSuccess) return frcnn_set_error(FRCNN_ERR_LAUNCH, "roi_pool_bwd_a16: memset failed");
         return FRCNN_OK;
     }
     FRCNN_REQUIRE(grad_out && argmax16, "roi_pool_bwd_a16: NULL pointer");
     FRCNN_REQUIRE(R * 49 < ((int64_t)1 << 31), "roi_pool_bwd_a16: R*bins too large");
-    return roi_pool_bwd_launch<uint16_t>(grad_out, argmax16, rois, spatial_scale, R, C, HW, 7, 7, grad_feat, s);
+    return roi_pool_bwd_launch<uint16_t>(p, grad_out, argmax16, rois, spatial_scale, R, C, HW, 7, 7, grad_feat, s);
 }
 
 FRCNN_EXPORT int frcnn_roi_pool_fwd(const float *feat, int C, int H, int W, const float *rois, int64_t R, int PH, int PW,
@@ -564,9 +603,9 @@ FRCNN_EXPORT int frcnn_roi_pool_fwd(const float *feat, int C, int H, int W, cons
     const int64_t total = R * C * PH * PW;
     FRCNN_REQUIRE(total < ((int64_t)1 << 38), "roi_pool_fwd: output too large");
     hipStream_t s = (hipStream_t)stream;
-    const size_t plane_bytes = (size_t)4 * H * W * 4;
-    if (PH == 7 && PW == 7 && plane_bytes <= 48 * 1024 && R < (1 << 24))
-        return roi_pool_fwd_launch<int32_t>(feat, C, H, W, rois, R, PH, PW, spatial_scale, out, argmax, s);
+    const RoiFwdPlan p = roi_pool_fwd_plan(C, H, W, R, PH, PW, false);
+    if (p.form == FRCNN_ROI_FWD_LDS)
+        return roi_pool_fwd_launch<int32_t>(p, feat, C, H, W, rois, R, spatial_scale, out, argmax, s);
     FRCNN_LAUNCH(roi_pool_fwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, feat, C, H, W,
                  (const float4 *)rois, total, PH, PW, spatial_scale, out, argmax);
     FRCNN_CHECK_LAUNCH("roi_pool_fwd_kernel");
@@ -586,12 +625,11 @@ FRCNN_EXPORT int frcnn_roi_pool_bwd(const float *grad_out, const int32_t *argmax
     }
     FRCNN_REQUIRE(grad_out && argmax, "roi_pool_bwd: NULL pointer");
     FRCNN_REQUIRE(R * PH * PW < ((int64_t)1 << 31), "roi_pool_bwd: R*bins too large");
-    // the CB-channel LDS kernel maps a thread to (RoI slot, element of the CB * bins run): it needs at least one whole run per pass of
-    // its 512 threads; larger bin grids (e.g. 17 x 17) take the one-channel kernel, which strides over any run length
-    if (HW * 4 * ROI_BWD_CB <= 64 * 1024 && (int64_t)PH * PW * ROI_BWD_CB <= 512) {
-        return roi_pool_bwd_launch<int32_t>(grad_out, argmax, nullptr, 0.0f, R, C, HW, PH, PW, grad_feat, s);
-    } else if (HW * 4 <= 64 * 1024) {
-        FRCNN_LAUNCH(roi_pool_bwd_kernel, dim3(C), dim3(256), (size_t)HW * 4, s, grad_out, argmax, (int)R, C, (int)HW,
+    const RoiBwdPlan p = roi_pool_bwd_plan(C, HW, PH, PW, false);
+    if (p.form == FRCNN_ROI_BWD_SHARED_CB) {
+        return roi_pool_bwd_launch<int32_t>(p, grad_out, argmax, nullptr, 0.0f, R, C, HW, PH, PW, grad_feat, s);
+    } else if (p.form == FRCNN_ROI_BWD_ONE_CHANNEL) {
+        FRCNN_LAUNCH(roi_pool_bwd_kernel, dim3(C), dim3(256), (size_t)p.lds, s, grad_out, argmax, (int)R, C, (int)HW,
                      PH * PW, grad_feat);
         FRCNN_CHECK_LAUNCH("roi_pool_bwd_kernel");
     } else {
@@ -601,5 +639,20 @@ FRCNN_EXPORT int frcnn_roi_pool_bwd(const float *grad_out, const int32_t *argmax
                      total, C, (int)HW, PH * PW, grad_feat);
         FRCNN_CHECK_LAUNCH("roi_pool_bwd_atomic_kernel");
     }
+    return FRCNN_OK;
+}
+
+FRCNN_EXPORT int frcnn_roi_pool_plan(int C, int H, int W, int64_t R, int PH, int PW, int argmax16, int have_rois, int *plan_host, int plan_len)
+{
+    FRCNN_REQUIRE(C > 0 && H > 0 && W > 0 && PH > 0 && PW > 0 && R >= 1, "roi_pool_plan: bad shape");
+    FRCNN_REQUIRE(plan_host, "roi_pool_plan: NULL pointer");
+    FRCNN_REQUIRE(plan_len >= FRCNN_ROI_PLAN_INTS, "roi_pool_plan: plan_len %d < %d", plan_len, FRCNN_ROI_PLAN_INTS);
+    FRCNN_REQUIRE(!argmax16 || (PH == 7 && PW == 7), "roi_pool_plan: the 16-bit pair pools 7 x 7 bins");
+    const RoiFwdPlan f = roi_pool_fwd_plan(C, H, W, R, PH, PW, argmax16 != 0);
+    const RoiBwdPlan b = roi_pool_bwd_plan(C, (int64_t)H * W, PH, PW, argmax16 != 0);
+    const bool priv = b.form == FRCNN_ROI_BWD_PRIVATE8 || b.form == FRCNN_ROI_BWD_PRIVATE4;
+    plan_host[0] = f.form; plan_host[1] = f.S; plan_host[2] = f.RB; plan_host[3] = f.exclusive; plan_host[4] = (int)f.lds;
+    plan_host[5] = b.form; plan_host[6] = (int)b.lds;
+    plan_host[7] = priv && have_rois ? 1 : 0;                                // RoIs of at least 7 x 7 cells add in rank order, without LDS atomics
     return FRCNN_OK;
 }

@@ -1860,6 +1860,26 @@ def roi_pool_with_argmax(features, rois, output_size=(7, 7), spatial_scale=1.0):
     return out, arg
 
 
+ROI_POOL_FWD_FORMS = ("lds", "generic")                                                      # FRCNN_ROI_FWD_*
+ROI_POOL_BWD_FORMS = ("private8", "private4", "shared_cb", "one_channel", "global_atomic")    # FRCNN_ROI_BWD_*
+
+
+def roi_pool_plan(C, H, W, R, output_size=(7, 7), argmax16=True, have_rois=True):
+    """What the RoIPool entry points execute for features [C, H, W] and R >= 1 RoIs (frcnn_roi_pool_plan: the host functions the launches use; no
+    device is touched, nothing is launched).  argmax16: the 16-bit pair (frcnn_roi_pool_fwd_a16 / _bwd_a16, 7 x 7 bins) instead of the int32
+    pair; have_rois: the 16-bit backward is given the boxes.  Returns a dict: fwd = one of ROI_POOL_FWD_FORMS, or None where the entry point
+    refuses the shape; S, RB, exclusive, fwd_lds (the LDS forward's RoI slices, RoIs per workgroup, whether it asks for 84 KB of LDS to have
+    a CU to itself, and its dynamic LDS bytes; 0 otherwise); bwd = one of ROI_POOL_BWD_FORMS or None; bwd_lds; rank_adds (RoIs of at least
+    7 x 7 cells add in rank order without LDS atomics).  FRCNN_ROI_BWD_SHARED in the environment is honoured as in the launch."""
+    PH, PW = (output_size, output_size) if isinstance(output_size, int) else output_size
+    out = np.zeros(8, dtype=np.int32)
+    check(lib.frcnn_roi_pool_plan(int(C), int(H), int(W), int(R), int(PH), int(PW), int(bool(argmax16)), int(bool(have_rois)), _np_ptr(out), out.size),
+          "roi_pool_plan")
+    v = [int(t) for t in out]
+    return {"fwd": ROI_POOL_FWD_FORMS[v[0]] if v[0] >= 0 else None, "S": v[1], "RB": v[2], "exclusive": bool(v[3]), "fwd_lds": v[4],
+            "bwd": ROI_POOL_BWD_FORMS[v[5]] if v[5] >= 0 else None, "bwd_lds": v[6], "rank_adds": bool(v[7])}
+
+
 def roi_pool(features, rois, output_size=(7, 7), spatial_scale=1.0):
     if isinstance(rois, (list, tuple)):
         if len(rois) != 1:

@@ -441,6 +441,23 @@ int frcnn_roi_pool_fwd_a16(const float *feat, int C, int H, int W, const float *
  * an odd C takes the shared-plane kernel, whose LDS atomics add in arrival order (last-bit differences between runs). */
 int frcnn_roi_pool_bwd_a16(const float *grad_out, const uint16_t *argmax16, const float *rois /*[R,4] or NULL*/, float spatial_scale,
                            int64_t R, int C, int H, int W, float *grad_feat, void *stream);
+/* What the four entry points above execute for a shape: the host functions the launches use; no device is touched, nothing is launched.
+ * argmax16: the 16-bit pair (PH = PW = 7) instead of the int32 pair; have_rois: frcnn_roi_pool_bwd_a16 is given the boxes.  R >= 1.
+ * plan_host receives FRCNN_ROI_PLAN_INTS ints (plan_len >= that):
+ *   [0] forward form (FRCNN_ROI_FWD_*; -1: the entry point refuses the shape)   [1] S = RoI slices (grid.y)   [2] RB = RoIs per workgroup
+ *   [3] 1 when the launch asks for 84 KB of LDS to have a CU to itself   [4] the forward's dynamic LDS bytes  ([1]..[4] are 0 for the generic form)
+ *   [5] backward form (FRCNN_ROI_BWD_*; -1: refused)   [6] the backward's dynamic LDS bytes
+ *   [7] 1 when RoIs of at least 7 x 7 cells add in rank order without LDS atomics (a wave-private form that is given the boxes)
+ * The environment variable FRCNN_ROI_BWD_SHARED (any value) makes the 16-bit backward take the shared-plane form, here as in the launch. */
+#define FRCNN_ROI_FWD_LDS 0                /* planes staged in LDS, dynamic task queue: 7 x 7 bins, 16 * H * W <= 48 KB */
+#define FRCNN_ROI_FWD_GENERIC 1            /* one lane per output element */
+#define FRCNN_ROI_BWD_PRIVATE8 0           /* wave-private planes, 8 copies: 16-bit argmax, even C */
+#define FRCNN_ROI_BWD_PRIVATE4 1           /* ... 4 copies */
+#define FRCNN_ROI_BWD_SHARED_CB 2           /* two channels per workgroup, one plane each, LDS atomics */
+#define FRCNN_ROI_BWD_ONE_CHANNEL 3        /* one channel per workgroup, any bin grid */
+#define FRCNN_ROI_BWD_GLOBAL_ATOMIC 4      /* memset + global fp32 atomics */
+#define FRCNN_ROI_PLAN_INTS 8
+int frcnn_roi_pool_plan(int C, int H, int W, int64_t R, int PH, int PW, int argmax16, int have_rois, int *plan_host, int plan_len);
 
 /* torchvision.ops.MultiScaleRoIAlign(names, PH, sampling_ratio) (models/new_model.py:127,143): level mapper
  * k = floor(k0 + log2(sqrt(area)/s0) + 1e-6) clamped to [k_min, k_min+n_levels-1]; per level roi_align
