@@ -13,6 +13,15 @@
 // Kernel 2 (topk_scatter_kernel): sums the per-segment partial ranks and scatters index, score and
 //   (optionally) the box to position rank(i) if rank(i) < K: the gather at model.py:48 is fused.
 // Work: N^2 pair compares -- used for N < 4096 only; larger N take the sample sort further down.
+//
+// Order contract (docs/PARITY.md, "top-k order contract"; tests/topk_ref.py is its reference):
+//   * the key is the score's BIT pattern under f2key (topk_dev.h), a total order: ... < -0.0 < +0.0 < denormals < ... < +inf, a NaN with
+//     the sign bit clear above +inf, one with it set below -inf; equal keys in ascending index order.  The reference's torch.sort is
+//     unstable and compares -0.0 == +0.0, and the CPU oracle's float compare is no order on NaNs: at these points it is unpinned or differs;
+//   * frcnn_argsort_desc (every entry live) sorts all N entries by that order, NaNs included;
+//   * frcnn_topk_sorted (proposal mode) sorts the LIVE entries, score >= 0: -0.0 and denormals are live, negatives and every NaN are not.
+//     Every key of that mode is built from ss_live_score(): what is not live carries the key of -1 and ranks behind all that is, so
+//     count = min(K, n_live) and out_idx / out_scores / out_boxes [0, count) are all written, whatever bits the dead scores have.
 #include "frcnn_common.h"
 #include "frcnn_dev.h"
 #include "frcnn_internal.h"
@@ -24,8 +33,8 @@ FRCNN_LAYOUT_STAMP(topk);
 #define TOPK_ROWS 256
 #define TOPK_SEG 1024
 
-__global__ __launch_bounds__(TOPK_ROWS) void topk_rank_kernel(const float *__restrict__ scores, int N, int32_t *__restrict__ partial,
-                                                              int32_t *__restrict__ count_zero)
+__global__ __launch_bounds__(TOPK_ROWS) void topk_rank_kernel(const float *__restrict__ scores, int N, int proposal_mode,
+                                                              int32_t *__restrict__ partial, int32_t *__restrict__ count_zero)
 {
     __shared__ uint4 seg4[TOPK_SEG / 4];
     uint32_t *seg = (uint32_t *)seg4;
@@ -36,10 +45,10 @@ __global__ __launch_bounds__(TOPK_ROWS) void topk_rank_kernel(const float *__res
 #pragma unroll
     for (int t = tid; t < TOPK_SEG; t += TOPK_ROWS) {
         const int j = c0 + t;
-        seg[t] = j < N ? f2key(scores[j]) : 0u;       // tail keys are never "greater"
+        seg[t] = j < N ? f2key(ss_live_score(scores[j], proposal_mode)) : 0u;       // tail keys are never "greater"
     }
     const int i = r0 + tid;
-    const uint32_t ki = i < N ? f2key(scores[i]) : 0xFFFFFFFFu;
+    const uint32_t ki = i < N ? f2key(ss_live_score(scores[i], proposal_mode)) : 0xFFFFFFFFu;
     __syncthreads();
     const int wb = r0 + (tid & ~63);                  // first row of this wave
     int rank = 0;
@@ -128,11 +137,11 @@ typedef unsigned long long u64;
 // the splitter sampling as a launch of its own (the generic top-k / argsort entry points; the proposal stage runs ss_sample_body
 // inside its prologue launch, see topk_dev.h and boxes.hip)
 template <int S>
-__global__ __launch_bounds__(256) void topk_sample_kernel(const float *__restrict__ scores, int N, int stride, SsCtl *__restrict__ ctl)
+__global__ __launch_bounds__(256) void topk_sample_kernel(const float *__restrict__ scores, int N, int stride, int proposal_mode, SsCtl *__restrict__ ctl)
 {
     __shared__ uint4 s_k4[S / 4];
     __shared__ int s_part[4][64];
-    ss_sample_body<S>([&](int i) { return scores[i]; }, N, stride, ctl, (int)blockIdx.x, s_k4, s_part);
+    ss_sample_body<S>([&](int i) { return ss_live_score(scores[i], proposal_mode); }, N, stride, ctl, (int)blockIdx.x, s_k4, s_part);
 }
 
 // number of splitters 1..255 that are > k  =  the bucket of k
@@ -158,7 +167,7 @@ __global__ __launch_bounds__(256) void topk_count_kernel(const float *__restrict
     for (int i = blockIdx.x * 256 + threadIdx.x; i < N; i += gridDim.x * 256) {
         const float sc = scores[i];
         valid += (!proposal_mode || sc >= 0.0f) ? 1 : 0;
-        atomicAdd(&s_cnt[ss_bucket(s_split, ss_key(sc, i))], 1);
+        atomicAdd(&s_cnt[ss_bucket(s_split, ss_key(ss_live_score(sc, proposal_mode), i))], 1);
     }
     valid = wave_sum_xor(valid);
     if ((threadIdx.x & 63) == 0 && valid) atomicAdd(&s_valid, valid);
@@ -183,7 +192,8 @@ __device__ __forceinline__ int ss_scan256(int v, int *s_w /*[4]*/)
 // Buckets become contiguous segments of `sorted`.  A block first counts its own 1024 keys per bucket in LDS (the returned value
 // is the key's slot inside the block's share), reserves the block's share of every non-empty bucket with ONE global atomic per
 // bucket, then writes: N / 1024 * (<= 256) global atomics instead of N on 256 hot words.
-__global__ __launch_bounds__(256) void topk_place_kernel(const float *__restrict__ scores, int N, SsCtl *__restrict__ ctl, u64 *__restrict__ sorted)
+__global__ __launch_bounds__(256) void topk_place_kernel(const float *__restrict__ scores, int N, int proposal_mode, SsCtl *__restrict__ ctl,
+                                                       u64 *__restrict__ sorted)
 {
     __shared__ u64 s_split[SS_BUCKETS];
     __shared__ int s_base[SS_BUCKETS], s_cnt[SS_BUCKETS];
@@ -199,7 +209,7 @@ __global__ __launch_bounds__(256) void topk_place_kernel(const float *__restrict
         const int i = (blockIdx.x * SS_PER_THREAD + e) * 256 + threadIdx.x;
         bk[e] = -1;
         if (i < N) {
-            k[e] = ss_key(scores[i], i);
+            k[e] = ss_key(ss_live_score(scores[i], proposal_mode), i);
             bk[e] = ss_bucket(s_split, k[e]);
             slot[e] = atomicAdd(&s_cnt[bk[e]], 1);
         }
@@ -271,7 +281,7 @@ __global__ __launch_bounds__(256) void topk_partition_kernel(const float *__rest
         if (i < N) {
             const float sc = scores[i];
             valid += (!proposal_mode || sc >= 0.0f) ? 1 : 0;
-            k[e] = ss_key(sc, i);
+            k[e] = ss_key(ss_live_score(sc, proposal_mode), i);
             bk[e] = ss_bucket(s_split, k[e]);
             slot[e] = atomicAdd(&s_cnt[bk[e]], 1);
         }
@@ -444,8 +454,8 @@ int frcnn_launch_topk(const float *scores, const float *boxes_in, int64_t N, int
         if (!sampled) {                                                         // (the proposal prologue has done it otherwise)
             int S, stride;
             ss_plan(N, K, &S, &stride);
-            if (S == 512) FRCNN_LAUNCH(topk_sample_kernel<512>, dim3(512 / 64), dim3(256), 0, s, scores, (int)N, stride, ctl);
-            else FRCNN_LAUNCH(topk_sample_kernel<SS_LARGE>, dim3(SS_LARGE / 64), dim3(256), 0, s, scores, (int)N, stride, ctl);
+            if (S == 512) FRCNN_LAUNCH(topk_sample_kernel<512>, dim3(512 / 64), dim3(256), 0, s, scores, (int)N, stride, proposal_mode, ctl);
+            else FRCNN_LAUNCH(topk_sample_kernel<SS_LARGE>, dim3(SS_LARGE / 64), dim3(256), 0, s, scores, (int)N, stride, proposal_mode, ctl);
             FRCNN_CHECK_LAUNCH("topk_sample_kernel");
         }
         // FRCNN_TOPK_FUSED: 2 = count + place + bucket ranking as ONE launch (two grid barriers), 1 = count + place fused and the ranking
@@ -468,7 +478,7 @@ int frcnn_launch_topk(const float *scores, const float *boxes_in, int64_t N, int
         } else {
             FRCNN_LAUNCH(topk_count_kernel, dim3(gb < 1024 ? gb : 1024), dim3(256), 0, s, scores, (int)N, proposal_mode, ctl);
             FRCNN_CHECK_LAUNCH("topk_count_kernel");
-            FRCNN_LAUNCH(topk_place_kernel, dim3(gb), dim3(256), 0, s, scores, (int)N, ctl, sorted);
+            FRCNN_LAUNCH(topk_place_kernel, dim3(gb), dim3(256), 0, s, scores, (int)N, proposal_mode, ctl, sorted);
             FRCNN_CHECK_LAUNCH("topk_place_kernel");
         }
         FRCNN_LAUNCH(topk_bucket_kernel, dim3(SS_BUCKETS, N < 65536 ? 4 : 8), dim3(256), 0, s, scores, (const float4 *)boxes_in, (int)N, (int)K, ctl,
@@ -479,7 +489,7 @@ int frcnn_launch_topk(const float *scores, const float *boxes_in, int64_t N, int
     const int nseg = (int)((N + TOPK_SEG - 1) / TOPK_SEG);
     const int nrow = (int)((N + TOPK_ROWS - 1) / TOPK_ROWS);
     int32_t *partial = (int32_t *)ws;
-    FRCNN_LAUNCH(topk_rank_kernel, dim3(nrow, nseg), dim3(TOPK_ROWS), 0, s, scores, (int)N, partial, out_count);
+    FRCNN_LAUNCH(topk_rank_kernel, dim3(nrow, nseg), dim3(TOPK_ROWS), 0, s, scores, (int)N, proposal_mode, partial, out_count);
     FRCNN_CHECK_LAUNCH("topk_rank_kernel");
     FRCNN_LAUNCH(topk_scatter_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, scores,
                  (const float4 *)boxes_in, partial, (int)N, nseg, (int)K, proposal_mode, out_idx, out_scores, (float4 *)out_boxes,

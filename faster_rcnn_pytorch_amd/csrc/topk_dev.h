@@ -32,6 +32,11 @@ __device__ __forceinline__ uint32_t f2key(float f)
     return b ^ ((uint32_t)((int32_t)b >> 31) | 0x80000000u);
 }
 __device__ __forceinline__ ss_u64 ss_key(float sc, int idx) { return ((ss_u64)f2key(sc) << 32) | (ss_u64)(uint32_t)(~idx); }
+// Proposal mode sorts the LIVE scores (sc >= 0) only.  A score that is not live -- a negative one, or a NaN of either sign -- gets the key
+// of -1, the value the proposal prologue writes for a filtered anchor: below every live key (the lowest, -0.0, maps to 0x7FFFFFFF), so
+// whatever is not live ranks behind everything that is, in index order, and no NaN bit pattern can out-rank a live score (sign clear:
+// the largest keys of the bit order).  The pipeline's own scores are >= 0 or exactly -1: their keys are what they always were.
+__device__ __forceinline__ float ss_live_score(float sc, int proposal_mode) { return (proposal_mode && !(sc >= 0.0f)) ? -1.0f : sc; }
 
 // samples per sort and splitter stride: 512 samples for the sizes of one feature map, SS_LARGE above; the stride covers ranks up to
 // ~1.5 K (at least), the whole distribution at most

@@ -111,14 +111,19 @@ int frcnn_proposal_prologue(const float *reg /*[N,4]*/, const float *cls /*[N,2]
                             void *stream);
 
 /* Stage 2: scores.sort(descending=True)[:K] (model.py:44-49).  Ties are ordered by ascending index
- * (torch's sort is unstable).  Entries with score < 0 never appear.
- * out_count = min(K, #valid).  boxes_in/out_boxes may both be NULL (no gather).                    */
+ * (torch's sort is unstable).  Only LIVE entries, score >= 0, are sorted: -0.0 and denormals are live,
+ * negatives and NaNs of either sign are not and never appear.  out_count = min(K, #live), and exactly the first
+ * out_count entries of the outputs are written.  The order is the total order on the score's bit pattern: every
+ * +0.0 comes before any -0.0 (torch compares them equal: unpinned there).
+ * boxes_in/out_boxes may both be NULL (no gather).                                                 */
 int frcnn_topk_sorted(const float *scores /*[N]*/, const float *boxes_in /*[N,4] or NULL*/, int64_t N, int64_t K,
                       int64_t *out_idx /*[K]*/, float *out_scores /*[K]*/, float *out_boxes /*[K,4] or NULL*/,
                       int32_t *out_count, void *workspace, size_t workspace_bytes, void *stream);
 
 /* Full descending argsort (every score live, negatives included): the sort inside torchvision.ops.nms
- * when the caller's boxes are not pre-sorted (per-class NMS, models/model.py:394).  Ties: ascending index. */
+ * when the caller's boxes are not pre-sorted (per-class NMS, models/model.py:394).  Ties: ascending index.
+ * Total order on the bit pattern: -0.0 < +0.0; a NaN with the sign bit clear sorts in front of +inf (larger
+ * payload first), one with the sign bit set behind -inf (torch.sort puts every NaN first).                */
 int frcnn_argsort_desc(const float *scores /*[N]*/, const float *boxes_in /*[N,4] or NULL*/, int64_t N,
                        int64_t *out_idx /*[N]*/, float *out_scores /*[N]*/, float *out_boxes /*[N,4] or NULL*/,
                        int32_t *out_count, void *workspace, size_t workspace_bytes, void *stream);
