@@ -23,6 +23,7 @@ OP_COCO_EVAL_POOLED = 15
 OP_DETECT_MERGE = 16
 MERGE_COUNT_CLIPPED, MERGE_UPSTREAM_ABORT, MERGE_LABEL_RANGE, MERGE_CLASS_OVERFLOW, MERGE_OUTPUT_OVERFLOW = 1, 2, 4, 8, 16   # frcnn_detect_merge's status bits
 MERGE_MAX_SETS, MERGE_MAX_CANDIDATES = 8, 2048
+SOFT_NMS_HARD, SOFT_NMS_LINEAR, SOFT_NMS_GAUSSIAN = 0, 1, 2  # frcnn_detect_merge_soft's method
 EVAL_TP, EVAL_FP, EVAL_IGNORED = 1, 2, 3                     # a record's flags: 2 bits per threshold
 EVAL_ERR_UPSTREAM_ABORT, EVAL_ERR_GT_OVERFLOW, EVAL_ERR_COUNT_RANGE, EVAL_ERR_LABEL_RANGE = 1, 2, 4, 8
 EVAL_ERR_LEDGER_OVERFLOW = 16
@@ -100,6 +101,7 @@ SIGNATURES = {
     "frcnn_detection_loss": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "frcnn_detect_postprocess": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _f, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "frcnn_detect_merge": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _sz, _vp]),
+    "frcnn_detect_merge_soft": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _f, _f, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _sz, _vp]),
     "frcnn_eval_update": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
                                 _vp, _sz, _vp]),
     "frcnn_eval_average_precision": (_i, [_vp, _vp, _vp, _i64, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -22,7 +22,7 @@ int frcnn_set_error(int code, const char *fmt, ...)
 }
 
 // ---- layout stamps (frcnn_layout.h): every object of the library registers the stamp it was compiled with ----
-#define FRCNN_N_OBJECTS 29             // the twenty-eight .hip objects + api.o (csrc/Makefile: SRCS_HIP)
+#define FRCNN_N_OBJECTS 30             // the twenty-nine .hip objects + api.o (csrc/Makefile: SRCS_HIP)
 struct LayoutReg { const char *object; uint64_t stamp; };
 static std::vector<LayoutReg> &layout_registry() { static std::vector<LayoutReg> r; return r; }     // function-local: static initialisers of other objects may run first
 void frcnn_layout_register(const char *object, uint64_t stamp) { layout_registry().push_back({object, stamp}); }
@@ -49,7 +49,7 @@ FRCNN_EXPORT uint64_t frcnn_layout_stamp(void) { return frcnn_layout_stamp_value
 FRCNN_EXPORT int frcnn_abi_version(void) { const int rc = frcnn_layout_check_impl(); return rc ? rc : FRCNN_ABI_VERSION; }
 FRCNN_EXPORT const char *frcnn_last_error(void) { return g_err; }
 
-// ---- workspace layout sizes (must agree with the carving in topk.hip / nms.hip / targets.hip / detect.hip / eval.hip / coco_eval.hip / coco_eval_pooled.hip / eval_merge.hip / detect_merge.hip) ----
+// ---- workspace layout sizes (must agree with the carving in topk.hip / nms.hip / targets.hip / detect.hip / eval.hip / coco_eval.hip / coco_eval_pooled.hip / eval_merge.hip / detect_merge.hip, which detect_soft.hip shares) ----
 size_t frcnn_ws_topk(int64_t N);
 size_t frcnn_ws_nms(int64_t K);
 size_t frcnn_ws_rpn_targets(int64_t N, int64_t G);

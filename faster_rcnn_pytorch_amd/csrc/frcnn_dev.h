@@ -141,6 +141,25 @@ template <typename Op> __device__ __forceinline__ float wave_reduce_dpp(float v,
 #undef FRCNN_DPP_STEP
     return v;
 }
+// the 64-bit maximum by the same chain, both halves moved together: lane 63 ends with the wave's result; a lane without a source combines with 0
+__device__ __forceinline__ unsigned long long wave_max_dpp(unsigned long long k)
+{
+#define FRCNN_DPP_STEP64(ctrl, rmask)                                                                                              \
+    do {                                                                                                                           \
+        const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)k, ctrl, rmask, 0xf, false);                   \
+        const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(k >> 32), ctrl, rmask, 0xf, false);           \
+        const unsigned long long other = ((unsigned long long)hi << 32) | lo;                                                      \
+        k = other > k ? other : k;                                                                                                 \
+    } while (0)
+    FRCNN_DPP_STEP64(0x111, 0xf);  // row_shr:1
+    FRCNN_DPP_STEP64(0x112, 0xf);  // row_shr:2
+    FRCNN_DPP_STEP64(0x114, 0xf);  // row_shr:4
+    FRCNN_DPP_STEP64(0x118, 0xf);  // row_shr:8   -> lane 15 of every row holds the row's result
+    FRCNN_DPP_STEP64(0x142, 0xa);  // row_bcast:15 into rows 1 and 3
+    FRCNN_DPP_STEP64(0x143, 0xc);  // row_bcast:31 into rows 2 and 3 -> lane 63 holds the wave's result
+#undef FRCNN_DPP_STEP64
+    return k;
+}
 __device__ __forceinline__ float wave_lane63(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63)); }
 __device__ __forceinline__ float wave_sum_dpp(float v) { return wave_reduce_dpp(v, 0.0f, [](float a, float b) { return a + b; }); }
 __device__ __forceinline__ float wave_max_dpp(float v) { return wave_reduce_dpp(v, -__builtin_inff(), [](float a, float b) { return fmaxf(a, b); }); }

@@ -15,6 +15,9 @@
 //     sgd.hip's kernels;
 //   * frcnn_tensor_stats_row / _state and frcnn_journal_totals / _state (include/frcnn_hip.h): written by telemetry.hip, read by the caller
 //     (telemetry.py) by offset;
+//   * DmArgs / DmWs + the DM_* limits (detect_merge_dev.h): the merge's kernel-argument rows and workspace carving, FILLED by dm_prepare in
+//     detect_merge.hip and read by the class kernels of detect_merge.hip and detect_soft.hip, whose rows the emit kernel of detect_merge.hip
+//     then reads back from the workspace;
 //   * the profiling table size and the ABI version.
 // Every object registers its stamp in a static initialiser; frcnn_layout_check() (api.cpp; also run by frcnn_abi_version()) compares
 // them all with api.cpp's own and names the object that disagrees -- the library then refuses to load (FRCNN_ERR_UNSUPPORTED) instead of
@@ -27,6 +30,7 @@
 #include "topk_dev.h"
 #include "sgd_dev.h"
 #include "ema_dev.h"
+#include "detect_merge_dev.h"
 
 constexpr uint64_t frcnn_lay_mix(uint64_t h, uint64_t v) { return (h ^ v) * 0x100000001b3ull; }
 
@@ -70,6 +74,8 @@ constexpr uint64_t frcnn_layout_stamp_value()
     LAY(offsetof(frcnn_tensor_stats_state, measured_tick)); LAY(offsetof(frcnn_tensor_stats_state, measures));
     LAY(offsetof(frcnn_tensor_stats_state, first_nonfinite_g)); LAY(offsetof(frcnn_tensor_stats_state, first_nonfinite_p));
     LAY(FRCNN_TENSOR_STATS_FINISH_THREADS); LAY(sizeof(frcnn_journal_totals)); LAY(sizeof(frcnn_journal_state)); LAY(FRCNN_JOURNAL_MAX_COLS);
+    LAY(sizeof(DmArgs)); LAY(offsetof(DmArgs, labels)); LAY(offsetof(DmArgs, scores)); LAY(offsetof(DmArgs, counts)); LAY(offsetof(DmArgs, caps));
+    LAY(offsetof(DmArgs, flags)); LAY(offsetof(DmArgs, K)); LAY(sizeof(DmWs)); LAY(DM_MAX_K); LAY(DM_MAX_CAND); LAY(DM_THREADS); LAY(DM_ROW_BITS);
 #ifdef FRCNN_LAYOUT_TEST_SKEW          // tests/test_cabi.py builds ONE object with this defined and expects the library to refuse to load
     LAY(FRCNN_LAYOUT_TEST_SKEW);
 #endif

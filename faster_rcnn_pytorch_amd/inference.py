@@ -20,9 +20,12 @@ class DetectGraph(object):
 
     proposal_evaluator= (an evaluation.ProposalEvaluator, or any CocoDetectionEvaluator(use_cats=False), with gt= an
     evaluation.CocoGroundTruth) also scores the frame's proposals -- the same forward's RoIs, model.detect(..., want_proposals=True) -- in
-    the same graph, with or without evaluator=.  self.proposals is then the graph's static proposal Detections."""
+    the same graph, with or without evaluator=.  self.proposals is then the graph's static proposal Detections.
 
-    def __init__(self, model, image_hw, threshold=0.05, device=None, warmup=2, evaluator=None, gt=None, proposal_evaluator=None):
+    soft_nms= (an ops.SoftNMS) is handed to model.detect: the captured suppression is Soft-NMS and the static result an
+    ops.MergedDetections; the evaluators take it unchanged."""
+
+    def __init__(self, model, image_hw, threshold=0.05, device=None, warmup=2, evaluator=None, gt=None, proposal_evaluator=None, soft_nms=None):
         m = getattr(model, "module", model)                     # a DDP-wrapped model: capture the module itself
         dev = torch.device(device) if device is not None else next(m.parameters()).device
         H, W = (int(v) for v in image_hw)
@@ -34,9 +37,10 @@ class DetectGraph(object):
         want = proposal_evaluator is not None
 
         def detect():
+            kw = {} if soft_nms is None else {"soft_nms": soft_nms}
             if not want:
-                return m.detect(self.x, float(threshold), threshold_dev=self.threshold), None
-            return m.detect(self.x, float(threshold), threshold_dev=self.threshold, want_proposals=True)
+                return m.detect(self.x, float(threshold), threshold_dev=self.threshold, **kw), None
+            return m.detect(self.x, float(threshold), threshold_dev=self.threshold, want_proposals=True, **kw)
         self.image_hw = (H, W)
         self.x = torch.zeros((1, 3, H, W), dtype=torch.float32, device=dev)
         self.threshold = torch.full((1,), float(threshold), dtype=torch.float32, device=dev)
@@ -79,10 +83,11 @@ class TTADetectGraph(object):
 
     __call__(xs) takes one frame per size (a single tensor when there is one size), copies each into its static buffer, replays, and
     returns the graph's static ops.MergedDetections: overwritten by the next call.  set_threshold() works as in DetectGraph: the views'
-    score threshold is a device tensor read at replay time."""
+    score threshold is a device tensor read at replay time.  soft_nms= (an ops.SoftNMS) is handed to model.detect_tta: the views
+    contribute their unsuppressed candidates and the merge's Soft-NMS scan is the only suppression."""
 
     def __init__(self, model, view_hws, hflip=True, threshold=0.05, nms_threshold=0.3, vote_threshold=None, evaluator=None, gt=None, device=None,
-                 warmup=2):
+                 warmup=2, soft_nms=None):
         m = getattr(model, "module", model)                     # a DDP-wrapped model: capture the module itself
         dev = torch.device(device) if device is not None else next(m.parameters()).device
         view_hws = list(view_hws)
@@ -103,7 +108,8 @@ class TTADetectGraph(object):
                 views.append((x, False))
                 if self.hflip:
                     views.append((x.flip(-1), True))
-            return m.detect_tta(views, float(threshold), threshold_dev=self.threshold, nms_threshold=nms_threshold, vote_threshold=vote_threshold)
+            kw = {} if soft_nms is None else {"soft_nms": soft_nms}
+            return m.detect_tta(views, float(threshold), threshold_dev=self.threshold, nms_threshold=nms_threshold, vote_threshold=vote_threshold, **kw)
         # eager warm-up on a side stream, as DetectGraph: lazy allocations, cached constants and anchor grids, workspaces
         side = torch.cuda.Stream(dev)
         side.wait_stream(torch.cuda.current_stream(dev))

@@ -325,32 +325,59 @@ class _Detector(nn.Module):
         return self._proposal_detections(rois, n_rois)
 
     @torch.no_grad()
-    def detect(self, x, opts_or_threshold, threshold_dev=None, want_prob=False, want_proposals=False):
+    def detect(self, x, opts_or_threshold, threshold_dev=None, want_prob=False, want_proposals=False, soft_nms=None):
         """predict without a host sync (graph-capturable): the test-mode path with the fixed-capacity proposals and their device count,
         the head on all P rows, and the post-processing of models/model.py:368-402 / models/new_model.py:420-470 in
         ops.detect_postprocess.  threshold_dev (a device float32[1]) overrides the threshold when given.  Returns ops.Detections (its
         n_rois is the proposal count); .to_host() gives what predict returns.  want_proposals=True returns (detections, proposals), the
-        second as proposals(x) gives them: one forward serves both evaluators."""
+        second as proposals(x) gives them: one forward serves both evaluators.
+        soft_nms (an ops.SoftNMS; None = the above, unchanged): the per-class suppression becomes Soft-NMS at the same 0.3.  The
+        post-process runs with nms_threshold = +inf -- nothing exceeds it, so every thresholded candidate comes out, class-major and in
+        score order -- and ops.merge_detections of that one set does the suppression; the result is an ops.MergedDetections (decayed
+        scores, a status word) that carries prob and n_rois through."""
         threshold = float(getattr(opts_or_threshold, "thres", opts_or_threshold))
         features, rois, n_rois = self._test_proposals(x)
         head_cls, head_reg = self._head(features, rois, x)                        # rows >= n_rois: zero boxes, ignored below
-        dets = ops.detect_postprocess(head_cls, head_reg, rois, n_rois, threshold, 0.3, threshold_dev=threshold_dev, want_prob=want_prob)
+        if soft_nms is None:
+            dets = ops.detect_postprocess(head_cls, head_reg, rois, n_rois, threshold, 0.3, threshold_dev=threshold_dev, want_prob=want_prob)
+        else:
+            dets = self._soft_suppress(self._candidates(head_cls, head_reg, rois, n_rois, threshold, threshold_dev, want_prob), soft_nms)
         return (dets, self._proposal_detections(rois, n_rois)) if want_proposals else dets
 
+    @staticmethod
+    def _candidates(head_cls, head_reg, rois, n_rois, threshold, threshold_dev, want_prob=False):
+        """Every thresholded candidate of the head outputs, unsuppressed: the post-process at nms_threshold = +inf."""
+        return ops.detect_postprocess(head_cls, head_reg, rois, n_rois, threshold, float("inf"), threshold_dev=threshold_dev, want_prob=want_prob)
+
+    def _soft_suppress(self, cands, soft_nms):
+        out = ops.merge_detections([cands], num_classes=self.num_classes, min_score=float("-inf"), nms_threshold=0.3, soft_nms=soft_nms)
+        return ops.MergedDetections(out.boxes, out.labels, out.scores, out.count, out.class_counts, cands.prob, cands.n_rois, out.status)
+
     @torch.no_grad()
-    def detect_tta(self, views, threshold, threshold_dev=None, nms_threshold=0.3, vote_threshold=None):
+    def detect_tta(self, views, threshold, threshold_dev=None, nms_threshold=0.3, vote_threshold=None, soft_nms=None):
         """Test-time augmentation without a host sync (graph-capturable): detect on every view, one after the other on the current
         stream, then ops.merge_detections.  views: one tensor x, which stands for the two views x and x.flip(-1), or a list of
         (x_k, mirrored) pairs of any input size each -- mirrored=True says x_k is the frame flipped horizontally, so its boxes are
         mirrored back; normalised boxes need nothing else across scales.  The merge takes every detection of the views (their scores
         passed `threshold` already), suppresses per class at nms_threshold and, with vote_threshold, replaces every kept box by the
-        score-weighted mean of the candidates that overlap it that much.  Returns ops.MergedDetections."""
+        score-weighted mean of the candidates that overlap it that much.  Returns ops.MergedDetections.
+        soft_nms (an ops.SoftNMS; None = the above, unchanged): every view contributes its UNSUPPRESSED thresholded candidates and the
+        merge's Soft-NMS scan (decay threshold nms_threshold) is the only suppression -- Detectron's order of operations.  This raises
+        the per-class candidate count to as many as K views x P RoIs against the merge's limit of 2048 per class; a class above it
+        comes out empty with count = -1 and MERGE_CLASS_OVERFLOW in the status word, as ever."""
         if isinstance(views, torch.Tensor):
             views = [(views, False), (views.flip(-1), True)]
         views = list(views)
-        sets = [self.detect(x, threshold, threshold_dev=threshold_dev) for x, _ in views]
+        if soft_nms is None:
+            sets = [self.detect(x, threshold, threshold_dev=threshold_dev) for x, _ in views]
+        else:
+            sets = []
+            for x, _ in views:
+                features, rois, n_rois = self._test_proposals(x)
+                head_cls, head_reg = self._head(features, rois, x)
+                sets.append(self._candidates(head_cls, head_reg, rois, n_rois, float(getattr(threshold, "thres", threshold)), threshold_dev))
         return ops.merge_detections(sets, hflip=[bool(f) for _, f in views], num_classes=self.num_classes, min_score=float("-inf"),
-                                    nms_threshold=nms_threshold, vote_threshold=vote_threshold)
+                                    nms_threshold=nms_threshold, vote_threshold=vote_threshold, soft_nms=soft_nms)
 
     def _suppress(self, raw_cls_bbox, raw_prob, threshold):
         """models/model.py:382-402 (per-class score mask + nms(0.3), class 0 = background skipped, results concatenated

@@ -403,14 +403,41 @@ def describe_merge_status(bits):
     return [n for b, n in names if bits & b]
 
 
-def merge_detections(sets, hflip=None, vflip=None, num_classes=None, min_score=0.0, nms_threshold=0.3, vote_threshold=None, capacity=None):
+class SoftNMS(collections.namedtuple("SoftNMS", "method sigma score_floor")):
+    """Soft-NMS (Bodla et al., 2017) as merge_detections' suppression step (frcnn_detect_merge_soft, include/frcnn_hip.h): a picked box
+    decays the scores of the boxes it overlaps instead of dropping them.  method "linear": score * (1 - IoU) where IoU > nms_threshold;
+    "gaussian": score * exp(-IoU^2 / sigma) where IoU > 0 (nms_threshold is not read); "hard": plain NMS, by the same scan.  A decayed
+    score below score_floor drops the box (Detectron's 0.001)."""
+    __slots__ = ()
+    METHODS = {"hard": _lib.SOFT_NMS_HARD, "linear": _lib.SOFT_NMS_LINEAR, "gaussian": _lib.SOFT_NMS_GAUSSIAN}
+
+    def __new__(cls, method="linear", sigma=0.5, score_floor=1e-3):
+        if method not in cls.METHODS:
+            raise ValueError("SoftNMS: method %r, expected one of %s" % (method, sorted(cls.METHODS)))
+        sigma, score_floor = float(sigma), float(score_floor)
+        if method == "gaussian" and not sigma > 0:
+            raise ValueError("SoftNMS: sigma = %r must be > 0 in gaussian mode" % sigma)
+        if score_floor != score_floor:
+            raise ValueError("SoftNMS: score_floor is NaN")
+        return super().__new__(cls, method, sigma, score_floor)
+
+    @property
+    def code(self):
+        return self.METHODS[self.method]
+
+
+def merge_detections(sets, hflip=None, vflip=None, num_classes=None, min_score=0.0, nms_threshold=0.3, vote_threshold=None, capacity=None, soft_nms=None):
     """Merges K <= 8 Detections of one frame -- the views of test-time augmentation, the results of two weight sets -- into one, in two
     launches and no host sync (frcnn_detect_merge, include/frcnn_hip.h): per class the live rows of every set with score > min_score, in
     (score descending, set ascending, row ascending) order, greedy nms(nms_threshold), class-major concatenation.  hflip / vflip: one bool
     per set, True where the view was mirrored (its boxes are mirrored back: 1 - x, 1 - y on normalised coordinates).  vote_threshold (None
     = off): box voting, every kept box becomes the score-weighted mean of the class's candidates with IoU >= vote_threshold.  The rows may
     come in any order and class_counts is not read, so the proposal Detections merge as well.  capacity: the output's rows, by default
-    min(the sets' capacities summed, (num_classes - 1) * 2048).  Returns MergedDetections."""
+    min(the sets' capacities summed, (num_classes - 1) * 2048).  soft_nms (a SoftNMS; None = the greedy suppression above, by
+    frcnn_detect_merge as ever): the suppression becomes the Soft-NMS scan of frcnn_detect_merge_soft -- nms_threshold is the decay's
+    threshold, the scores that come out are the decayed ones, still in descending order inside a class.  Returns MergedDetections."""
+    if soft_nms is not None and not isinstance(soft_nms, SoftNMS):
+        raise TypeError("merge_detections: soft_nms must be an ops.SoftNMS or None, got %r" % (soft_nms,))
     sets = list(sets)
     K = len(sets)
     if not 1 <= K <= _lib.MERGE_MAX_SETS:
@@ -445,13 +472,15 @@ def merge_detections(sets, hflip=None, vflip=None, num_classes=None, min_score=0
     nb = _lib.workspace_bytes(_lib.OP_DETECT_MERGE, max(cap, 0), C_)
     ws = _workspace(dev, nb)
     vp = C.c_void_p * K
+    rows = (K, vp(*[t.data_ptr() for t in boxes]), vp(*[t.data_ptr() for t in labels]), vp(*[t.data_ptr() for t in scores]),
+            vp(*[t.data_ptr() for t in counts]), (C.c_int64 * K)(*caps), (C.c_uint32 * K)(*[int(h) | (int(v) << 1) for h, v in zip(hflip, vflip)]),
+            C_, float(min_score), float(nms_threshold), -1.0 if vote_threshold is None else float(vote_threshold))
+    outs = (_ptr(out_boxes), _ptr(out_labels), _ptr(out_scores), _ptr(count), _ptr(class_counts), _ptr(status), cap, _ptr(ws), nb, _stream())
     with torch.cuda.device(dev):
-        check(lib.frcnn_detect_merge(K, vp(*[t.data_ptr() for t in boxes]), vp(*[t.data_ptr() for t in labels]), vp(*[t.data_ptr() for t in scores]),
-                                     vp(*[t.data_ptr() for t in counts]), (C.c_int64 * K)(*caps),
-                                     (C.c_uint32 * K)(*[int(h) | (int(v) << 1) for h, v in zip(hflip, vflip)]), C_, float(min_score),
-                                     float(nms_threshold), -1.0 if vote_threshold is None else float(vote_threshold), _ptr(out_boxes),
-                                     _ptr(out_labels), _ptr(out_scores), _ptr(count), _ptr(class_counts), _ptr(status), cap, _ptr(ws), nb, _stream()),
-              "detect_merge")
+        if soft_nms is None:
+            check(lib.frcnn_detect_merge(*(rows + outs)), "detect_merge")
+        else:
+            check(lib.frcnn_detect_merge_soft(*(rows + (soft_nms.code, soft_nms.sigma, soft_nms.score_floor) + outs)), "detect_merge_soft")
     return MergedDetections(out_boxes, out_labels, out_scores, count, class_counts, None, sets[0].n_rois, status)
 
 

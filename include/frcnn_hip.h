@@ -577,6 +577,36 @@ int frcnn_detect_merge(int K, const float *const *boxes /*[caps[k],4] xyxy*/, co
                        int32_t *out_count /*[1]*/, int32_t *out_class_counts /*[C-1] or NULL*/, int32_t *out_status /*[1] or NULL*/,
                        int64_t out_capacity, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Soft-NMS (Bodla et al., 2017) as the merge's suppression step: defined by this project, restated from the published algorithm. */
+#define FRCNN_SOFT_NMS_HARD 0       /* an overlapped candidate is dropped: frcnn_detect_merge's result, bit for bit */
+#define FRCNN_SOFT_NMS_LINEAR 1     /* its score is multiplied by 1 - IoU */
+#define FRCNN_SOFT_NMS_GAUSSIAN 2   /* its score is multiplied by exp(-IoU^2 / sigma) */
+/* frcnn_detect_merge with another suppression step.  Transform, Candidates, Order, Box voting, Emit, Limits, the workspace
+ * (FRCNN_OP_DETECT_MERGE), the status bits, the -1 counts and the refusals are frcnn_detect_merge's, word for word; two launches whatever
+ * the data holds, graph-capturable, the per-set rows by value in the kernel arguments.  The order gives every candidate of a class a sorted
+ * position p.
+ * Suppression: every candidate p carries a working score w_p (fp32), at first its own score.  While a candidate is live:
+ *   1. Pick the live candidate with the largest w, on a tie the smallest p (-0 counts as +0: the order of the candidates' keys).
+ *   2. Emit it with score w and its (flipped-back) box; it is no longer live.  Scores are therefore non-increasing inside a class.
+ *   3. For every live j: ov = the fp32 IoU quotient of the suppression decision (picked box, box j); a NaN ov decays nothing.
+ *        HARD:     ov > nms_threshold (strict): j is dropped.
+ *        LINEAR:   ov > nms_threshold: w_j = w_j * (1.0f - ov), one fp32 subtraction and one fp32 multiplication.
+ *        GAUSSIAN: ov > 0: w_j = w_j * (float)exp(-((double)ov * (double)ov) / (double)sigma): the weight in binary64 (the device's exp,
+ *                  within an ulp of it), rounded once to fp32, then one fp32 multiplication.  nms_threshold is not read.
+ *      After a decay j stays live only if w_j >= score_floor (a NaN drops).  A candidate that was never decayed is never tested against
+ *      the floor.  For nms_threshold >= 0 a NaN or zero-area box is never decayed, decays nobody and is emitted at its own score: its
+ *      ov is NaN or 0.
+ * Box voting: as frcnn_detect_merge -- the voters of an emitted box are itself and every candidate of the class, live, dropped or emitted,
+ *   with IoU >= vote_threshold, weighted by their ORIGINAL scores in the binary64 order stated there; the emitted score is the working score.
+ * Cost: one step per candidate of a class, the classes in parallel (the greedy scan skips suppressed boxes, this one cannot).
+ * FRCNN_ERR_INVALID_ARG also for a method outside 0 .. 2, a sigma that is not > 0 in GAUSSIAN mode, and a NaN score_floor. */
+int frcnn_detect_merge_soft(int K, const float *const *boxes /*[caps[k],4] xyxy*/, const int32_t *const *labels /*[caps[k]]*/,
+                            const float *const *scores /*[caps[k]]*/, const int32_t *const *counts /*[1]*/, const int64_t *caps,
+                            const uint32_t *flags, int C, float min_score, float nms_threshold, float vote_threshold, int method, float sigma,
+                            float score_floor, float *out_boxes /*[out_capacity,4]*/, int32_t *out_labels /*[out_capacity]*/,
+                            float *out_scores /*[out_capacity]*/, int32_t *out_count /*[1]*/, int32_t *out_class_counts /*[C-1] or NULL*/,
+                            int32_t *out_status /*[1] or NULL*/, int64_t out_capacity, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- detection evaluator: the VOC AP protocol (evaluation/voc_eval.py:67-112,115-135,138-225) ------------------------ */
 /* Flags of a record: 2 bits per threshold t (bits 2t, 2t+1). */
 #define FRCNN_EVAL_TP 1u
