@@ -71,6 +71,14 @@ def log2f(x):
     return np.array([L.orc_log2f(float(v)) for v in x.ravel()], dtype=np.float32).reshape(x.shape)
 
 
+def log2f_array(x):
+    """orc_log2f over a whole array in one call (bulk tests); element for element the scalar function."""
+    x = _f32(x)
+    out = np.empty_like(x)
+    _chk(lib().orc_log2f_n(_p(x), C.c_int64(x.size), _p(out)), "log2f_n")
+    return out
+
+
 # -- anchors ------------------------------------------------------------------
 def anchor_base(base_size=16, ratios=(0.5, 1, 2), scales=(8, 16, 32)):
     r = np.asarray(ratios, dtype=np.float64)
