@@ -1778,29 +1778,6 @@ static CfWs cf_carve(void *ws, int C, size_t u_floats = 0, size_t vm_floats = 0)
 }
 size_t frcnn_ws_rpn_conv_f32(int64_t C) { return (C > 0 && C <= 4096) ? cf_carve(nullptr, (int)C).total : 0; }
 
-static int cf_run(const float *const *in, float *const *out, const int *H, const int *W, int n_levels, int C, const float *w, const CfWs &ws,
-                  hipStream_t s)
-{
-    CfArgs a;
-    a.n_levels = n_levels; a.C = C; a.n_co_tiles = C / CF_MT; a.Kc = C / CF_CI;
-    int tiles = 0;
-    for (int l = 0; l < FRCNN_MAX_LEVELS; ++l) {
-        if (l < n_levels) {
-            a.lv[l] = {in[l], out[l], H[l], W[l], H[l] * W[l], tiles};
-            tiles += (H[l] * W[l] + CF_NT - 1) / CF_NT;
-        } else a.lv[l] = {nullptr, nullptr, 1, 1, 1, 1 << 30};
-    }
-    a.n_pos_tiles = tiles;
-    a.pos_major = (long long)tiles * CF_NT * C > 2ll * C * C * 9 ? 1 : 0;      // activations larger than twice the weights
-    const long long n_tiles = (long long)tiles * a.n_co_tiles, units = n_tiles * a.Kc;
-    FRCNN_REQUIRE(n_tiles <= CF_MAX_TILES && units < (1ll << 31), "rpn_conv3x3_f32: %lld tiles above the limit %d", n_tiles, CF_MAX_TILES);
-    a.n_units = (int)units;
-    a.G = (int)std::min<long long>(cf_ranges(), units);
-    FRCNN_LAUNCH(rpn_conv3x3_f32_kernel, dim3((unsigned)a.G), dim3(256), 0, s, a, w, ws.part, ws.cnt);
-    FRCNN_CHECK_LAUNCH("rpn_conv3x3_f32_kernel");
-    return FRCNN_OK;
-}
-
 // development A/B: FRCNN_CONV_F32_DIRECT=1 keeps the direct (9 C deep) kernel for forward / data gradient
 static bool cf_use_direct()
 {
@@ -1828,22 +1805,6 @@ static long long wn_padded(int M, const int *H, const int *W, int n_levels, int 
     return narrow ? t64 : t128;
 }
 
-static long long wn_fill(WnArgs *a, int M, const float *const *in, float *const *out, const int *H, const int *W, int n_levels)
-{
-    long long off = 0;
-    wn_padded(M, H, W, n_levels, &a->tg);
-    for (int l = 0; l < FRCNN_MAX_LEVELS; ++l) {
-        if (l < n_levels) {
-            const int tw = (W[l] + M - 1) / M, th = (H[l] + M - 1) / M;
-            a->lv[l] = {in ? in[l] : nullptr, out ? out[l] : nullptr, H[l], W[l], tw, th * tw, (int)off};
-            off += ((long long)th * tw + a->tg - 1) / a->tg * a->tg;
-        } else a->lv[l] = {nullptr, nullptr, 1, 1, 1, 0, 1 << 30};
-    }
-    a->bias = nullptr; a->relu = 0; a->zero_pad = 0; a->db_part = nullptr; a->out2 = nullptr; a->bits_out = nullptr; a->bits = nullptr;
-    a->n_levels = n_levels; a->C = 0; a->Ttot = (int)off;
-    return off;
-}
-
 // The tile size of a call: what the stage executes scales with planes x padded tiles (36 planes over a quarter of the tiles against 16), so m = 4
 // wherever that product is at least 15 % smaller -- every map of more than a few hundred tiles; small maps, whose 4 x 4 tiles would mostly be
 // padding, keep m = 2 and its smaller rounding error.  FRCNN_WINO_M=2|4 forces one (development A/B and the tests' second form)
@@ -1857,9 +1818,9 @@ static int wn_pick_m(const int *H, const int *W, int n_levels)
 
 static bool wn_dims_ok(int Cin, int Cout) { return Cin > 0 && Cout > 0 && Cin % WN_KC == 0 && Cout % WN_KC == 0 && Cin <= 4096 && Cout <= 4096; }
 
-// A product of the stage as the host plans it: the tile shape, the tile and unit counts, the workgroups and how the units are cut among them.  wn_run and
-// wn_wgrad launch from these, frcnn_conv3x3_f32_supported checks their limits, frcnn_conv3x3_f32_plan reports them: one copy of every rule.
-struct WnProduct { int MT, NW, n_m_tiles, n_t_tiles, Kc; long long n_tiles, units; int G, whole, sched; };
+// A product of the stage as the host plans it: the tile shape, the tile and unit counts, the workgroups and how the units are cut among them (ok: within the
+// control block's limits, set by wn_geom).  A call's three products live in its WnGeom, below.
+struct WnProduct { int MT, NW, n_m_tiles, n_t_tiles, Kc; long long n_tiles, units; int G, whole, sched; bool ok; };
 static bool wn_product_ok(const WnProduct &p) { return p.n_tiles <= CF_MAX_TILES && p.units < (1ll << 31); }
 static bool wn_no_fuse()                                             // development A/B: FRCNN_WINO_NO_FUSE=1 keeps the 64 -> 64 product and its output transform apart
 {
@@ -1906,40 +1867,100 @@ static WnProduct wn_wgrad_product(int M, int Cin, int Cout, long long Ttot)
     return p;
 }
 
-static CfWs wn_carve(void *workspace, int Cin, int Cout, int M, long long Ttot)
+// The geometry of a call on levels H x W with Cin -> Cout channels: the tile size, the padded tile total, the per-level tile records, the three products
+// and the verdict of every limit the kernels' 32-bit offsets and the control block set.  An entry point fills ONE (wn_geom) and hands it down: wn_run and
+// wn_wgrad launch from it, cf_check and frcnn_conv3x3_f32_supported read its verdicts, frcnn_conv3x3_f32_plan and the size queries report it: one copy of
+// every rule.  (H, W: the caller's host arrays, at least n_levels long, 1 <= n_levels <= FRCNN_MAX_LEVELS.  wn_geom takes any sizes and channel counts, so that
+// it can judge them, but the products mean something only where empty_level < 0 and wn_dims_ok(Cin, Cout): readers check those first.)
+struct WnGeom {
+    const int *H, *W;
+    int n_levels, Cin, Cout, M, P, tg;                               // tile size (2 | 4), its (M + 2)^2 planes, the granularity the tile counts are padded to
+    long long Ttot;                                                  // padded tile total
+    WnLevel lv[FRCNN_MAX_LEVELS];                                    // (x, y NULL: wn_fill adds a call's pointers)
+    WnProduct fwd, dgrad, wgrad;
+    int empty_level, large_level;                                    // the first level with a side < 1 / with H W max(Cin, Cout) >= 2^31, or -1
+    bool tiles_ok, planes_ok;                                        // Ttot < 2^24;  P max(Cin, Cout) Ttot < 2^33 (the transformed operands' offsets)
+};
+static void wn_geom(WnGeom *g, const int *H, const int *W, int n_levels, int Cin, int Cout)
 {
-    const int C = ((std::max(Cin, Cout) + CF_MT - 1) / CF_MT) * CF_MT, P = (M + 2) * (M + 2);
-    return cf_carve(workspace, C, (size_t)P * Cin * Cout, (size_t)P * std::max(Cin, Cout) * Ttot);
+    const int M = wn_pick_m(H, W, n_levels), Cm = std::max(Cin, Cout);
+    g->H = H; g->W = W; g->n_levels = n_levels; g->Cin = Cin; g->Cout = Cout; g->M = M; g->P = (M + 2) * (M + 2);
+    g->empty_level = g->large_level = -1;
+    long long off = 0;
+    wn_padded(M, H, W, n_levels, &g->tg);
+    for (int l = 0; l < FRCNN_MAX_LEVELS; ++l) {
+        if (l < n_levels) {
+            const int tw = (W[l] + M - 1) / M, th = (H[l] + M - 1) / M;
+            g->lv[l] = {nullptr, nullptr, H[l], W[l], tw, th * tw, (int)off};
+            off += ((long long)th * tw + g->tg - 1) / g->tg * g->tg;
+            if (g->empty_level < 0 && (H[l] <= 0 || W[l] <= 0)) g->empty_level = l;
+            if (g->large_level < 0 && (long long)H[l] * W[l] * Cm >= (1ll << 31)) g->large_level = l;
+        } else g->lv[l] = {nullptr, nullptr, 1, 1, 1, 0, 1 << 30};
+    }
+    g->Ttot = off;
+    g->tiles_ok = off < (1ll << 24);
+    g->planes_ok = (long long)g->P * Cm * off < (1ll << 31) * 4;
+    g->fwd = wn_product(M, Cout, Cin, off, g->tg);
+    g->dgrad = wn_product(M, Cin, Cout, off, g->tg);
+    g->wgrad = wn_wgrad_product(M, Cin, Cout, off);
+    for (WnProduct *p : {&g->fwd, &g->dgrad, &g->wgrad}) p->ok = wn_product_ok(*p);
 }
 
+// a launch's arguments: the geometry's records with the call's per-level pointers
+static void wn_fill(WnArgs *a, const WnGeom &g, const float *const *in, float *const *out)
+{
+    for (int l = 0; l < FRCNN_MAX_LEVELS; ++l) {
+        a->lv[l] = g.lv[l];
+        if (l < g.n_levels) { a->lv[l].x = in ? in[l] : nullptr; a->lv[l].y = out ? out[l] : nullptr; }
+    }
+    a->bias = nullptr; a->relu = 0; a->zero_pad = 0; a->db_part = nullptr; a->out2 = nullptr; a->bits_out = nullptr; a->bits = nullptr;
+    a->n_levels = g.n_levels; a->C = 0; a->Ttot = (int)g.Ttot; a->tg = g.tg;
+}
+
+// the run-time tile size as a template parameter: f(std::integral_constant<int, 2 | 4>)
+template <class F>
+static auto wn_with_m(int M, F &&f) { return M == 4 ? f(std::integral_constant<int, 4>{}) : f(std::integral_constant<int, 2>{}); }
+
+static CfWs wn_carve(void *workspace, const WnGeom &g, int M, long long Ttot)
+{
+    const int C = ((std::max(g.Cin, g.Cout) + CF_MT - 1) / CF_MT) * CF_MT, P = (M + 2) * (M + 2);
+    return cf_carve(workspace, C, (size_t)P * g.Cin * g.Cout, (size_t)P * std::max(g.Cin, g.Cout) * Ttot);
+}
+// the bytes a call on g's shapes needs: whichever tile size it picks (the choice may be forced by the environment)
+static size_t wn_workspace(const WnGeom &g)
+{
+    const int other = 6 - g.M;
+    return std::max(wn_carve(nullptr, g, g.M, g.Ttot).total, wn_carve(nullptr, g, other, wn_padded(other, g.H, g.W, g.n_levels, nullptr)).total);
+}
+
+// the queries' geometry: false (the query answers 0) for arguments none is made of; a channel count a query does not take stands in as 1
+static bool wn_query(WnGeom *g, const int *H, const int *W, int n_levels, int Cin = 1, int Cout = 1)
+{
+    if (!H || !W || n_levels < 1 || n_levels > FRCNN_MAX_LEVELS || Cin <= 0 || Cout <= 0) return false;
+    wn_geom(g, H, W, n_levels, Cin, Cout);
+    return true;
+}
 FRCNN_EXPORT size_t frcnn_conv3x3_f32_workspace(const int *H_host, const int *W_host, int n_levels, int Cin, int Cout)
 {
-    if (!H_host || !W_host || n_levels < 1 || n_levels > FRCNN_MAX_LEVELS || !wn_dims_ok(Cin, Cout)) return 0;
-    size_t need = 0;
-    for (int M = 2; M <= 4; M += 2) {                                // whichever tile size a call picks (the choice may be forced by the environment)
-        WnArgs a;
-        const long long Ttot = wn_fill(&a, M, nullptr, nullptr, H_host, W_host, n_levels);
-        need = std::max(need, wn_carve(nullptr, Cin, Cout, M, Ttot).total);
-    }
-    return need;
+    WnGeom g;
+    return wn_dims_ok(Cin, Cout) && wn_query(&g, H_host, W_host, n_levels, Cin, Cout) ? wn_workspace(g) : 0;
 }
 FRCNN_EXPORT size_t frcnn_rpn_conv3x3_f32_workspace(const int *H_host, const int *W_host, int n_levels, int C)
 {
-    if (C <= 0 || C % CF_MT != 0) return 0;
-    return frcnn_conv3x3_f32_workspace(H_host, W_host, n_levels, C, C);
+    return C > 0 && C % CF_MT == 0 ? frcnn_conv3x3_f32_workspace(H_host, W_host, n_levels, C, C) : 0;
 }
 
 template <int M>
-static int wn_strips(WnStrips *st, const WnArgs &a, const int *H, int n_levels, long long channels, int halo, size_t *lds_bytes, int sm = M,
-                     int *settled = nullptr)
+static int wn_strips(WnStrips *st, const WnArgs &a, long long channels, int halo, size_t *lds_bytes, int sm = M, int *settled = nullptr)
 {
+    const int n_levels = a.n_levels;
     int n_strips = 0;
     for (int per_block = Wn<M>::TPB; per_block >= 256; per_block /= 2) {       // the largest strips that still give the chip >= 4096 workgroups
         n_strips = 0;
         if (settled) *settled = per_block;                           // (frcnn_conv3x3_f32_plan reports it)
         for (int l = 0; l < FRCNN_MAX_LEVELS; ++l) {
             st->first[l] = n_strips;
-            const int tw = l < n_levels ? a.lv[l].tw : 1, th = l < n_levels ? (H[l] + M - 1) / M : 1;
+            const int tw = l < n_levels ? a.lv[l].tw : 1, th = l < n_levels ? (a.lv[l].H + M - 1) / M : 1;
             st->segs[l] = (tw + Wn<M>::WT - 1) / Wn<M>::WT;
             st->rows[l] = std::min(128, std::max(1, per_block / std::min(tw, Wn<M>::WT)));   // (M R + 2)(M wt + 2) <= Wn<M>::LDS for every wt <= WT
             if (l < n_levels) n_strips += st->segs[l] * ((th + st->rows[l] - 1) / st->rows[l]);
@@ -1949,79 +1970,87 @@ static int wn_strips(WnStrips *st, const WnArgs &a, const int *H, int n_levels, 
     }
     size_t fl = 0;                                                   // LDS: the largest (M R + 2 halo)(M wt + 2 halo) window of the levels
     for (int l = 0; l < n_levels; ++l) {
-        const int wt = std::min(a.lv[l].tw, Wn<M>::WT), th = (H[l] + M - 1) / M, nr = std::min(st->rows[l], th);
+        const int wt = std::min(a.lv[l].tw, Wn<M>::WT), th = (a.lv[l].H + M - 1) / M, nr = std::min(st->rows[l], th);
         fl = std::max(fl, (size_t)(sm * nr + 2 * halo) * (size_t)(sm * wt + 2 * halo));      // sm = staged pixels per tile side (2 for pooled gradients)
     }
     *lds_bytes = fl * sizeof(float);
     return n_strips;
 }
 
-// forward (transposed = false) or data gradient (true) of the convolution with w [Cout][Cin][3][3] through the Winograd domain: four
-// launches for all levels.  forward: K = Cin, M = Cout (+ bias, ReLU in the output transform);  data gradient: K = Cout, M = Cin, the
-// incoming gradient optionally masked by the forward's ReLU output
-// later != NULL (frcnn_conv3x3_f32_bwd): the output transform is not launched but described there -- the caller launches it with the weight gradient's last kernel
+// wn_run: forward or data gradient of the convolution with w [Cout][Cin][3][3] through the Winograd domain, and a call's options by name.  The default is the
+// plain forward: K = Cin, Mo = Cout, four launches for all levels (three where the weight transform rides in the input transform's launch, or where the product
+// and the output transform are one kernel: 64 -> 64 channels on 4 x 4 tiles).
+// later (frcnn_conv3x3_f32_bwd): the output transform is not launched but described there -- the caller launches it with the weight gradient's last kernel
 // (and, with `products` set by the caller, the product too: gemm_pending -- the caller launches it with the weight gradient's product)
-struct WnOutLater { WnArgs a; const float *Mp; int Mo; bool pending; bool products; bool gemm_pending; WgArgs g; int MT, NW; };
+struct WnOutLater { WnArgs a; const float *Mp; int Mo; bool pending = false, products = false, gemm_pending = false; WgArgs g; int MT, NW; };
+struct WnRunOpts {
+    bool transposed = false;                                         // the data gradient: K = Cout, Mo = Cin, the weights rotated
+    const float *bias = nullptr; int relu = 0;                       // forward: + bias[c], then 0 none | 1 ReLU | 2 ReLU + max_pool2d(2, 2) (4 x 4 tile only)
+    unsigned short *bits_out = nullptr; float *xt = nullptr;         // forward: where the ReLU's sign (pool window) words go / the transformed activations are kept
+    const float *u_rot = nullptr;                                    // forward: the rotated weight transform is WRITTEN here too;  data gradient: read here, none made
+    const unsigned short *bits_in = nullptr; bool pooled = false;    // data gradient: the forward's words mask `in`; `in` is at the pooled resolution (4 x 4 tile only)
+    float *dm_out = nullptr; bool want_bias = false;                 // data gradient: also leave the gradient's weight-gradient transform here / the bias partials
+    WnOutLater *later = nullptr;
+};
 template <int M>
-static int wn_run(const float *const *in, float *const *out, const unsigned short *bits_in, const int *H, const int *W, int n_levels, int Cin, int Cout,
-                  const float *w, bool transposed, const float *bias, int relu, unsigned short *bits_out, float *xt, void *workspace, hipStream_t s,
-                  bool pooled = false, const float *u_rot = nullptr, float *dm_out = nullptr, bool want_bias = false, WnOutLater *later = nullptr)
+static int wn_run(const WnGeom &g, const float *const *in, float *const *out, const float *w, const WnRunOpts &o, void *workspace, hipStream_t s)
 {
-    // relu (forward): 0 none, 1 ReLU, 2 ReLU + max_pool2d(2, 2);  pooled (data gradient): `in` is at the pooled resolution, bits_in are pool words
-    constexpr int P = Wn<M>::P;
-    const int K = transposed ? Cout : Cin, Mo = transposed ? Cin : Cout;
+    const int Cin = g.Cin, Cout = g.Cout, K = o.transposed ? Cout : Cin, Mo = o.transposed ? Cin : Cout, relu = o.relu, rot = o.transposed ? 1 : 0;
+    const long long Ttot = g.Ttot;
+    const bool pooled = o.pooled;
+    const float *const u_rot = o.u_rot;
     WnArgs a;
-    const long long Ttot = wn_fill(&a, M, in, out, H, W, n_levels);
-    a.bits = bits_in;
-    FRCNN_REQUIRE(Ttot < (1ll << 24) && (long long)P * std::max(K, Mo) * Ttot < (1ll << 31) * 4, "conv3x3_f32: %lld output tiles are too many", Ttot);
-    const CfWs ws = wn_carve(workspace, Cin, Cout, M, Ttot);
-    const WnProduct pr = wn_product(M, Mo, K, Ttot, a.tg);
-    const int MT = pr.MT;
-    FRCNN_REQUIRE(wn_product_ok(pr), "conv3x3_f32: %lld tiles above the limit %d", pr.n_tiles, CF_MAX_TILES);
-    const unsigned wb = (unsigned)((Mo / 16) * (K / 16));
+    wn_fill(&a, g, in, out);
+    a.bits = o.bits_in;
+    FRCNN_REQUIRE(g.tiles_ok && g.planes_ok, "conv3x3_f32: %lld output tiles are too many", Ttot);
+    const CfWs ws = wn_carve(workspace, g, M, Ttot);
+    const WnProduct &pr = o.transposed ? g.dgrad : g.fwd;
+    FRCNN_REQUIRE(pr.ok, "conv3x3_f32: %lld tiles above the limit %d", pr.n_tiles, CF_MAX_TILES);
+    const unsigned wb = (unsigned)((Mo / 16) * (K / 16)), n_wb = !o.transposed && u_rot ? 2 * wb : wb;       // weight blocks (both transforms: twice)
     const float *Uuse = ws.U;
     // the weight transform rides in the input transform's launch (rpn_wino_weight_input_kernel) where that is the plain one (MODE 0, not pooled).
     // Under the profiler brackets the two stay launches of their own: a bracket times ONE kernel name (the values are the same bits either way)
-    const bool w_in_input = !(transposed && u_rot) && !dm_out && !pooled && !frcnn_prof_on();
-    if (transposed && u_rot) Uuse = u_rot;                           // the forward already made the rotated transform
+    const bool w_in_input = !(o.transposed && u_rot) && !o.dm_out && !pooled && !frcnn_prof_on();
+    if (o.transposed && u_rot) Uuse = u_rot;                         // the forward already made the rotated transform
     else if (!w_in_input) {
-        FRCNN_LAUNCH(rpn_wino_weight_kernel<M>, dim3(!transposed && u_rot ? 2 * wb : wb), dim3(256), 0, s, w, ws.U, (float *)u_rot, Cout, Cin, transposed ? 1 : 0);
+        FRCNN_LAUNCH(rpn_wino_weight_kernel<M>, dim3(n_wb), dim3(256), 0, s, w, ws.U, (float *)u_rot, Cout, Cin, rot);
         FRCNN_CHECK_LAUNCH("rpn_wino_weight_kernel");
     }
     a.C = K;
-    float *Vb = xt ? xt : ws.V;                                      // kept for the weight gradient (zero padding columns included) or scratch
-    a.zero_pad = xt ? 1 : 0;
+    float *Vb = o.xt ? o.xt : ws.V;                                  // kept for the weight gradient or scratch
+    a.zero_pad = o.xt ? 1 : 0;
     WnStrips st;
     size_t lds = 0;
     FRCNN_REQUIRE(!pooled || M == 4, "conv3x3_f32: a pooled gradient on the %d x %d tile", M, M);      // (the entry points refuse it first)
-    const int n_strips = wn_strips<M>(&st, a, H, n_levels, K, 1, &lds, pooled ? 2 : M);
-    if (dm_out) {                                                    // data gradient that also feeds the weight gradient: both transforms, one pass
-        a.out2 = dm_out; a.zero_pad = 1;
-        if (want_bias) {
+    const int n_strips = wn_strips<M>(&st, a, K, 1, &lds, pooled ? 2 : M);
+    const dim3 in_grid((unsigned)n_strips, (unsigned)K);
+    if (o.dm_out) {                                                  // data gradient that also feeds the weight gradient: both transforms, one pass
+        a.out2 = o.dm_out; a.zero_pad = 1;
+        if (o.want_bias) {
             const size_t C9 = (size_t)((std::max(Cin, Cout) + CF_MT - 1) / CF_MT) * CF_MT;
             FRCNN_REQUIRE((size_t)K * n_strips <= C9 * C9 * 9, "conv3x3_f32_bwd_data: %d strips are too many for the bias partials", n_strips);
             a.db_part = ws.wt;
         }
         if (pooled) {
-            if constexpr (M == 4) FRCNN_LAUNCH((rpn_wino_input_kernel<4, 2, true>), dim3((unsigned)n_strips, (unsigned)K), dim3(256), lds, s, a, st, Vb);
-        } else FRCNN_LAUNCH((rpn_wino_input_kernel<M, 2, false>), dim3((unsigned)n_strips, (unsigned)K), dim3(256), lds, s, a, st, Vb);
+            if constexpr (M == 4) FRCNN_LAUNCH((rpn_wino_input_kernel<4, 2, true>), in_grid, dim3(256), lds, s, a, st, Vb);
+        } else FRCNN_LAUNCH((rpn_wino_input_kernel<M, 2, false>), in_grid, dim3(256), lds, s, a, st, Vb);
     } else if (pooled) {
-        if constexpr (M == 4) FRCNN_LAUNCH((rpn_wino_input_kernel<4, 0, true>), dim3((unsigned)n_strips, (unsigned)K), dim3(256), lds, s, a, st, Vb);
+        if constexpr (M == 4) FRCNN_LAUNCH((rpn_wino_input_kernel<4, 0, true>), in_grid, dim3(256), lds, s, a, st, Vb);
     } else if (w_in_input) {
         // weight blocks: as many grid rows as hold them all, WN_W_ROWS at the most (a 512 -> 512 layer on a one-strip map has 2048 of them)
-        const unsigned n_wb = !transposed && u_rot ? 2 * wb : wb, w_rows = std::min<unsigned>((n_wb + (unsigned)n_strips - 1) / (unsigned)n_strips, WN_W_ROWS);
+        const unsigned w_rows = std::min<unsigned>((n_wb + (unsigned)n_strips - 1) / (unsigned)n_strips, WN_W_ROWS);
         FRCNN_LAUNCH(rpn_wino_weight_input_kernel<M>, dim3((unsigned)n_strips, (unsigned)K + w_rows), dim3(256), std::max(lds, sizeof(float) * 16 * WN_WS), s, a, st, Vb,
-                     w, ws.U, (float *)u_rot, Cout, Cin, transposed ? 1 : 0, n_wb, w_rows);
-    } else FRCNN_LAUNCH((rpn_wino_input_kernel<M, 0, false>), dim3((unsigned)n_strips, (unsigned)K), dim3(256), lds, s, a, st, Vb);
+                     w, ws.U, (float *)u_rot, Cout, Cin, rot, n_wb, w_rows);
+    } else FRCNN_LAUNCH((rpn_wino_input_kernel<M, 0, false>), in_grid, dim3(256), lds, s, a, st, Vb);
     FRCNN_CHECK_LAUNCH("rpn_wino_input_kernel");
+    a.C = Mo; a.bias = o.bias; a.relu = relu; a.bits_out = o.bits_out;           // from here on: the output side
     if constexpr (M == 4) {
         if (pr.sched == FRCNN_CONV_SCHED_FUSED_OUT64) {                  // 64 -> 64 channels: the product with the output transform fused in (wn_product)
-            a.C = Mo; a.bias = bias; a.relu = relu; a.bits_out = bits_out;
             const size_t wl = (size_t)WO_NB * K * (64 + WO_TB) * sizeof(float);      // 96 KB
-            // per call: the attribute is per device, and a process may drive several (the call is a table lookup in the runtime)
-            if (relu == 2) (void)hipFuncSetAttribute((const void *)rpn_wino_gemm_out64_kernel<64, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wl);
-            else (void)hipFuncSetAttribute((const void *)rpn_wino_gemm_out64_kernel<64, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wl);
             const dim3 gr((unsigned)(Ttot / WO_TB));
+            // the attribute per call: it is per device, and a process may drive several (the call is a table lookup in the runtime)
+            const void *fn = relu == 2 ? (const void *)rpn_wino_gemm_out64_kernel<64, true> : (const void *)rpn_wino_gemm_out64_kernel<64, false>;
+            (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wl);
             if (relu == 2) FRCNN_LAUNCH((rpn_wino_gemm_out64_kernel<64, true>), gr, dim3(256), wl, s, a, Uuse, Vb);
             else FRCNN_LAUNCH((rpn_wino_gemm_out64_kernel<64, false>), gr, dim3(256), wl, s, a, Uuse, Vb);
             FRCNN_CHECK_LAUNCH("rpn_wino_gemm_out64_kernel");
@@ -2029,34 +2058,39 @@ static int wn_run(const float *const *in, float *const *out, const unsigned shor
         }
     }
     // (the schedule -- whole-tile ranges, one tile per workgroup, or ranges that cut tiles -- is wn_product's)
-    WgArgs g = {Uuse, Vb, ws.M, (long long)Mo * K, (long long)K * Ttot, (long long)Mo * Ttot, Mo, (int)Ttot, (int)Ttot,
-                pr.n_m_tiles, pr.n_t_tiles, pr.Kc, (int)pr.units, pr.G, pr.whole};
+    WgArgs gm = {Uuse, Vb, ws.M, (long long)Mo * K, (long long)K * Ttot, (long long)Mo * Ttot, Mo, (int)Ttot, (int)Ttot,
+                 pr.n_m_tiles, pr.n_t_tiles, pr.Kc, (int)pr.units, pr.G, pr.whole};
+    WnOutLater *const later = relu != 2 ? o.later : nullptr;
     // (not where this product reads the workspace's U, which the weight gradient's product overwrites: only with the forward's rotated transform at hand)
-    if (later && later->products && relu != 2 && Uuse != ws.U) { later->g = g; later->MT = MT; later->NW = a.tg; later->gemm_pending = true; }
-    else { const int rc = wn_launch_gemm(false, MT, a.tg, g, ws.part, ws.cnt, s); if (rc) return rc; }
-    a.C = Mo; a.bias = bias; a.relu = relu; a.bits_out = bits_out;
-    if (later && relu != 2) { later->a = a; later->Mp = ws.M; later->Mo = Mo; later->pending = true; return FRCNN_OK; }
+    if (later && later->products && Uuse != ws.U) { later->g = gm; later->MT = pr.MT; later->NW = a.tg; later->gemm_pending = true; }
+    else { const int rc = wn_launch_gemm(false, pr.MT, a.tg, gm, ws.part, ws.cnt, s); if (rc) return rc; }
+    if (later) { later->a = a; later->Mp = ws.M; later->Mo = Mo; later->pending = true; return FRCNN_OK; }
+    const dim3 out_grid((unsigned)((Ttot + 255) / 256), (unsigned)Mo);
     if (relu == 2) {
-        if constexpr (M == 4) FRCNN_LAUNCH((rpn_wino_output_kernel<4, true>), dim3((unsigned)((Ttot + 255) / 256), (unsigned)Mo), dim3(256), 0, s, a, ws.M);
-    } else FRCNN_LAUNCH((rpn_wino_output_kernel<M, false>), dim3((unsigned)((Ttot + 255) / 256), (unsigned)Mo), dim3(256), 0, s, a, ws.M);
+        if constexpr (M == 4) FRCNN_LAUNCH((rpn_wino_output_kernel<4, true>), out_grid, dim3(256), 0, s, a, ws.M);
+    } else FRCNN_LAUNCH((rpn_wino_output_kernel<M, false>), out_grid, dim3(256), 0, s, a, ws.M);
     FRCNN_CHECK_LAUNCH("rpn_wino_output_kernel");
     return FRCNN_OK;
 }
 
-// in_mult / out_mult: what the GEMM of the call needs of the two channel counts (a side that is tiled by 128, or only chunked by 32)
-static int cf_check(const void *const *p0, const void *const *p1, const int *H, const int *W, int n_levels, int Cin, int Cout, int in_mult, int out_mult,
-                    const void *w, void *ws, size_t ws_bytes, const char *what)
+// What every entry point is handed beside its own options, and the refusals they share, in their order; *g is the call's geometry where FRCNN_OK comes back.
+// what: the entry point's name in the messages;  p0, p1: its two per-level pointer lists;  w: the weights (or their gradient);  in_mult / out_mult: what the
+// GEMM of the call needs of the two channel counts (a side that is tiled by 128, or only chunked by 32)
+struct CfCall { const char *what; const void *const *p0, *const *p1; const int *H, *W; int n_levels, Cin, Cout, in_mult, out_mult; const void *w; void *ws; size_t ws_bytes; };
+static int cf_check(WnGeom *g, const CfCall &c)
 {
-    FRCNN_REQUIRE(p0 && p1 && H && W && w && ws, "%s: NULL pointer", what);
-    FRCNN_REQUIRE(n_levels >= 1 && n_levels <= FRCNN_MAX_LEVELS, "%s: 1 <= n_levels <= %d", what, FRCNN_MAX_LEVELS);
-    if (!wn_dims_ok(Cin, Cout) || Cin % in_mult != 0 || Cout % out_mult != 0)
-        return frcnn_set_error(FRCNN_ERR_UNSUPPORTED, "%s: Cin=%d / Cout=%d must be multiples of %d / %d", what, Cin, Cout, in_mult, out_mult);
-    for (int l = 0; l < n_levels; ++l) {
-        FRCNN_REQUIRE(p0[l] && p1[l] && H[l] > 0 && W[l] > 0, "%s: bad level %d", what, l);
-        FRCNN_REQUIRE((long long)H[l] * W[l] * std::max(Cin, Cout) < (1ll << 31), "%s: level %d too large", what, l);
+    const char *what = c.what;
+    FRCNN_REQUIRE(c.p0 && c.p1 && c.H && c.W && c.w && c.ws, "%s: NULL pointer", what);
+    FRCNN_REQUIRE(c.n_levels >= 1 && c.n_levels <= FRCNN_MAX_LEVELS, "%s: 1 <= n_levels <= %d", what, FRCNN_MAX_LEVELS);
+    if (!wn_dims_ok(c.Cin, c.Cout) || c.Cin % c.in_mult != 0 || c.Cout % c.out_mult != 0)
+        return frcnn_set_error(FRCNN_ERR_UNSUPPORTED, "%s: Cin=%d / Cout=%d must be multiples of %d / %d", what, c.Cin, c.Cout, c.in_mult, c.out_mult);
+    wn_geom(g, c.H, c.W, c.n_levels, c.Cin, c.Cout);
+    for (int l = 0; l < c.n_levels; ++l) {
+        FRCNN_REQUIRE(c.p0[l] && c.p1[l] && l != g->empty_level, "%s: bad level %d", what, l);
+        FRCNN_REQUIRE(l != g->large_level, "%s: level %d too large", what, l);
     }
-    const size_t need = frcnn_conv3x3_f32_workspace(H, W, n_levels, Cin, Cout);
-    if (ws_bytes < need) return frcnn_set_error(FRCNN_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", what, ws_bytes, need);
+    const size_t need = wn_workspace(*g);
+    if (c.ws_bytes < need) return frcnn_set_error(FRCNN_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", what, c.ws_bytes, need);
     return FRCNN_OK;
 }
 
@@ -2064,181 +2098,173 @@ FRCNN_EXPORT int frcnn_conv3x3_f32_fwd(const float *const *x_dev, float *const *
                                        const float *w_dev, const float *bias_dev, int relu, unsigned short *relu_bits_dev, float *x_transformed_dev, float *u_rotated_dev,
                                        void *workspace, size_t workspace_bytes, void *stream)
 {
-    int rc = cf_check((const void *const *)x_dev, (const void *const *)y_dev, H_host, W_host, n_levels, Cin, Cout, WN_KC, 64, w_dev, workspace, workspace_bytes,
-                      "conv3x3_f32_fwd");
-    if (rc) return rc;
+    const CfCall c = {.what = "conv3x3_f32_fwd", .p0 = (const void *const *)x_dev, .p1 = (const void *const *)y_dev, .H = H_host, .W = W_host, .n_levels = n_levels,
+                      .Cin = Cin, .Cout = Cout, .in_mult = WN_KC, .out_mult = 64, .w = w_dev, .ws = workspace, .ws_bytes = workspace_bytes};
+    WnGeom g;
+    if (const int rc = cf_check(&g, c)) return rc;
     FRCNN_REQUIRE(relu >= 0 && relu <= 2, "conv3x3_f32_fwd: relu = %d (0 none, 1 ReLU, 2 ReLU + max_pool2d(2, 2))", relu);
-    if (relu == 2 && wn_pick_m(H_host, W_host, n_levels) != 4)
+    if (relu == 2 && g.M != 4)
         return frcnn_set_error(FRCNN_ERR_UNSUPPORTED, "conv3x3_f32_fwd: the fused max-pool needs the 4 x 4 tile (frcnn_conv3x3_f32_tile_size)");
-    if (wn_pick_m(H_host, W_host, n_levels) == 4)
-        return wn_run<4>(x_dev, y_dev, nullptr, H_host, W_host, n_levels, Cin, Cout, w_dev, false, bias_dev, relu, relu_bits_dev, x_transformed_dev, workspace, (hipStream_t)stream,
-                         false, u_rotated_dev);
-    return wn_run<2>(x_dev, y_dev, nullptr, H_host, W_host, n_levels, Cin, Cout, w_dev, false, bias_dev, relu, relu_bits_dev, x_transformed_dev, workspace, (hipStream_t)stream,
-                     false, u_rotated_dev);
+    const WnRunOpts o = {.bias = bias_dev, .relu = relu, .bits_out = relu_bits_dev, .xt = x_transformed_dev, .u_rot = u_rotated_dev};
+    return wn_with_m(g.M, [&](auto m) { return wn_run<decltype(m)::value>(g, x_dev, y_dev, w_dev, o, workspace, (hipStream_t)stream); });
 }
 
 // 1 when the three calls would accept these shapes (channel multiples, tile / unit counts within the control block, sizes within the 32-bit offsets the
 // kernels use), 0 otherwise: what a caller's dispatch (ops.conv3x3_supported) asks before it routes a layer here instead of to the vendor library
+static bool wn_supported(const WnGeom &g, bool need_grads)
+{
+    if (!wn_dims_ok(g.Cin, g.Cout) || g.Cout % 64 != 0 || (need_grads && g.Cin % 64 != 0)) return false;
+    if (g.empty_level >= 0 || g.large_level >= 0 || !g.tiles_ok || !g.planes_ok || !g.fwd.ok) return false;
+    return !need_grads || (g.dgrad.ok && g.wgrad.ok);
+}
 FRCNN_EXPORT int frcnn_conv3x3_f32_supported(const int *H_host, const int *W_host, int n_levels, int Cin, int Cout, int need_grads)
 {
-    if (!H_host || !W_host || n_levels < 1 || n_levels > FRCNN_MAX_LEVELS || !wn_dims_ok(Cin, Cout) || Cout % 64 != 0 || (need_grads && Cin % 64 != 0)) return 0;
-    const int M = wn_pick_m(H_host, W_host, n_levels), P = (M + 2) * (M + 2), Cm = std::max(Cin, Cout);
-    WnArgs a;
-    const long long Ttot = wn_fill(&a, M, nullptr, nullptr, H_host, W_host, n_levels);
-    for (int l = 0; l < n_levels; ++l)
-        if (H_host[l] <= 0 || W_host[l] <= 0 || (long long)H_host[l] * W_host[l] * Cm >= (1ll << 31)) return 0;
-    if (Ttot >= (1ll << 24) || (long long)P * Cm * Ttot >= (1ll << 31) * 4) return 0;
-    if (!wn_product_ok(wn_product(M, Cout, Cin, Ttot, a.tg))) return 0;                          // forward
-    if (need_grads && (!wn_product_ok(wn_product(M, Cin, Cout, Ttot, a.tg)) || !wn_product_ok(wn_wgrad_product(M, Cin, Cout, Ttot)))) return 0;      // data gradient, weight gradient
-    return 1;
+    WnGeom g;
+    return wn_query(&g, H_host, W_host, n_levels, Cin, Cout) && wn_supported(g, need_grads != 0) ? 1 : 0;
 }
 
-template <int M>
-static void wn_plan_strips(int *o, const WnArgs &a, const int *H, int n_levels, long long channels)
-{
-    WnStrips st;
-    size_t lds = 0;
-    o[1] = wn_strips<M>(&st, a, H, n_levels, channels, 1, &lds, M, &o[0]);
-    for (int l = 0; l < n_levels; ++l) {
-        const int th = (H[l] + M - 1) / M, tw = a.lv[l].tw;
-        int *q = o + 2 + 4 * l;
-        q[0] = st.segs[l]; q[1] = st.rows[l];
-        q[2] = th % st.rows[l];                                      // a last strip with fewer tile rows than the others (a level of one short strip included)
-        q[3] = tw % Wn<M>::WT;                                       // a last segment with fewer tiles than WT
-    }
-}
 FRCNN_EXPORT int frcnn_conv3x3_f32_plan(const int *H_host, const int *W_host, int n_levels, int Cin, int Cout, int *plan_host, int plan_len)
 {
     static_assert(FRCNN_CONV_PLAN_MAX_LEVELS == FRCNN_MAX_LEVELS, "the plan's per-level records");
     FRCNN_REQUIRE(H_host && W_host && plan_host, "conv3x3_f32_plan: NULL pointer");
     FRCNN_REQUIRE(plan_len >= FRCNN_CONV_PLAN_INTS, "conv3x3_f32_plan: plan_len %d < %d", plan_len, FRCNN_CONV_PLAN_INTS);
     FRCNN_REQUIRE(n_levels >= 1 && n_levels <= FRCNN_MAX_LEVELS, "conv3x3_f32_plan: 1 <= n_levels <= %d", FRCNN_MAX_LEVELS);
-    for (int l = 0; l < n_levels; ++l) FRCNN_REQUIRE(H_host[l] > 0 && W_host[l] > 0, "conv3x3_f32_plan: bad level %d", l);
-    if (!frcnn_conv3x3_f32_supported(H_host, W_host, n_levels, Cin, Cout, 0))
+    WnGeom g;
+    wn_geom(&g, H_host, W_host, n_levels, Cin, Cout);
+    FRCNN_REQUIRE(g.empty_level < 0, "conv3x3_f32_plan: bad level %d", g.empty_level);
+    if (!wn_supported(g, false))
         return frcnn_set_error(FRCNN_ERR_UNSUPPORTED, "conv3x3_f32_plan: the forward does not take Cin=%d / Cout=%d on these shapes", Cin, Cout);
-    const bool grads = frcnn_conv3x3_f32_supported(H_host, W_host, n_levels, Cin, Cout, 1) != 0;
+    const bool grads = wn_supported(g, true);
     for (int i = 0; i < FRCNN_CONV_PLAN_INTS; ++i) plan_host[i] = 0;
-    const int M = wn_pick_m(H_host, W_host, n_levels);
     WnArgs a;
-    const long long Ttot = wn_fill(&a, M, nullptr, nullptr, H_host, W_host, n_levels);
+    wn_fill(&a, g, nullptr, nullptr);
     int *o = plan_host;
-    o[0] = M; o[1] = a.tg; o[2] = (int)Ttot; o[3] = n_levels; o[4] = cf_ranges(); o[5] = wn_ranges_nt(); o[6] = M == 4 ? 1 : 0;
+    o[0] = g.M; o[1] = g.tg; o[2] = (int)g.Ttot; o[3] = n_levels; o[4] = cf_ranges(); o[5] = wn_ranges_nt(); o[6] = g.M == 4 ? 1 : 0;
     o += FRCNN_CONV_PLAN_HEAD;
-    const WnProduct pr[3] = {wn_product(M, Cout, Cin, Ttot, a.tg), grads ? wn_product(M, Cin, Cout, Ttot, a.tg) : WnProduct{},
-                             grads ? wn_wgrad_product(M, Cin, Cout, Ttot) : WnProduct{}};
+    const WnProduct *pr[3] = {&g.fwd, &g.dgrad, &g.wgrad};
     for (int k = 0; k < 3; ++k, o += FRCNN_CONV_PLAN_PRODUCT) {
         if (k > 0 && !grads) continue;
-        const WnProduct &p = pr[k];
+        const WnProduct &p = *pr[k];
         o[0] = 1; o[1] = p.MT; o[2] = p.NW; o[3] = p.n_m_tiles; o[4] = p.n_t_tiles; o[5] = p.Kc; o[6] = (int)p.n_tiles; o[7] = (int)p.units; o[8] = p.G; o[9] = p.sched;
     }
-    for (int k = 0; k < 2; ++k, o += FRCNN_CONV_PLAN_STRIPS) {
-        if (M == 4) wn_plan_strips<4>(o, a, H_host, n_levels, k ? Cout : Cin);
-        else wn_plan_strips<2>(o, a, H_host, n_levels, k ? Cout : Cin);
-    }
+    for (int k = 0; k < 2; ++k, o += FRCNN_CONV_PLAN_STRIPS) wn_with_m(g.M, [&](auto m) {       // the transform launches over Cin, then Cout channels
+        constexpr int M = decltype(m)::value;
+        WnStrips st;
+    size_t lds = 0;
+        o[1] = wn_strips<M>(&st, a, k ? Cout : Cin, 1, &lds, M, &o[0]);
+        for (int l = 0; l < n_levels; ++l) {
+            int *q = o + 2 + 4 * l;
+            q[0] = st.segs[l]; q[1] = st.rows[l];
+            q[2] = (a.lv[l].H + M - 1) / M % st.rows[l];             // a last strip with fewer tile rows than the others (a level of one short strip included)
+            q[3] = a.lv[l].tw % Wn<M>::WT;                           // a last segment with fewer tiles than WT
+        }
+    });
     return FRCNN_OK;
 }
 
 FRCNN_EXPORT int frcnn_conv3x3_f32_tile_size(const int *H_host, const int *W_host, int n_levels)
 {
-    if (!H_host || !W_host || n_levels < 1 || n_levels > FRCNN_MAX_LEVELS) return 0;
-    return wn_pick_m(H_host, W_host, n_levels);
-}
-
-FRCNN_EXPORT size_t frcnn_conv3x3_f32_relu_bits_words(const int *H_host, const int *W_host, int n_levels, int Cout)
-{
-    if (!H_host || !W_host || n_levels < 1 || n_levels > FRCNN_MAX_LEVELS || Cout <= 0) return 0;
-    WnArgs a;
-    return (size_t)Cout * (size_t)wn_fill(&a, wn_pick_m(H_host, W_host, n_levels), nullptr, nullptr, H_host, W_host, n_levels);
+    WnGeom g;
+    return wn_query(&g, H_host, W_host, n_levels) ? g.M : 0;
 }
 
 FRCNN_EXPORT size_t frcnn_conv3x3_f32_u_floats(const int *H_host, const int *W_host, int n_levels, int Cin, int Cout)
 {
-    if (!H_host || !W_host || n_levels < 1 || n_levels > FRCNN_MAX_LEVELS || Cin <= 0 || Cout <= 0) return 0;
-    const int M = wn_pick_m(H_host, W_host, n_levels);
-    return (size_t)((M + 2) * (M + 2)) * (size_t)Cin * (size_t)Cout;
+    WnGeom g;
+    return wn_query(&g, H_host, W_host, n_levels, Cin, Cout) ? (size_t)g.P * (size_t)Cin * (size_t)Cout : 0;
 }
 
 FRCNN_EXPORT size_t frcnn_conv3x3_f32_xt_floats(const int *H_host, const int *W_host, int n_levels, int Cin)
 {
-    if (!H_host || !W_host || n_levels < 1 || n_levels > FRCNN_MAX_LEVELS || Cin <= 0) return 0;
-    const int M = wn_pick_m(H_host, W_host, n_levels);
-    WnArgs a;
-    return (size_t)((M + 2) * (M + 2)) * (size_t)Cin * (size_t)wn_fill(&a, M, nullptr, nullptr, H_host, W_host, n_levels);
+    WnGeom g;
+    return wn_query(&g, H_host, W_host, n_levels, Cin) ? (size_t)g.P * (size_t)Cin * (size_t)g.Ttot : 0;
+}
+
+FRCNN_EXPORT size_t frcnn_conv3x3_f32_relu_bits_words(const int *H_host, const int *W_host, int n_levels, int Cout)
+{
+    WnGeom g;
+    return wn_query(&g, H_host, W_host, n_levels, 1, Cout) ? (size_t)Cout * (size_t)g.Ttot : 0;
 }
 
 FRCNN_EXPORT int frcnn_conv3x3_f32_bwd_data(const float *const *dy_dev, const unsigned short *relu_bits_dev, float *const *dx_dev, const int *H_host, const int *W_host,
                                             int n_levels, int Cin, int Cout, const float *w_dev, const float *u_rotated_dev, int pooled, float *dy_transformed_dev,
                                             int want_bias_partials, void *workspace, size_t workspace_bytes, void *stream)
 {
-    int rc = cf_check((const void *const *)dy_dev, (const void *const *)dx_dev, H_host, W_host, n_levels, Cin, Cout, 64, WN_KC, w_dev, workspace, workspace_bytes,
-                      "conv3x3_f32_bwd_data");
-    if (rc) return rc;
-    if (pooled && (!relu_bits_dev || wn_pick_m(H_host, W_host, n_levels) != 4))
+    const CfCall c = {.what = "conv3x3_f32_bwd_data", .p0 = (const void *const *)dy_dev, .p1 = (const void *const *)dx_dev, .H = H_host, .W = W_host, .n_levels = n_levels,
+                      .Cin = Cin, .Cout = Cout, .in_mult = 64, .out_mult = WN_KC, .w = w_dev, .ws = workspace, .ws_bytes = workspace_bytes};
+    WnGeom g;
+    if (const int rc = cf_check(&g, c)) return rc;
+    if (pooled && (!relu_bits_dev || g.M != 4))
         return frcnn_set_error(FRCNN_ERR_UNSUPPORTED, "conv3x3_f32_bwd_data: a pooled gradient needs the forward's words and the 4 x 4 tile");
-    if (wn_pick_m(H_host, W_host, n_levels) == 4)
-        return wn_run<4>(dy_dev, dx_dev, relu_bits_dev, H_host, W_host, n_levels, Cin, Cout, w_dev, true, nullptr, 0, nullptr, nullptr, workspace, (hipStream_t)stream,
-                         pooled != 0, u_rotated_dev, dy_transformed_dev, want_bias_partials != 0);
-    return wn_run<2>(dy_dev, dx_dev, relu_bits_dev, H_host, W_host, n_levels, Cin, Cout, w_dev, true, nullptr, 0, nullptr, nullptr, workspace, (hipStream_t)stream,
-                     false, u_rotated_dev, dy_transformed_dev, want_bias_partials != 0);
+    const WnRunOpts o = {.transposed = true, .u_rot = u_rotated_dev, .bits_in = relu_bits_dev, .pooled = pooled != 0, .dm_out = dy_transformed_dev,
+                         .want_bias = want_bias_partials != 0};
+    return wn_with_m(g.M, [&](auto m) { return wn_run<decltype(m)::value>(g, dy_dev, dx_dev, w_dev, o, workspace, (hipStream_t)stream); });
 }
 
 // weight gradient through the Winograd domain: V = B^T d B of the features and dM = A g A^T of the (masked) output gradient, both [xi][channel][t];
 // dU = sum over the tiles on the k-contiguous form of the stage's GEMM (K = Ttot); dW = G^T dU G: four launches for all levels (+ one for the
 // bias gradient)
+struct WnWgradOpts {
+    const unsigned short *bits = nullptr; bool pooled = false;       // the forward's words mask d_outs; d_outs are at the pooled resolution (4 x 4 tile only)
+    float *dbias = nullptr;                                          // also the bias gradient
+    const float *xt = nullptr, *dm_in = nullptr;                     // the forward's / the data gradient call's kept transform: that side is not transformed again
+    const WnOutLater *later = nullptr;                               // what the data gradient's call left to this one's launches (frcnn_conv3x3_f32_bwd)
+};
 template <int M>
-static int wn_wgrad(const float *const *feats, const float *const *d_outs, const unsigned short *bits, const int *H, const int *W, int n_levels, int Cin, int Cout,
-                    float *dw, float *dbias, const float *xt, void *workspace, hipStream_t s, bool pooled = false, const float *dm_in = nullptr,
-                    const WnOutLater *later = nullptr)
+static int wn_wgrad(const WnGeom &g, const float *const *feats, const float *const *d_outs, float *dw, const WnWgradOpts &o, void *workspace, hipStream_t s)
 {
+    const int Cin = g.Cin, Cout = g.Cout, n_levels = g.n_levels;
+    const long long Ttot = g.Ttot;
+    const WnOutLater *const later = o.later;
     WnArgs a;
-    const long long Ttot = wn_fill(&a, M, feats, nullptr, H, W, n_levels);
-    FRCNN_REQUIRE(Ttot < (1ll << 24), "conv3x3_f32_wgrad: %lld output tiles are too many", Ttot);
-    const CfWs ws = wn_carve(workspace, Cin, Cout, M, Ttot);
-    const WnProduct pr = wn_wgrad_product(M, Cin, Cout, Ttot);
+    wn_fill(&a, g, feats, nullptr);
+    FRCNN_REQUIRE(g.tiles_ok, "conv3x3_f32_wgrad: %lld output tiles are too many", Ttot);
+    const CfWs ws = wn_carve(workspace, g, M, Ttot);
+    const WnProduct &pr = g.wgrad;
     const int MT = pr.MT, NW = pr.NW, C9 = ((std::max(Cin, Cout) + CF_MT - 1) / CF_MT) * CF_MT;            // ws.wt holds C9^2 * 9 floats
-    FRCNN_REQUIRE(wn_product_ok(pr), "conv3x3_f32_wgrad: %lld tiles above the limit %d", pr.n_tiles, CF_MAX_TILES);
+    FRCNN_REQUIRE(pr.ok, "conv3x3_f32_wgrad: %lld tiles above the limit %d", pr.n_tiles, CF_MAX_TILES);
     WnStrips st;
     a.C = Cin; a.zero_pad = 1;
     size_t lds = 0;
     int n_strips = 0;
-    if (!xt) {                                                       // the forward did not keep B^T d B of the activations: transform them again
-        n_strips = wn_strips<M>(&st, a, H, n_levels, Cin, 1, &lds);
+    if (!o.xt) {                                                     // the forward did not keep B^T d B of the activations: transform them again
+        n_strips = wn_strips<M>(&st, a, Cin, 1, &lds);
         FRCNN_LAUNCH((rpn_wino_input_kernel<M, 0, false>), dim3((unsigned)n_strips, (unsigned)Cin), dim3(256), lds, s, a, st, ws.V);
         FRCNN_CHECK_LAUNCH("rpn_wino_input_kernel");
     }
     WnArgs g1 = a;                                                   // the output gradient (and its mask) as the transform's input
     for (int l = 0; l < n_levels; ++l) g1.lv[l].x = d_outs[l];
-    g1.bits = bits;
+    g1.bits = o.bits;
     g1.C = Cout;
-    FRCNN_REQUIRE(!pooled || M == 4, "conv3x3_f32_wgrad: a pooled gradient on the %d x %d tile", M, M);
-    n_strips = wn_strips<M>(&st, g1, H, n_levels, Cout, dm_in ? 1 : 0, &lds, pooled ? 2 : M);      // (dm_in: the strips of the data gradient's launch that made it)
+    FRCNN_REQUIRE(!o.pooled || M == 4, "conv3x3_f32_wgrad: a pooled gradient on the %d x %d tile", M, M);
+    n_strips = wn_strips<M>(&st, g1, Cout, o.dm_in ? 1 : 0, &lds, o.pooled ? 2 : M);      // (dm_in: the strips of the data gradient's launch that made it)
     const int n_strips_dy = n_strips;
-    FRCNN_REQUIRE(!dbias || (size_t)Cout * n_strips_dy <= (size_t)C9 * C9 * 9, "conv3x3_f32_wgrad: %d strips are too many for the bias partials", n_strips_dy);
-    if (dbias) g1.db_part = ws.wt;                                   // the bias gradient's strip partials ride in this launch (in the direct form's weight
+    FRCNN_REQUIRE(!o.dbias || (size_t)Cout * n_strips_dy <= (size_t)C9 * C9 * 9, "conv3x3_f32_wgrad: %d strips are too many for the bias partials", n_strips_dy);
+    if (o.dbias) g1.db_part = ws.wt;                                 // the bias gradient's strip partials ride in this launch (in the direct form's weight
                                                                      // buffer, idle in this form) and are added up by the last launch
-    if (dm_in) {
+    if (o.dm_in) {
         // the data gradient's call already transformed the output gradient for this product (and left the bias partials in ws.wt)
-    } else if (pooled) {
+    } else if (o.pooled) {
         if constexpr (M == 4) FRCNN_LAUNCH((rpn_wino_input_kernel<4, 1, true>), dim3((unsigned)n_strips, (unsigned)Cout), dim3(256), lds, s, g1, st, ws.M);
     } else FRCNN_LAUNCH((rpn_wino_input_kernel<M, 1, false>), dim3((unsigned)n_strips, (unsigned)Cout), dim3(256), lds, s, g1, st, ws.M);
     FRCNN_CHECK_LAUNCH("rpn_wino_input_kernel");
-    WgArgs g = {dm_in ? dm_in : ws.M, xt ? xt : ws.V, ws.U, Ttot * Cout, Ttot * Cin, (long long)Cout * Cin, (int)Ttot, (int)Ttot, Cin, pr.n_m_tiles, pr.n_t_tiles, pr.Kc,
-                (int)pr.units, pr.G, pr.whole};
+    WgArgs gm = {o.dm_in ? o.dm_in : ws.M, o.xt ? o.xt : ws.V, ws.U, Ttot * Cout, Ttot * Cin, (long long)Cout * Cin, (int)Ttot, (int)Ttot, Cin, pr.n_m_tiles, pr.n_t_tiles, pr.Kc,
+                 (int)pr.units, pr.G, pr.whole};
     bool both = false;
     if (later && later->gemm_pending) {
         // the data gradient's product, which that call left to this one: one launch for both where the pair of tile shapes is built, else its own launch first
-        const int rc = wn_launch_gemm2(later->MT, later->NW, later->g, MT, NW, g, ws.part, ws.cnt, ws.part2, ws.cnt2, s, &both);
+        const int rc = wn_launch_gemm2(later->MT, later->NW, later->g, MT, NW, gm, ws.part, ws.cnt, ws.part2, ws.cnt2, s, &both);
         if (rc) return rc;
         if (!both) { const int rc1 = wn_launch_gemm(false, later->MT, later->NW, later->g, ws.part, ws.cnt, s); if (rc1) return rc1; }
     }
-    if (!both) { const int rc = wn_launch_gemm(true, MT, NW, g, ws.part, ws.cnt, s); if (rc) return rc; }
-    const unsigned n = (unsigned)Cout * (unsigned)Cin, n_dw_blocks = (n + 255u) / 256u + (dbias ? (unsigned)Cout : 0u);
+    if (!both) { const int rc = wn_launch_gemm(true, MT, NW, gm, ws.part, ws.cnt, s); if (rc) return rc; }
+    const unsigned n = (unsigned)Cout * (unsigned)Cin, n_dw_blocks = (n + 255u) / 256u + (o.dbias ? (unsigned)Cout : 0u);
     if (later && later->pending) {
         // the data gradient's output transform, which that call left to this one: neither of the two kernels reads what the other writes
         const unsigned gx = (unsigned)((later->a.Ttot + 255) / 256);
         if (!frcnn_prof_on()) {                                      // (the profiler brackets time ONE kernel name each: separate launches there)
             const unsigned dw_rows = std::min<unsigned>((n_dw_blocks + gx - 1) / gx, WN_W_ROWS);
-            FRCNN_LAUNCH(rpn_wino_output_dw_kernel<M>, dim3(gx, (unsigned)later->Mo + dw_rows), dim3(256), 0, s, later->a, later->Mp, ws.U, dw, n, dbias, ws.wt,
+            FRCNN_LAUNCH(rpn_wino_output_dw_kernel<M>, dim3(gx, (unsigned)later->Mo + dw_rows), dim3(256), 0, s, later->a, later->Mp, ws.U, dw, n, o.dbias, ws.wt,
                          n_strips_dy, n_dw_blocks, dw_rows);
             FRCNN_CHECK_LAUNCH("rpn_wino_output_dw_kernel");
             return FRCNN_OK;
@@ -2246,7 +2272,7 @@ static int wn_wgrad(const float *const *feats, const float *const *d_outs, const
         FRCNN_LAUNCH((rpn_wino_output_kernel<M, false>), dim3(gx, (unsigned)later->Mo), dim3(256), 0, s, later->a, later->Mp);
         FRCNN_CHECK_LAUNCH("rpn_wino_output_kernel");
     }
-    FRCNN_LAUNCH(rpn_wino_dw_kernel<M>, dim3(n_dw_blocks), dim3(256), 0, s, ws.U, dw, n, dbias, ws.wt, n_strips_dy);
+    FRCNN_LAUNCH(rpn_wino_dw_kernel<M>, dim3(n_dw_blocks), dim3(256), 0, s, ws.U, dw, n, o.dbias, ws.wt, n_strips_dy);
     FRCNN_CHECK_LAUNCH("rpn_wino_dw_kernel");
     return FRCNN_OK;
 }
@@ -2255,15 +2281,13 @@ FRCNN_EXPORT int frcnn_conv3x3_f32_wgrad(const float *const *x_dev, const float 
                                          int n_levels, int Cin, int Cout, float *dw_dev, float *dbias_dev, const float *x_transformed_dev, int pooled,
                                          const float *dy_transformed_dev, void *workspace, size_t workspace_bytes, void *stream)
 {
-    int rc = cf_check((const void *const *)x_dev, (const void *const *)dy_dev, H_host, W_host, n_levels, Cin, Cout, 64, 64, dw_dev, workspace, workspace_bytes,
-                      "conv3x3_f32_wgrad");
-    if (rc) return rc;
-    if (wn_pick_m(H_host, W_host, n_levels) == 4)
-        return wn_wgrad<4>(x_dev, dy_dev, relu_bits_dev, H_host, W_host, n_levels, Cin, Cout, dw_dev, dbias_dev, x_transformed_dev, workspace, (hipStream_t)stream,
-                           pooled != 0, dy_transformed_dev);
-    if (pooled) return frcnn_set_error(FRCNN_ERR_UNSUPPORTED, "conv3x3_f32_wgrad: a pooled gradient needs the forward's words and the 4 x 4 tile");
-    return wn_wgrad<2>(x_dev, dy_dev, relu_bits_dev, H_host, W_host, n_levels, Cin, Cout, dw_dev, dbias_dev, x_transformed_dev, workspace, (hipStream_t)stream, false,
-                       dy_transformed_dev);
+    const CfCall c = {.what = "conv3x3_f32_wgrad", .p0 = (const void *const *)x_dev, .p1 = (const void *const *)dy_dev, .H = H_host, .W = W_host, .n_levels = n_levels,
+                      .Cin = Cin, .Cout = Cout, .in_mult = 64, .out_mult = 64, .w = dw_dev, .ws = workspace, .ws_bytes = workspace_bytes};
+    WnGeom g;
+    if (const int rc = cf_check(&g, c)) return rc;
+    if (pooled && g.M != 4) return frcnn_set_error(FRCNN_ERR_UNSUPPORTED, "conv3x3_f32_wgrad: a pooled gradient needs the forward's words and the 4 x 4 tile");
+    const WnWgradOpts o = {.bits = relu_bits_dev, .pooled = pooled != 0, .dbias = dbias_dev, .xt = x_transformed_dev, .dm_in = dy_transformed_dev};
+    return wn_with_m(g.M, [&](auto m) { return wn_wgrad<decltype(m)::value>(g, x_dev, dy_dev, dw_dev, o, workspace, (hipStream_t)stream); });
 }
 
 // Both gradients of a layer whose forward kept the transformed activations, in one call: what frcnn_conv3x3_f32_bwd_data (with dy_transformed_dev) followed by
@@ -2271,34 +2295,28 @@ FRCNN_EXPORT int frcnn_conv3x3_f32_wgrad(const float *const *x_dev, const float 
 // as ONE launch (rpn_wino_output_dw_kernel) and, on the tile-shape pairs of wn_launch_gemm2, the two products as one (rpn_wino_gemm2_kernel): three or four
 // launches where the two calls make five.  A 64 -> 64 layer on the 4 x 4 tile, whose product and output transform are one kernel already, runs exactly the two
 // calls' launches.
-template <int M>
-static int wn_bwd(const float *const *dy, const unsigned short *bits, float *const *dx, const int *H, const int *W, int n_levels, int Cin, int Cout, const float *w,
-                  const float *u_rot, bool pooled, const float *xt, float *dyt, float *dw, float *dbias, void *workspace, hipStream_t s)
-{
-    // development A/B: FRCNN_CONV_F32_BWD_PRODUCTS=2 launches the two products of the call one after the other
-    static const bool two = [] { const char *e = getenv("FRCNN_CONV_F32_BWD_PRODUCTS"); return e && atoi(e) == 2; }();
-    WnOutLater later;
-    later.pending = later.gemm_pending = false;
-    later.products = !two && !frcnn_prof_on();                       // (under the profiler brackets every kernel name keeps launches of its own)
-    int rc = wn_run<M>(dy, dx, bits, H, W, n_levels, Cin, Cout, w, true, nullptr, 0, nullptr, nullptr, workspace, s, pooled, u_rot, dyt, dbias != nullptr, &later);
-    if (rc) return rc;
-    return wn_wgrad<M>(dy, dy, bits, H, W, n_levels, Cin, Cout, dw, dbias, xt, workspace, s, pooled, dyt, &later);
-}
 FRCNN_EXPORT int frcnn_conv3x3_f32_bwd(const float *const *dy_dev, const unsigned short *relu_bits_dev, float *const *dx_dev, const int *H_host, const int *W_host,
                                        int n_levels, int Cin, int Cout, const float *w_dev, const float *u_rotated_dev, int pooled, const float *x_transformed_dev,
                                        float *dy_transformed_dev, float *dw_dev, float *dbias_dev, void *workspace, size_t workspace_bytes, void *stream)
 {
-    int rc = cf_check((const void *const *)dy_dev, (const void *const *)dx_dev, H_host, W_host, n_levels, Cin, Cout, 64, 64, w_dev, workspace, workspace_bytes,
-                      "conv3x3_f32_bwd");
-    if (rc) return rc;
+    // development A/B: FRCNN_CONV_F32_BWD_PRODUCTS=2 launches the two products of the call one after the other
+    static const bool two = [] { const char *e = getenv("FRCNN_CONV_F32_BWD_PRODUCTS"); return e && atoi(e) == 2; }();
+    const CfCall c = {.what = "conv3x3_f32_bwd", .p0 = (const void *const *)dy_dev, .p1 = (const void *const *)dx_dev, .H = H_host, .W = W_host, .n_levels = n_levels,
+                      .Cin = Cin, .Cout = Cout, .in_mult = 64, .out_mult = 64, .w = w_dev, .ws = workspace, .ws_bytes = workspace_bytes};
+    WnGeom g;
+    if (const int rc = cf_check(&g, c)) return rc;
     FRCNN_REQUIRE(x_transformed_dev && dy_transformed_dev && dw_dev, "conv3x3_f32_bwd: NULL pointer (both cached transforms and dw are required)");
-    if (pooled && (!relu_bits_dev || wn_pick_m(H_host, W_host, n_levels) != 4))
+    if (pooled && (!relu_bits_dev || g.M != 4))
         return frcnn_set_error(FRCNN_ERR_UNSUPPORTED, "conv3x3_f32_bwd: a pooled gradient needs the forward's words and the 4 x 4 tile");
-    if (wn_pick_m(H_host, W_host, n_levels) == 4)
-        return wn_bwd<4>(dy_dev, relu_bits_dev, dx_dev, H_host, W_host, n_levels, Cin, Cout, w_dev, u_rotated_dev, pooled != 0, x_transformed_dev, dy_transformed_dev, dw_dev,
-                         dbias_dev, workspace, (hipStream_t)stream);
-    return wn_bwd<2>(dy_dev, relu_bits_dev, dx_dev, H_host, W_host, n_levels, Cin, Cout, w_dev, u_rotated_dev, false, x_transformed_dev, dy_transformed_dev, dw_dev, dbias_dev,
-                     workspace, (hipStream_t)stream);
+    WnOutLater later;
+    later.products = !two && !frcnn_prof_on();                       // (under the profiler brackets every kernel name keeps launches of its own)
+    const WnRunOpts ro = {.transposed = true, .u_rot = u_rotated_dev, .bits_in = relu_bits_dev, .pooled = pooled != 0, .dm_out = dy_transformed_dev,
+                          .want_bias = dbias_dev != nullptr, .later = &later};
+    const WnWgradOpts wo = {.bits = relu_bits_dev, .pooled = pooled != 0, .dbias = dbias_dev, .xt = x_transformed_dev, .dm_in = dy_transformed_dev, .later = &later};
+    return wn_with_m(g.M, [&](auto m) {
+        const int rc1 = wn_run<decltype(m)::value>(g, dy_dev, dx_dev, w_dev, ro, workspace, (hipStream_t)stream);
+        return rc1 ? rc1 : wn_wgrad<decltype(m)::value>(g, dy_dev, dy_dev, dw_dev, wo, workspace, (hipStream_t)stream);
+    });
 }
 
 // ---- the stage's k-contiguous GEMM on its own: O[m][n] = sum_k A[m][k] B[n][k] (fp32, fixed summation order).  The weight gradient of a 1 x 1 convolution
@@ -2325,15 +2343,65 @@ FRCNN_EXPORT int frcnn_gemm_nt_f32(const float *A_dev, const float *B_dev, float
 FRCNN_EXPORT size_t frcnn_gemm_nt_f32_workspace(void) { return cf_carve(nullptr, CF_MT).total; }
 
 // ---- the RPN head's entry points: Cin = Cout = C, no bias (rpn_head.hip adds it), no mask; FRCNN_CONV_F32_DIRECT=1 routes them to the direct kernels
+// the direct form's forward (and, on packed weights, its data gradient): C = g.Cin = g.Cout
+static int cf_run(const WnGeom &g, const float *const *in, float *const *out, const float *w, const CfWs &ws, hipStream_t s)
+{
+    const int C = g.Cin;
+    CfArgs a;
+    a.n_levels = g.n_levels; a.C = C; a.n_co_tiles = C / CF_MT; a.Kc = C / CF_CI;
+    int tiles = 0;
+    for (int l = 0; l < FRCNN_MAX_LEVELS; ++l) {
+        if (l < g.n_levels) {
+            a.lv[l] = {in[l], out[l], g.H[l], g.W[l], g.H[l] * g.W[l], tiles};
+            tiles += (g.H[l] * g.W[l] + CF_NT - 1) / CF_NT;
+        } else a.lv[l] = {nullptr, nullptr, 1, 1, 1, 1 << 30};
+    }
+    a.n_pos_tiles = tiles;
+    a.pos_major = (long long)tiles * CF_NT * C > 2ll * C * C * 9 ? 1 : 0;      // activations larger than twice the weights
+    const long long n_tiles = (long long)tiles * a.n_co_tiles, units = n_tiles * a.Kc;
+    FRCNN_REQUIRE(n_tiles <= CF_MAX_TILES && units < (1ll << 31), "rpn_conv3x3_f32: %lld tiles above the limit %d", n_tiles, CF_MAX_TILES);
+    a.n_units = (int)units;
+    a.G = (int)std::min<long long>(cf_ranges(), units);
+    FRCNN_LAUNCH(rpn_conv3x3_f32_kernel, dim3((unsigned)a.G), dim3(256), 0, s, a, w, ws.part, ws.cnt);
+    FRCNN_CHECK_LAUNCH("rpn_conv3x3_f32_kernel");
+    return FRCNN_OK;
+}
+// the direct form's weight gradient: 32 x 32 tiles of dW, each summed by S workgroups over the levels' row segments
+static int cf_wgrad_run(const WnGeom &g, const float *const *feats, const float *const *d_outs, float *dw, const CfWs &ws, hipStream_t s)
+{
+    CwArgs a;
+    a.n_levels = g.n_levels; a.C = g.Cin;
+    long long units = 0;
+    for (int l = 0; l < FRCNN_MAX_LEVELS; ++l) {
+        if (l < g.n_levels) {
+            const int ns = (g.W[l] + CW_TC - 1) / CW_TC;
+            a.lv[l] = {feats[l], d_outs[l], g.H[l], g.W[l], g.H[l] * g.W[l], ns, (int)units};
+            units += (long long)ns * g.H[l];
+        } else a.lv[l] = {nullptr, nullptr, 1, 1, 1, 1, 1 << 30};
+    }
+    FRCNN_REQUIRE(units < (1ll << 30), "rpn_conv3x3_f32_wgrad: too many row segments");
+    a.n_units = (int)units;
+    const int tiles = (g.Cin / 32) * (g.Cin / 32);
+    int S = CW_WPS * (cf_ranges() / CF_WPS) / tiles;                 // CW_WPS workgroups per CU: 256 tiles at C = 512, 64 tiles at C = 256
+    if (S < 1) S = 1;
+    if (S > 16) S = 16;
+    while (S > 1 && (long long)S * 4 > units) --S;
+    a.S = S;
+    FRCNN_LAUNCH(rpn_conv3x3_f32_wgrad_kernel, dim3((unsigned)(tiles * S)), dim3(256), 0, s, a, dw, ws.part, ws.cnt);
+    FRCNN_CHECK_LAUNCH("rpn_conv3x3_f32_wgrad_kernel");
+    return FRCNN_OK;
+}
+
 FRCNN_EXPORT int frcnn_rpn_conv3x3_f32_fwd(const float *const *feats_dev, float *const *outs_dev, const int *H_host, const int *W_host, int n_levels, int C,
                                            const float *w3_dev, void *workspace, size_t workspace_bytes, void *stream)
 {
     if (!cf_use_direct())
         return frcnn_conv3x3_f32_fwd(feats_dev, outs_dev, H_host, W_host, n_levels, C, C, w3_dev, nullptr, 0, nullptr, nullptr, nullptr, workspace, workspace_bytes, stream);
-    int rc = cf_check((const void *const *)feats_dev, (const void *const *)outs_dev, H_host, W_host, n_levels, C, C, CF_MT, CF_MT, w3_dev, workspace, workspace_bytes,
-                      "rpn_conv3x3_f32_fwd");
-    if (rc) return rc;
-    return cf_run(feats_dev, outs_dev, H_host, W_host, n_levels, C, w3_dev, cf_carve(workspace, C), (hipStream_t)stream);
+    const CfCall c = {.what = "rpn_conv3x3_f32_fwd", .p0 = (const void *const *)feats_dev, .p1 = (const void *const *)outs_dev, .H = H_host, .W = W_host, .n_levels = n_levels,
+                      .Cin = C, .Cout = C, .in_mult = CF_MT, .out_mult = CF_MT, .w = w3_dev, .ws = workspace, .ws_bytes = workspace_bytes};
+    WnGeom g;
+    if (const int rc = cf_check(&g, c)) return rc;
+    return cf_run(g, feats_dev, outs_dev, w3_dev, cf_carve(workspace, C), (hipStream_t)stream);
 }
 
 FRCNN_EXPORT int frcnn_rpn_conv3x3_f32_bwd_data(const float *const *d_outs_dev, float *const *d_feats_dev, const int *H_host, const int *W_host, int n_levels,
@@ -2341,14 +2409,15 @@ FRCNN_EXPORT int frcnn_rpn_conv3x3_f32_bwd_data(const float *const *d_outs_dev, 
 {
     if (!cf_use_direct())
         return frcnn_conv3x3_f32_bwd_data(d_outs_dev, nullptr, d_feats_dev, H_host, W_host, n_levels, C, C, w3_dev, nullptr, 0, nullptr, 0, workspace, workspace_bytes, stream);
-    int rc = cf_check((const void *const *)d_outs_dev, (const void *const *)d_feats_dev, H_host, W_host, n_levels, C, C, CF_MT, CF_MT, w3_dev, workspace,
-                      workspace_bytes, "rpn_conv3x3_f32_bwd_data");
-    if (rc) return rc;
+    const CfCall c = {.what = "rpn_conv3x3_f32_bwd_data", .p0 = (const void *const *)d_outs_dev, .p1 = (const void *const *)d_feats_dev, .H = H_host, .W = W_host, .n_levels = n_levels,
+                      .Cin = C, .Cout = C, .in_mult = CF_MT, .out_mult = CF_MT, .w = w3_dev, .ws = workspace, .ws_bytes = workspace_bytes};
+    WnGeom g;
+    if (const int rc = cf_check(&g, c)) return rc;
     const CfWs ws = cf_carve(workspace, C);
     hipStream_t s = (hipStream_t)stream;
     FRCNN_LAUNCH(rpn_conv_f32_pack_kernel, dim3((unsigned)((C / 16) * (C / 16))), dim3(256), 0, s, w3_dev, ws.wt, C);
     FRCNN_CHECK_LAUNCH("rpn_conv_f32_pack_kernel");
-    return cf_run(d_outs_dev, d_feats_dev, H_host, W_host, n_levels, C, ws.wt, ws, s);
+    return cf_run(g, d_outs_dev, d_feats_dev, ws.wt, ws, s);
 }
 
 FRCNN_EXPORT int frcnn_rpn_conv3x3_f32_wgrad(const float *const *feats_dev, const float *const *d_outs_dev, const int *H_host, const int *W_host, int n_levels,
@@ -2356,34 +2425,9 @@ FRCNN_EXPORT int frcnn_rpn_conv3x3_f32_wgrad(const float *const *feats_dev, cons
 {
     if (!cf_use_direct())
         return frcnn_conv3x3_f32_wgrad(feats_dev, d_outs_dev, nullptr, H_host, W_host, n_levels, C, C, dw_dev, nullptr, nullptr, 0, nullptr, workspace, workspace_bytes, stream);
-    int rc = cf_check((const void *const *)feats_dev, (const void *const *)d_outs_dev, H_host, W_host, n_levels, C, C, CF_MT, CF_MT, dw_dev, workspace, workspace_bytes,
-                      "rpn_conv3x3_f32_wgrad");
-    if (rc) return rc;
-    const CfWs ws = cf_carve(workspace, C);
-    CwArgs a;
-    a.n_levels = n_levels; a.C = C;
-    long long units = 0;
-    for (int l = 0; l < FRCNN_MAX_LEVELS; ++l) {
-        if (l < n_levels) {
-            const int ns = (W_host[l] + CW_TC - 1) / CW_TC;
-            a.lv[l] = {feats_dev[l], d_outs_dev[l], H_host[l], W_host[l], H_host[l] * W_host[l], ns, (int)units};
-            units += (long long)ns * H_host[l];
-        } else a.lv[l] = {nullptr, nullptr, 1, 1, 1, 1, 1 << 30};
-    }
-    FRCNN_REQUIRE(units < (1ll << 30), "rpn_conv3x3_f32_wgrad: too many row segments");
-    a.n_units = (int)units;
-    const int tiles = (C / 32) * (C / 32);
-    static const int cus = [] {
-        int dev = 0, c = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev);
-        return c;
-    }();
-    int S = CW_WPS * cus / tiles;                                   // CW_WPS workgroups per CU: 256 tiles at C = 512, 64 tiles at C = 256
-    if (S < 1) S = 1;
-    if (S > 16) S = 16;
-    while (S > 1 && (long long)S * 4 > units) --S;
-    a.S = S;
-    FRCNN_LAUNCH(rpn_conv3x3_f32_wgrad_kernel, dim3((unsigned)(tiles * S)), dim3(256), 0, (hipStream_t)stream, a, dw_dev, ws.part, ws.cnt);
-    FRCNN_CHECK_LAUNCH("rpn_conv3x3_f32_wgrad_kernel");
-    return FRCNN_OK;
+    const CfCall c = {.what = "rpn_conv3x3_f32_wgrad", .p0 = (const void *const *)feats_dev, .p1 = (const void *const *)d_outs_dev, .H = H_host, .W = W_host, .n_levels = n_levels,
+                      .Cin = C, .Cout = C, .in_mult = CF_MT, .out_mult = CF_MT, .w = dw_dev, .ws = workspace, .ws_bytes = workspace_bytes};
+    WnGeom g;
+    if (const int rc = cf_check(&g, c)) return rc;
+    return cf_wgrad_run(g, feats_dev, d_outs_dev, dw_dev, cf_carve(workspace, C), (hipStream_t)stream);
 }

@@ -991,67 +991,93 @@ def conv3x3_f32_products(mode=None):
 CONV_TRACE = None        # a list while a caller (bench.py) records which calls the fp32 conv stage gets in one step: dicts kind / Cin / Cout / shapes / mask / bias
 
 
-def _conv_trace(what, Cin, Cout, H, W, mask=False, bias=False, cached=False, relu_bits=False, pooled=False, urot=False):
+def _conv_trace(what, Cin, Cout, hw, mask=False, bias=False, cached=False, relu_bits=False, pooled=False, urot=False):
     if CONV_TRACE is not None:
         kind = "wgrad" if what.endswith("wgrad") else ("bwd_data" if what.endswith("bwd_data") else "fwd")
-        CONV_TRACE.append({"kind": kind, "Cin": int(Cin), "Cout": int(Cout), "shapes": [(int(h), int(w)) for h, w in zip(H, W)], "mask": bool(mask),
+        CONV_TRACE.append({"kind": kind, "Cin": int(Cin), "Cout": int(Cout), "shapes": [(int(h), int(w)) for h, w in hw], "mask": bool(mask),
                            "bias": bool(bias), "cached": bool(cached), "relu_bits": bool(relu_bits), "pooled": bool(pooled), "urot": bool(urot)})
 
 
-def _conv_f32_call(fn, what, ins, outs, C_, w_or_dw):
-    dev = ins[0].device
-    H = _host_i32([t.shape[2] for t in ins])
-    W = _host_i32([t.shape[3] for t in ins])
-    ip = (C.c_void_p * len(ins))(*[t.data_ptr() for t in ins])
-    op = (C.c_void_p * len(outs))(*[t.data_ptr() for t in outs])
-    nb = int(lib.frcnn_rpn_conv3x3_f32_workspace(_np_ptr(H), _np_ptr(W), len(ins), C_))
+def _level_sizes(hw):
+    """Level sizes hw = [(h, w), ...] as the C ABI takes them: (H, W, n), two host int32 arrays by pointer (a pointer keeps its array alive) and the count."""
+    return _np_ptr(_host_i32([h for h, _ in hw])), _np_ptr(_host_i32([w_ for _, w_ in hw])), len(hw)
+
+
+def _sizes_of(ts):
+    return [(int(t.shape[2]), int(t.shape[3])) for t in ts]
+
+
+def _ptr_list(ts):
+    return (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+
+
+def _conv3x3_call(fn, what, hw, Cin, Cout, dev, args_of, rpn=False, trace=True, **flags):
+    """One call into the fp32 conv stage on levels of sizes hw: args_of(H, W, n, workspace, bytes, stream) -> fn's arguments; flags: what CONV_TRACE keeps
+    of the call beside its shapes.  rpn: the RPN head's entry points (Cin = Cout, a multiple of 128)."""
+    if trace:
+        _conv_trace(what, Cin, Cout, hw, **flags)
+    H, W, n = _level_sizes(hw)
+    nb = int(lib.frcnn_rpn_conv3x3_f32_workspace(H, W, n, Cin) if rpn else lib.frcnn_conv3x3_f32_workspace(H, W, n, Cin, Cout))
     if nb == 0:
-        raise _lib.FrcnnError("%s: C = %d is outside what the fp32 conv kernels are built for (a multiple of 128)" % (what, C_))
-    ws = _ctrl_workspace(dev, "rpn_conv_f32", nb)     # ticket words zero on first use, left zero by every call; slabs + transposed weights behind them
+        raise _lib.FrcnnError(("%s: C = %d is outside what the fp32 conv kernels are built for (a multiple of 128)" % (what, Cin)) if rpn else
+                              ("%s: Cin = %d / Cout = %d is outside what the fp32 conv stage is built for (multiples of 32)" % (what, Cin, Cout)))
+    # ONE block for every fp32 3x3 of the step, sized by the largest layer seen: ticket words zero on first use, left zero by every call; slabs, weights
+    # and transformed operands behind them
+    ws = _ctrl_workspace(dev, "rpn_conv_f32", nb)
     with torch.cuda.device(dev):
-        check(fn(ip, op, _np_ptr(H), _np_ptr(W), len(ins), C_, _ptr(w_or_dw), _ptr(ws), ws.numel(), _stream()), what)
-    _conv_trace(what, C_, C_, H, W)
+        check(fn(*args_of(H, W, n, _ptr(ws), ws.numel(), _stream())), what)
 
 
-def _conv_f32_levels(ts, name):
+def _conv3x3_levels(ts, Cc, name, rpn=False):
+    """The levels of one call, each fp32 [1,Cc,h,w] (Cc None: the first level's), contiguous.  rpn: in the RPN head's words."""
     ts = [_req(t, torch.float32, name) for t in ts]
     if not ts:
-        raise ValueError("rpn_conv3x3: no feature level")
-    Cc = ts[0].shape[1]
+        raise ValueError("rpn_conv3x3: no feature level" if rpn else "conv3x3: no level")
+    Cc = ts[0].shape[1] if Cc is None else Cc
     for t in ts:
         if t.dim() != 4 or t.shape[0] != 1 or t.shape[1] != Cc:
-            raise ValueError("rpn_conv3x3: every level must be [1,C,h,w] (batch 1 per GPU) with the same C")
-    return ts, Cc
+            raise ValueError("rpn_conv3x3: every level must be [1,C,h,w] (batch 1 per GPU) with the same C" if rpn else
+                             "conv3x3: every %s level must be [1,%d,h,w] (batch 1 per GPU)" % (name, Cc))
+    return ts
+
+
+def _rpn_conv3x3_call(fn, what, ins, outs, w_or_dw):
+    ip, op, Cc = _ptr_list(ins), _ptr_list(outs), ins[0].shape[1]
+    hw = _sizes_of(ins)
+    _conv3x3_call(fn, what, hw, Cc, Cc, ins[0].device, lambda H, W, n, ws, nws, st: (ip, op, H, W, n, Cc, _ptr(w_or_dw), ws, nws, st), rpn=True, trace=False)
+    _conv_trace(what, Cc, Cc, hw)                     # (these calls are recorded once they have succeeded)
 
 
 def rpn_conv3x3_fwd(feats, w3):
     """Bias-free 3x3 convolution (padding 1) of every level with the shared weight w3 [C,C,3,3]: fp32 [1,C,h,w] -> fp32 [1,C,h,w]."""
-    feats, Cc = _conv_f32_levels(feats, "feature map")
+    feats = _conv3x3_levels(feats, None, "feature map", rpn=True)
+    Cc = feats[0].shape[1]
     w3 = _req(w3, name="w3")
     if tuple(w3.shape) != (Cc, Cc, 3, 3):
         raise ValueError("rpn_conv3x3: weight must be [C,C,3,3] with C = %d" % Cc)
     outs = [torch.empty_like(f) for f in feats]
-    _conv_f32_call(lib.frcnn_rpn_conv3x3_f32_fwd, "rpn_conv3x3_f32_fwd", feats, outs, Cc, w3)
+    _rpn_conv3x3_call(lib.frcnn_rpn_conv3x3_f32_fwd, "rpn_conv3x3_f32_fwd", feats, outs, w3)
     return outs
 
 
 def rpn_conv3x3_bwd_data(d_outs, w3):
     """Gradient of rpn_conv3x3_fwd with respect to its inputs (the same kernel on the transposed, flipped weights)."""
-    d_outs, Cc = _conv_f32_levels(d_outs, "d_out")
+    d_outs = _conv3x3_levels(d_outs, None, "d_out", rpn=True)
     w3 = _req(w3, name="w3")
     outs = [torch.empty_like(d) for d in d_outs]
-    _conv_f32_call(lib.frcnn_rpn_conv3x3_f32_bwd_data, "rpn_conv3x3_f32_bwd_data", d_outs, outs, Cc, w3)
+    _rpn_conv3x3_call(lib.frcnn_rpn_conv3x3_f32_bwd_data, "rpn_conv3x3_f32_bwd_data", d_outs, outs, w3)
     return outs
 
 
 def rpn_conv3x3_wgrad(feats, d_outs):
     """Gradient of rpn_conv3x3_fwd with respect to w3, summed over the levels: fp32 [C,C,3,3]."""
-    feats, Cc = _conv_f32_levels(feats, "feature map")
-    d_outs, _ = _conv_f32_levels(d_outs, "d_out")
+    feats = _conv3x3_levels(feats, None, "feature map", rpn=True)
+    d_outs = _conv3x3_levels(d_outs, None, "d_out", rpn=True)
+    Cc = feats[0].shape[1]
     if len(d_outs) != len(feats) or any(a.shape != b.shape for a, b in zip(feats, d_outs)):
         raise ValueError("rpn_conv3x3_wgrad: feats and d_outs differ in shape")
     dw = torch.empty((Cc, Cc, 3, 3), dtype=torch.float32, device=feats[0].device)
-    _conv_f32_call(lib.frcnn_rpn_conv3x3_f32_wgrad, "rpn_conv3x3_f32_wgrad", feats, d_outs, Cc, dw)
+    _rpn_conv3x3_call(lib.frcnn_rpn_conv3x3_f32_wgrad, "rpn_conv3x3_f32_wgrad", feats, d_outs, dw)
     return dw
 
 
@@ -1079,8 +1105,7 @@ def rpn_conv3x3_supported(feats, w3):
     C_ = int(w3.shape[0])
     if C_ % 128 != 0 or tuple(w3.shape) != (C_, C_, 3, 3) or len(feats) > 5:
         return False
-    Hh, Wh = _host_i32([f.shape[2] for f in feats]), _host_i32([f.shape[3] for f in feats])
-    return bool(lib.frcnn_conv3x3_f32_supported(_np_ptr(Hh), _np_ptr(Wh), len(feats), C_, C_, 1))
+    return bool(lib.frcnn_conv3x3_f32_supported(*_level_sizes(_sizes_of(feats)), C_, C_, 1))
 
 
 def rpn_conv3x3(feats, w3):
@@ -1089,32 +1114,6 @@ def rpn_conv3x3(feats, w3):
 
 
 # ---- the same stage for the backbone's 3x3 convolutions (Cin != Cout, bias + ReLU in the output transform, ReLU's backward in the input transforms)
-def _conv3x3_call(fn, what, H, W, n, Cin, Cout, dev, args_of, mask=False, bias=False, cached=False, relu_bits=False, pooled=False, urot=False, trace=True):
-    if trace:
-        _conv_trace(what, Cin, Cout, H, W, mask, bias, cached, relu_bits, pooled, urot)
-    Hh, Wh = _host_i32(H), _host_i32(W)
-    nb = int(lib.frcnn_conv3x3_f32_workspace(_np_ptr(Hh), _np_ptr(Wh), n, Cin, Cout))
-    if nb == 0:
-        raise _lib.FrcnnError("%s: Cin = %d / Cout = %d is outside what the fp32 conv stage is built for (multiples of 32)" % (what, Cin, Cout))
-    ws = _ctrl_workspace(dev, "rpn_conv_f32", nb)     # ONE block for every fp32 3x3 of the step, sized by the largest layer seen
-    with torch.cuda.device(dev):
-        check(fn(*args_of(_np_ptr(Hh), _np_ptr(Wh), _ptr(ws), ws.numel(), _stream())), what)
-
-
-def _ptr_list(ts):
-    return (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-
-
-def _conv3x3_levels(ts, Cc, name):
-    ts = [_req(t, torch.float32, name) for t in ts]
-    if not ts:
-        raise ValueError("conv3x3: no level")
-    for t in ts:
-        if t.dim() != 4 or t.shape[0] != 1 or t.shape[1] != Cc:
-            raise ValueError("conv3x3: every %s level must be [1,%d,h,w] (batch 1 per GPU)" % (name, Cc))
-    return ts
-
-
 def conv3x3_fwd(xs, w, bias=None, relu=False, keep_transformed=False, want_bits=False, pool=False, u_rotated=None):
     """y_l = act(bias + conv3x3(x_l, w)), padding 1, for a list of fp32 levels [1,Cin,h,w] sharing w [Cout,Cin,3,3] (frcnn_conv3x3_f32_fwd).
     keep_transformed: also return the transformed activations (a flat fp32 tensor) for conv3x3_wgrad(..., x_transformed=).
@@ -1136,29 +1135,28 @@ def conv3x3_fwd(xs, w, bias=None, relu=False, keep_transformed=False, want_bits=
     ys = [torch.empty((1, Cout, x.shape[2] // 2, x.shape[3] // 2) if pool else (1, Cout, x.shape[2], x.shape[3]), dtype=torch.float32, device=x.device) for x in xs]
     xp, yp = _ptr_list(xs), _ptr_list(ys)
     xt = bits = None
-    Hh, Wh = _host_i32([x.shape[2] for x in xs]), _host_i32([x.shape[3] for x in xs])
+    hw = _sizes_of(xs)
+    sizes = _level_sizes(hw)
     if keep_transformed:
-        xt = torch.empty((int(lib.frcnn_conv3x3_f32_xt_floats(_np_ptr(Hh), _np_ptr(Wh), len(xs), Cin)),), dtype=torch.float32, device=xs[0].device)
+        xt = torch.empty((int(lib.frcnn_conv3x3_f32_xt_floats(*sizes, Cin)),), dtype=torch.float32, device=xs[0].device)
     if want_bits:
         if not relu:
             raise ValueError("conv3x3_fwd: want_bits needs relu=True")
-        bits = torch.empty((int(lib.frcnn_conv3x3_f32_relu_bits_words(_np_ptr(Hh), _np_ptr(Wh), len(xs), Cout)),), dtype=torch.int16, device=xs[0].device)
-    _conv3x3_call(lib.frcnn_conv3x3_f32_fwd, "conv3x3_f32_fwd", [x.shape[2] for x in xs], [x.shape[3] for x in xs], len(xs), Cin, Cout, xs[0].device,
-                  lambda H, W, ws, nws, st: (xp, yp, H, W, len(xs), Cin, Cout, _ptr(w), _ptr(bias), (2 if pool else 1) if relu else 0, _ptr(bits), _ptr(xt), _ptr(u_rotated), ws, nws, st),
+        bits = torch.empty((int(lib.frcnn_conv3x3_f32_relu_bits_words(*sizes, Cout)),), dtype=torch.int16, device=xs[0].device)
+    _conv3x3_call(lib.frcnn_conv3x3_f32_fwd, "conv3x3_f32_fwd", hw, Cin, Cout, xs[0].device,
+                  lambda H, W, n, ws, nws, st: (xp, yp, H, W, n, Cin, Cout, _ptr(w), _ptr(bias), (2 if pool else 1) if relu else 0, _ptr(bits), _ptr(xt), _ptr(u_rotated), ws, nws, st),
                   bias=bias is not None, relu_bits=bits is not None, pooled=bool(pool), urot=u_rotated is not None)
     return (ys, xt, bits) if (keep_transformed or want_bits) else ys
 
 
 def conv3x3_dy_buffer(hw, Cout, device):
     """An uninitialised buffer for the weight-gradient transform of an output gradient over maps of sizes hw = [(h, w), ...] (the convolution's own sizes)."""
-    Hh, Wh = _host_i32([h for h, _ in hw]), _host_i32([w_ for _, w_ in hw])
-    return torch.empty((int(lib.frcnn_conv3x3_f32_xt_floats(_np_ptr(Hh), _np_ptr(Wh), len(hw), int(Cout))),), dtype=torch.float32, device=device)
+    return torch.empty((int(lib.frcnn_conv3x3_f32_xt_floats(*_level_sizes(hw), int(Cout))),), dtype=torch.float32, device=device)
 
 
 def conv3x3_u_buffer(xs, w):
     """An uninitialised buffer for the rotated weight transform of these levels (frcnn_conv3x3_f32_u_floats)."""
-    Hh, Wh = _host_i32([x.shape[2] for x in xs]), _host_i32([x.shape[3] for x in xs])
-    n = int(lib.frcnn_conv3x3_f32_u_floats(_np_ptr(Hh), _np_ptr(Wh), len(xs), int(w.shape[1]), int(w.shape[0])))
+    n = int(lib.frcnn_conv3x3_f32_u_floats(*_level_sizes(_sizes_of(xs)), int(w.shape[1]), int(w.shape[0])))
     return torch.empty((n,), dtype=torch.float32, device=w.device)
 
 
@@ -1174,9 +1172,9 @@ def conv3x3_bwd_data(dys, w, relu_bits=None, pooled_from=None, u_rotated=None, d
     relu_bits = _conv3x3_bits(relu_bits, hw, Cout)
     dxs = [torch.empty((1, Cin, h, w_), dtype=torch.float32, device=d.device) for d, (h, w_) in zip(dys, hw)]
     gp, xp = _ptr_list(dys), _ptr_list(dxs)
-    _conv3x3_call(lib.frcnn_conv3x3_f32_bwd_data, "conv3x3_f32_bwd_data", [h for h, _ in hw], [w_ for _, w_ in hw], len(dys), Cin, Cout,
-                  dys[0].device, lambda H, W, ws, nws, st: (gp, _ptr(relu_bits), xp, H, W, len(dys), Cin, Cout, _ptr(w), _ptr(u_rotated), 1 if pooled_from else 0, _ptr(dy_transformed),
-                                            1 if want_bias_partials else 0, ws, nws, st),
+    _conv3x3_call(lib.frcnn_conv3x3_f32_bwd_data, "conv3x3_f32_bwd_data", hw, Cin, Cout, dys[0].device,
+                  lambda H, W, n, ws, nws, st: (gp, _ptr(relu_bits), xp, H, W, n, Cin, Cout, _ptr(w), _ptr(u_rotated), 1 if pooled_from else 0, _ptr(dy_transformed),
+                                               1 if want_bias_partials else 0, ws, nws, st),
                   mask=relu_bits is not None, pooled=bool(pooled_from), urot=u_rotated is not None, cached=dy_transformed is not None)
     return dxs
 
@@ -1184,7 +1182,7 @@ def conv3x3_bwd_data(dys, w, relu_bits=None, pooled_from=None, u_rotated=None, d
 def _conv3x3_full_sizes(dys, pooled_from):
     """The convolution's own output sizes: those of dys, or -- for a pooled gradient -- the ones given (checked against dys)."""
     if not pooled_from:
-        return [(int(d.shape[2]), int(d.shape[3])) for d in dys]
+        return _sizes_of(dys)
     hw = [(int(h), int(w_)) for h, w_ in pooled_from]
     if len(hw) != len(dys) or any((h // 2, w_ // 2) != (int(d.shape[2]), int(d.shape[3])) for d, (h, w_) in zip(dys, hw)):
         raise ValueError("conv3x3: pooled gradient shapes do not match pooled_from")
@@ -1195,8 +1193,7 @@ def _conv3x3_bits(relu_bits, hw, Cout):
     if relu_bits is None:
         return None
     relu_bits = _req(relu_bits, torch.int16, "relu_bits")
-    Hh, Wh = _host_i32([h for h, _ in hw]), _host_i32([w_ for _, w_ in hw])
-    if relu_bits.numel() != int(lib.frcnn_conv3x3_f32_relu_bits_words(_np_ptr(Hh), _np_ptr(Wh), len(hw), Cout)):
+    if relu_bits.numel() != int(lib.frcnn_conv3x3_f32_relu_bits_words(*_level_sizes(hw), Cout)):
         raise ValueError("conv3x3: relu_bits does not belong to these shapes")
     return relu_bits
 
@@ -1209,14 +1206,14 @@ def conv3x3_wgrad(xs, dys, relu_bits=None, want_bias=False, x_transformed=None, 
     dys = _conv3x3_levels(dys, Cout, "d_out")
     if len(xs) != len(dys) or any(((a.shape[2] // 2, a.shape[3] // 2) if pooled else tuple(a.shape[2:])) != tuple(b.shape[2:]) for a, b in zip(xs, dys)):
         raise ValueError("conv3x3_wgrad: inputs and d_out differ in shape")
-    relu_bits = _conv3x3_bits(relu_bits, [(int(x.shape[2]), int(x.shape[3])) for x in xs], Cout)
+    relu_bits = _conv3x3_bits(relu_bits, _sizes_of(xs), Cout)
     dev = xs[0].device
     dw = torch.empty((Cout, Cin, 3, 3), dtype=torch.float32, device=dev)
     db = torch.empty((Cout,), dtype=torch.float32, device=dev) if want_bias else None
     xp, gp = _ptr_list(xs), _ptr_list(dys)
-    _conv3x3_call(lib.frcnn_conv3x3_f32_wgrad, "conv3x3_f32_wgrad", [x.shape[2] for x in xs], [x.shape[3] for x in xs], len(xs), Cin, Cout, dev,
-                  lambda H, W, ws, nws, st: (xp, gp, _ptr(relu_bits), H, W, len(xs), Cin, Cout, _ptr(dw), _ptr(db), _ptr(x_transformed), 1 if pooled else 0, _ptr(dy_transformed),
-                                            ws, nws, st),
+    _conv3x3_call(lib.frcnn_conv3x3_f32_wgrad, "conv3x3_f32_wgrad", _sizes_of(xs), Cin, Cout, dev,
+                  lambda H, W, n, ws, nws, st: (xp, gp, _ptr(relu_bits), H, W, n, Cin, Cout, _ptr(dw), _ptr(db), _ptr(x_transformed), 1 if pooled else 0, _ptr(dy_transformed),
+                                               ws, nws, st),
                   mask=relu_bits is not None, bias=want_bias, cached=x_transformed is not None, pooled=pooled, urot=dy_transformed is not None)
     return dw, db
 
@@ -1230,9 +1227,8 @@ def conv3x3_bwd(dys, w, x_transformed, relu_bits=None, pooled_from=None, u_rotat
     hw = _conv3x3_full_sizes(dys, pooled_from)
     relu_bits = _conv3x3_bits(relu_bits, hw, Cout)
     dev = dys[0].device
-    H, W = [h for h, _ in hw], [w_ for _, w_ in hw]
     x_transformed = _req(x_transformed, torch.float32, "x_transformed")
-    if x_transformed.numel() != int(lib.frcnn_conv3x3_f32_xt_floats(_np_ptr(_host_i32(H)), _np_ptr(_host_i32(W)), len(hw), Cin)):
+    if x_transformed.numel() != int(lib.frcnn_conv3x3_f32_xt_floats(*_level_sizes(hw), Cin)):
         raise ValueError("conv3x3_bwd: x_transformed does not belong to these shapes")
     dxs = [torch.empty((1, Cin, h, w_), dtype=torch.float32, device=dev) for h, w_ in hw]
     dyt = conv3x3_dy_buffer(hw, Cout, dev)
@@ -1240,11 +1236,11 @@ def conv3x3_bwd(dys, w, x_transformed, relu_bits=None, pooled_from=None, u_rotat
     db = torch.empty((Cout,), dtype=torch.float32, device=dev) if want_bias else None
     gp, xp = _ptr_list(dys), _ptr_list(dxs)
     # the trace keeps the two calls this one stands for (bench.py prices the stage's work from them)
-    _conv_trace("conv3x3_f32_bwd_data", Cin, Cout, H, W, relu_bits is not None, False, True, False, bool(pooled_from), u_rotated is not None)
-    _conv3x3_call(lib.frcnn_conv3x3_f32_bwd, "conv3x3_f32_bwd", H, W, len(dys), Cin, Cout, dev,
-                  lambda Hp, Wp, ws, nws, st: (gp, _ptr(relu_bits), xp, Hp, Wp, len(dys), Cin, Cout, _ptr(w), _ptr(u_rotated), 1 if pooled_from else 0, _ptr(x_transformed),
+    _conv_trace("conv3x3_f32_bwd_data", Cin, Cout, hw, relu_bits is not None, False, True, False, bool(pooled_from), u_rotated is not None)
+    _conv3x3_call(lib.frcnn_conv3x3_f32_bwd, "conv3x3_f32_bwd", hw, Cin, Cout, dev,
+                  lambda H, W, n, ws, nws, st: (gp, _ptr(relu_bits), xp, H, W, n, Cin, Cout, _ptr(w), _ptr(u_rotated), 1 if pooled_from else 0, _ptr(x_transformed),
                                                _ptr(dyt), _ptr(dw), _ptr(db), ws, nws, st), trace=False)
-    _conv_trace("conv3x3_f32_wgrad", Cin, Cout, H, W, relu_bits is not None, want_bias, True, False, bool(pooled_from), True)
+    _conv_trace("conv3x3_f32_wgrad", Cin, Cout, hw, relu_bits is not None, want_bias, True, False, bool(pooled_from), True)
     return dxs, dw, db
 
 
@@ -1263,8 +1259,7 @@ def conv3x3_supported(x, weight, need_input_grad=None):
     if tuple(weight.shape[2:]) != (3, 3) or Cout % 64 != 0 or Cin % 32 != 0 or Cin * Cout * x.shape[2] * x.shape[3] < CONV3X3_MIN_WORK:
         return False
     grads = torch.is_grad_enabled() and (weight.requires_grad or (x.requires_grad if need_input_grad is None else need_input_grad))
-    Hh, Wh = _host_i32([x.shape[2]]), _host_i32([x.shape[3]])
-    return bool(lib.frcnn_conv3x3_f32_supported(_np_ptr(Hh), _np_ptr(Wh), 1, Cin, Cout, 1 if grads else 0))       # channel multiples and the control block's limits
+    return bool(lib.frcnn_conv3x3_f32_supported(*_level_sizes(_sizes_of([x])), Cin, Cout, 1 if grads else 0))       # channel multiples and the control block's limits
 
 
 CONV3X3_SCHEDULES = ("stream_k", "whole_ranges", "one_tile", "fused_out64")       # FRCNN_CONV_SCHED_*
@@ -1277,14 +1272,14 @@ def conv3x3_plan(shapes, Cin, Cout, device=None):
     available), fwd / bwd_data / wgrad = None where the call does not take the shapes, else a dict tile_h, tile_w, m_tiles, t_tiles, Kc, n_tiles, units, G,
     schedule (one of CONV3X3_SCHEDULES), and strips_in / strips_out (the transform launches over Cin / Cout channels) = a dict per_block, n_strips, levels =
     [dict segments, rows, last_strip_rows (0: full), last_segment_tiles (0: full)]."""
-    Hh, Wh = _host_i32([h for h, _ in shapes]), _host_i32([w_ for _, w_ in shapes])
-    HEAD, PROD, STRIPS, n = 8, 10, 2 + 4 * 8, len(shapes)
+    Hp, Wp, n = _level_sizes(shapes)
+    HEAD, PROD, STRIPS = 8, 10, 2 + 4 * 8
     out = np.zeros(HEAD + 3 * PROD + 2 * STRIPS, dtype=np.int32)
     if device is not None and torch.device(device).type == "cuda":
         with torch.cuda.device(device):
-            check(lib.frcnn_conv3x3_f32_plan(_np_ptr(Hh), _np_ptr(Wh), n, int(Cin), int(Cout), _np_ptr(out), out.size), "conv3x3_f32_plan")
+            check(lib.frcnn_conv3x3_f32_plan(Hp, Wp, n, int(Cin), int(Cout), _np_ptr(out), out.size), "conv3x3_f32_plan")
     else:
-        check(lib.frcnn_conv3x3_f32_plan(_np_ptr(Hh), _np_ptr(Wh), n, int(Cin), int(Cout), _np_ptr(out), out.size), "conv3x3_f32_plan")
+        check(lib.frcnn_conv3x3_f32_plan(Hp, Wp, n, int(Cin), int(Cout), _np_ptr(out), out.size), "conv3x3_f32_plan")
     v = [int(t) for t in out]
     plan = {"tile": v[0], "tg": v[1], "padded_tiles": v[2], "G": v[4], "G_wgrad": v[5], "pool": bool(v[6])}
     for k, name in enumerate(("fwd", "bwd_data", "wgrad")):
@@ -1351,8 +1346,7 @@ def conv3x3(x, weight, bias=None, relu=False, pool=False):
 
 def conv3x3_pool_supported(x):
     """Whether conv3x3(..., pool=True) can take a map of x's size: the fused max-pool lives in the 4 x 4 tile's output transform."""
-    Hh, Wh = _host_i32([x.shape[2]]), _host_i32([x.shape[3]])
-    return int(lib.frcnn_conv3x3_f32_tile_size(_np_ptr(Hh), _np_ptr(Wh), 1)) == 4
+    return int(lib.frcnn_conv3x3_f32_tile_size(*_level_sizes(_sizes_of([x])))) == 4
 
 
 # ---- 1 x 1 convolutions: torch's forward and input gradient, the weight gradient on the conv stage's k-contiguous GEMM (no NHWC transposes)
