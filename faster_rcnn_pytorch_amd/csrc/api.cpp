@@ -1,6 +1,7 @@
 // api.cpp -- host-only part of libfrcnn_hip.so: status strings, workspace sizing,
 // host-side anchor bases, and the per-kernel HIP-event timing facility.
 #include "frcnn_common.h"
+#include "frcnn_host.h"
 #include "frcnn_layout.h"
 #include <cmath>
 #include <cstdarg>
@@ -49,24 +50,7 @@ FRCNN_EXPORT uint64_t frcnn_layout_stamp(void) { return frcnn_layout_stamp_value
 FRCNN_EXPORT int frcnn_abi_version(void) { const int rc = frcnn_layout_check_impl(); return rc ? rc : FRCNN_ABI_VERSION; }
 FRCNN_EXPORT const char *frcnn_last_error(void) { return g_err; }
 
-// ---- workspace layout sizes (must agree with the carving in topk.hip / nms.hip / targets.hip / detect.hip / eval.hip / coco_eval.hip / coco_eval_pooled.hip / eval_merge.hip / detect_merge.hip, which detect_soft.hip shares) ----
-size_t frcnn_ws_topk(int64_t N);
-size_t frcnn_ws_nms(int64_t K);
-size_t frcnn_ws_rpn_targets(int64_t N, int64_t G);
-size_t frcnn_ws_head_targets(int64_t n);
-size_t frcnn_ws_region_proposal(int64_t N, int64_t K, int64_t P);
-size_t frcnn_ws_preprocess(int64_t in_hw, int64_t out_hw);
-size_t frcnn_ws_head_bwd(int64_t C);
-size_t frcnn_ws_rpn_conv(void);
-size_t frcnn_ws_rpn_conv_wgrad(void);
-size_t frcnn_ws_rpn_conv_f32(int64_t C);
-size_t frcnn_ws_detect(int64_t P, int64_t C);
-size_t frcnn_ws_eval(int64_t D, int64_t G);
-size_t frcnn_ws_coco_eval(int64_t D, int64_t G);
-size_t frcnn_ws_eval_merge(int64_t n1, int64_t n2);
-size_t frcnn_ws_coco_eval_pooled(int64_t D, int64_t G);
-size_t frcnn_ws_detect_merge(int64_t out_capacity, int64_t C);
-
+// ---- workspace sizes: every op's layout function answers for its own (declared in frcnn_host.h) ----
 FRCNN_EXPORT size_t frcnn_workspace_bytes(int op, int64_t n1, int64_t n2)
 {
     if (n1 < 0 || n2 < 0) return 0;
@@ -89,6 +73,30 @@ FRCNN_EXPORT size_t frcnn_workspace_bytes(int op, int64_t n1, int64_t n2)
     case FRCNN_OP_DETECT_MERGE: return frcnn_ws_detect_merge(n1, n2);
     default: return 0;
     }
+}
+
+// ---- the current device: CU count and LDS opt-in (frcnn_host.h) ----
+int frcnn_cu_count()
+{
+    static std::atomic<int> per_dev[64];                             // 0 = not asked yet; per device: one process may drive several
+    int dev = -1, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0) return 0;
+    if (dev < 64 && (n = per_dev[dev].load(std::memory_order_relaxed)) > 0) return n;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) return 0;
+    if (dev < 64) per_dev[dev].store(n, std::memory_order_relaxed);
+    return n;
+}
+
+int frcnn_reserve_lds(const void *kernel, size_t bytes, const char *who, std::atomic<unsigned char> *done)
+{
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0) return frcnn_set_error(FRCNN_ERR_LAUNCH, "%s: no current device", who);
+    if (dev >= 64 || !done[dev].load(std::memory_order_acquire)) {
+        const hipError_t rc = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        if (rc != hipSuccess) return frcnn_set_error(FRCNN_ERR_LAUNCH, "%s: cannot reserve %zu bytes of LDS: %s", who, bytes, hipGetErrorString(rc));
+        if (dev < 64) done[dev].store(1, std::memory_order_release);
+    }
+    return FRCNN_OK;
 }
 
 // ---- A1: FRCNNAnchorMaker.generate_anchor_base (anchor.py:15-32): float64 math, float32 store ----

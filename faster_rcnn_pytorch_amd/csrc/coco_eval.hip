@@ -38,11 +38,18 @@ FRCNN_LAYOUT_STAMP(coco_eval);
 #define COCO_CROWD_BIT 4               // s_gflag: bits 0 .. 3 = ignored in area range a, bit 4 = crowd
 
 // workspace: the packed keys of the frame's detections, one segment per category (any content; nothing must be zero)
-size_t frcnn_ws_coco_eval(int64_t D, int64_t G)
+struct CocoWs { u64 *keys; size_t total; };
+
+static CocoWs coco_ws_layout(int64_t D, void *workspace)
 {
-    if (!eval_supported(D, G)) return 0;
-    return 256 + align_up((size_t)D * sizeof(u64), 256);        // + the slack that aligns the caller's pointer
+    CocoWs w;
+    WsCarver c = WsCarver::any_base(workspace);
+    w.keys = c.get<u64>((size_t)D);
+    w.total = c.bytes();
+    return w;
 }
+
+size_t frcnn_ws_coco_eval(int64_t D, int64_t G) { return eval_supported(D, G) ? coco_ws_layout(D, nullptr).total : 0; }
 
 __device__ __forceinline__ bool coco_outside(double area, int a)
 {
@@ -374,13 +381,12 @@ FRCNN_EXPORT int frcnn_coco_eval_update(const float *boxes, const int32_t *label
     FRCNN_REQUIRE(record_capacity >= 1, "coco_eval_update: record_capacity must be >= 1");
     FRCNN_REQUIRE(((uintptr_t)boxes & 15) == 0 && ((uintptr_t)gt_boxes & 7) == 0 && ((uintptr_t)gt_area & 7) == 0,
                   "coco_eval_update: boxes must be 16-byte aligned, gt_boxes and gt_area 8-byte aligned");
-    const size_t need = frcnn_ws_coco_eval(det_capacity, gt_capacity);
-    if (workspace_bytes < need) return frcnn_set_error(FRCNN_ERR_WORKSPACE, "coco_eval_update: workspace %zu < %zu bytes", workspace_bytes, need);
-    u64 *keys = (u64 *)eval_ws_base(workspace);
+    const CocoWs w = coco_ws_layout(det_capacity, workspace);
+    FRCNN_REQUIRE_WS("coco_eval_update", workspace_bytes, w.total);
     hipStream_t s = (hipStream_t)stream;
     FRCNN_LAUNCH(coco_update_kernel, dim3((unsigned)(C - 1)), dim3(EVAL_THREADS), 0, s, (const float4 *)boxes, labels, scores, count_dev,
                  (int)det_capacity, gt_boxes, gt_area, gt_labels, gt_iscrowd, n_gt_dev, (int)gt_capacity, frame_dev, thresholds_dev, T, max_det,
-                 (u64 *)npig, rec_score, rec_label, rec_image, rec_rank, rec_flags, (long long)record_capacity, (u64 *)cursor, error_word, keys);
+                 (u64 *)npig, rec_score, rec_label, rec_image, rec_rank, rec_flags, (long long)record_capacity, (u64 *)cursor, error_word, w.keys);
     FRCNN_CHECK_LAUNCH("coco_update_kernel");
     return FRCNN_OK;
 }
@@ -397,10 +403,9 @@ FRCNN_EXPORT int frcnn_coco_eval_accumulate(const int32_t *labels_sorted, const 
                   "coco_eval_accumulate: NULL pointer");
     FRCNN_REQUIRE(capacity >= 1, "coco_eval_accumulate: capacity must be >= 1");
     FRCNN_REQUIRE(max_det_0 >= 1 && max_det_1 >= 1 && max_det_2 >= 1, "coco_eval_accumulate: maxDets must be >= 1");
-    const size_t need = 256 + (size_t)COCO_A * (size_t)capacity * sizeof(double);
-    if (workspace_bytes < need)
-        return frcnn_set_error(FRCNN_ERR_WORKSPACE, "coco_eval_accumulate: workspace %zu < %zu bytes", workspace_bytes, need);
-    double *pw = (double *)eval_ws_base(workspace);
+    WsCarver c = WsCarver::any_base(workspace);
+    double *pw = (double *)c.here();                            // one piece, sized to the byte (not rounded up to the carver's 256)
+    FRCNN_REQUIRE_WS("coco_eval_accumulate", workspace_bytes, c.bytes() + (size_t)COCO_A * (size_t)capacity * sizeof(double));
     hipStream_t s = (hipStream_t)stream;
     FRCNN_LAUNCH(coco_accumulate_kernel, dim3((unsigned)((C - 1) * COCO_A)), dim3(EVAL_THREADS), 0, s, labels_sorted, ranks_sorted, flags_sorted,
                  (const u64 *)n_dev, (long long)capacity, (const u64 *)npig, rec_thresholds_dev, R, T, C - 1, max_det_0, max_det_1, max_det_2,

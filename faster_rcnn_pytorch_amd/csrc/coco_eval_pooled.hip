@@ -37,7 +37,7 @@ FRCNN_LAYOUT_STAMP(coco_eval_pooled);
 #define POOL_F_IGNORED 1u               // a chain's ground-truth flags
 #define POOL_F_CROWD 2u
 
-// the carving of the workspace behind its 256-byte aligned base
+// the carving of the workspace behind its 256-byte aligned base, as the kernels address it (pool_ws_layout is the host's side of it)
 #define POOL_OFF_GPERM 256                                                     // int32 [EVAL_MAX_G]: pooled index -> original position
 #define POOL_OFF_DOUT (POOL_OFF_GPERM + EVAL_MAX_G * 4)                        // u8 [EVAL_MAX_P]: bit a = the detection's area lies outside range a
 #define POOL_OFF_DET (POOL_OFF_DOUT + EVAL_MAX_P)                              // double [5][EVAL_MAX_P]: x, y, x + w, y + h, w * h by rank
@@ -51,11 +51,21 @@ struct PoolHeader {                     // written by the rank kernel, read by e
     u64 base;                           // the frame's first record slot
 };
 
-size_t frcnn_ws_coco_eval_pooled(int64_t D, int64_t G)
+struct PoolWs { char *base; size_t total; };
+
+// The fixed pieces (header | gperm | dout | det) are ONE piece of the carver, POOL_OFF_KEYS bytes: the keys behind it then lie where
+// the kernels' POOL_OFF_KEYS says (a multiple of 256, asserted above), and the size cannot move away from the offsets.
+static PoolWs pool_ws_layout(int64_t D, void *workspace)
 {
-    if (!eval_supported(D, G)) return 0;
-    return 256 + POOL_OFF_KEYS + align_up((size_t)D * sizeof(u64), 256);       // + the slack that aligns the caller's pointer
+    PoolWs w;
+    WsCarver c = WsCarver::any_base(workspace);
+    w.base = (char *)c.take(POOL_OFF_KEYS);
+    c.get<u64>((size_t)D);
+    w.total = c.bytes();
+    return w;
 }
+
+size_t frcnn_ws_coco_eval_pooled(int64_t D, int64_t G) { return eval_supported(D, G) ? pool_ws_layout(D, nullptr).total : 0; }
 
 __device__ __forceinline__ bool pool_outside(double area, int a)
 {
@@ -379,10 +389,9 @@ FRCNN_EXPORT int frcnn_coco_eval_update_pooled(const float *boxes, const int32_t
     FRCNN_REQUIRE(record_capacity >= 1, "coco_eval_update_pooled: record_capacity must be >= 1");
     FRCNN_REQUIRE(((uintptr_t)boxes & 15) == 0 && ((uintptr_t)gt_boxes & 7) == 0 && ((uintptr_t)gt_area & 7) == 0,
                   "coco_eval_update_pooled: boxes must be 16-byte aligned, gt_boxes and gt_area 8-byte aligned");
-    const size_t need = frcnn_ws_coco_eval_pooled(det_capacity, gt_capacity);
-    if (workspace_bytes < need)
-        return frcnn_set_error(FRCNN_ERR_WORKSPACE, "coco_eval_update_pooled: workspace %zu < %zu bytes", workspace_bytes, need);
-    char *ws = eval_ws_base(workspace);
+    const PoolWs w = pool_ws_layout(det_capacity, workspace);
+    FRCNN_REQUIRE_WS("coco_eval_update_pooled", workspace_bytes, w.total);
+    char *ws = w.base;
     hipStream_t s = (hipStream_t)stream;
     FRCNN_LAUNCH(coco_pooled_rank_kernel, dim3(1), dim3(EVAL_THREADS), 0, s, (const float4 *)boxes, labels, scores, count_dev, (int)det_capacity,
                  gt_area, gt_labels, gt_iscrowd, n_gt_dev, (int)gt_capacity, frame_dev, C - 1, max_det, (u64 *)npig, rec_score, rec_label, rec_image,

@@ -239,14 +239,12 @@ FRCNN_EXPORT int frcnn_conv3x3_c3_wgrad(const float *x_dev, const float *dy_dev,
     FRCNN_REQUIRE(dw_dev && workspace, "conv3x3_c3_wgrad: NULL pointer");
     if (Cout % 4 != 0 || W > 1700)      // LDS: 3 (rows + 2)(W + 2) floats
         return frcnn_set_error(FRCNN_ERR_UNSUPPORTED, "conv3x3_c3_wgrad: Cout = %d must be a multiple of 4 and W = %d at most 1700", Cout, W);
-    if (workspace_bytes < frcnn_conv3x3_c3_wgrad_workspace(H, Cout))
-        return frcnn_set_error(FRCNN_ERR_WORKSPACE, "conv3x3_c3_wgrad: workspace %zu < %zu bytes", workspace_bytes, frcnn_conv3x3_c3_wgrad_workspace(H, Cout));
+    FRCNN_REQUIRE_WS("conv3x3_c3_wgrad", workspace_bytes, frcnn_conv3x3_c3_wgrad_workspace(H, Cout));
     hipStream_t s = (hipStream_t)stream;
     float *part = (float *)workspace;
     // rows per block: the fewest that keep the launch within one block per CU (one round), as far as the window fits the LDS
     const int groups = (Cout + C3_CPW * C3_WAVES - 1) / (C3_CPW * C3_WAVES);
-    int cus = 256, dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const int cus = frcnn_cu_count_or(256);
     const int fit = (int)((150 * 1024) / (12 * (size_t)(W + 2))) - 2;
     const int rows = std::max(1, std::min(fit, (int)(((long long)H * groups + cus - 1) / cus)));
     const int nb = (H + rows - 1) / rows;

@@ -130,12 +130,12 @@ static bool crop_shapes_ok(int h, int w, int H1, int W1, int ch, int cw)
 
 static size_t crop_ws_layout(void *base, CropImg *d)
 {
-    InCarver c = {(char *)base, 0};
+    WsCarver c(base);
     d->rows_cap = crop_rows_cap(d->h, d->H1, d->ch);
     d->x = rs_axis_take(c, d->w, d->W1, d->cw);
     d->y = rs_axis_take(c, d->h, d->H1, d->ch);
     d->tmp = c.get<uint8_t>((size_t)d->rows_cap * d->cw * 3);
-    return c.o;
+    return c.bytes();
 }
 
 FRCNN_EXPORT size_t frcnn_resize_crop_workspace(int h, int w, int H1, int W1, int ch, int cw)

@@ -30,28 +30,22 @@ typedef det_u64 u64;
 static bool det_supported(int64_t P, int64_t C) { return P >= 1 && P <= DET_MAX_P && C >= 2 && C <= DET_MAX_C; }
 
 // workspace: boxes [C-1][P] float4 | scores [C-1][P] f32 | kept rows [C-1][P] i32 | counts [C-1] i32, each 256-byte aligned
-struct DetWs { float4 *box; float *score; int32_t *kept; int32_t *cnt; };
+struct DetWs { float4 *box; float *score; int32_t *kept; int32_t *cnt; size_t total; };
 
-static size_t det_ws_layout(int64_t P, int64_t C, char *base, DetWs *w)
+static DetWs det_ws_layout(int64_t P, int64_t C, void *workspace)
 {
     const size_t n = (size_t)(C - 1) * (size_t)P;
-    size_t off = 0;
-    if (w) w->box = (float4 *)(base + off);
-    off += align_up(n * sizeof(float4), 256);
-    if (w) w->score = (float *)(base + off);
-    off += align_up(n * sizeof(float), 256);
-    if (w) w->kept = (int32_t *)(base + off);
-    off += align_up(n * sizeof(int32_t), 256);
-    if (w) w->cnt = (int32_t *)(base + off);
-    off += align_up((size_t)(C - 1) * sizeof(int32_t), 256);
-    return off;
+    DetWs w;
+    WsCarver c = WsCarver::any_base(workspace);
+    w.box = c.get<float4>(n);
+    w.score = c.get<float>(n);
+    w.kept = c.get<int32_t>(n);
+    w.cnt = c.get<int32_t>((size_t)(C - 1));
+    w.total = c.bytes();
+    return w;
 }
 
-size_t frcnn_ws_detect(int64_t P, int64_t C)
-{
-    if (!det_supported(P, C)) return 0;
-    return 256 + det_ws_layout(P, C, nullptr, nullptr);          // + the slack that aligns the caller's pointer
-}
+size_t frcnn_ws_detect(int64_t P, int64_t C) { return det_supported(P, C) ? det_ws_layout(P, C, nullptr).total : 0; }
 
 __global__ __launch_bounds__(DET_THREADS) void detect_decode_kernel(const float *__restrict__ head_cls, const float *__restrict__ head_reg,
                                                                     const float *__restrict__ rois, int P, int C, float4 *__restrict__ ws_box,
@@ -199,11 +193,8 @@ FRCNN_EXPORT int frcnn_detect_postprocess(const float *head_cls, const float *he
     FRCNN_REQUIRE(head_cls && head_reg && rois && n_rois_dev && out_boxes && out_labels && out_scores && out_count && workspace,
                   "detect_postprocess: NULL pointer");
     FRCNN_REQUIRE(((uintptr_t)out_boxes & 15) == 0, "detect_postprocess: out_boxes must be 16-byte aligned");
-    const size_t need = frcnn_ws_detect(P, C);
-    if (workspace_bytes < need) return frcnn_set_error(FRCNN_ERR_WORKSPACE, "detect_postprocess: workspace %zu < %zu bytes", workspace_bytes, need);
-    DetWs w;
-    char *base = (char *)workspace + (align_up((uintptr_t)workspace, 256) - (uintptr_t)workspace);
-    det_ws_layout(P, C, base, &w);
+    const DetWs w = det_ws_layout(P, C, workspace);
+    FRCNN_REQUIRE_WS("detect_postprocess", workspace_bytes, w.total);
     hipStream_t s = (hipStream_t)stream;
     const int Pi = (int)P;
     FRCNN_LAUNCH(detect_decode_kernel, dim3((unsigned)((P + DET_THREADS / 64 - 1) / (DET_THREADS / 64))), dim3(DET_THREADS), 0, s, head_cls, head_reg,

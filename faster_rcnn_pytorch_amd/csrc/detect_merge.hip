@@ -33,8 +33,8 @@ FRCNN_LAYOUT_STAMP(detect_merge);
 
 size_t frcnn_ws_detect_merge(int64_t out_capacity, int64_t C)
 {
-    if (!dm_supported(out_capacity, C)) return 0;
-    return 256 + dm_ws_layout(out_capacity, C, nullptr, nullptr);  // + the slack that aligns the caller's pointer
+    DmWs w;
+    return dm_supported(out_capacity, C) ? dm_ws_layout(out_capacity, C, nullptr, &w) : 0;
 }
 
 __global__ __launch_bounds__(DM_THREADS) void detect_merge_class_kernel(const DmArgs a, int C, float min_score, float nms_thr, float vote_thr,
@@ -149,10 +149,7 @@ int dm_prepare(const char *op, int K, const float *const *boxes, const int32_t *
     for (int k = 0; k < K; ++k)
         if (caps[k] > ((int64_t)1 << DM_ROW_BITS))
             return frcnn_set_error(FRCNN_ERR_UNSUPPORTED, "%s: capacity %lld of set %d above 2^%d", op, (long long)caps[k], k, DM_ROW_BITS);
-    const size_t need = frcnn_ws_detect_merge(out_capacity, C);
-    if (workspace_bytes < need) return frcnn_set_error(FRCNN_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", op, workspace_bytes, need);
-    char *base = (char *)workspace + (align_up((uintptr_t)workspace, 256) - (uintptr_t)workspace);
-    dm_ws_layout(out_capacity, C, base, w);
+    FRCNN_REQUIRE_WS(op, workspace_bytes, dm_ws_layout(out_capacity, C, workspace, w));
     *a = DmArgs{};
     for (int k = 0; k < K; ++k) {
         a->boxes[k] = (const float4 *)boxes[k];

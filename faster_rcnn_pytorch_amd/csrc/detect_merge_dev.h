@@ -6,6 +6,7 @@
 #pragma once
 #include "frcnn_common.h"
 #include "frcnn_dev.h"
+#include "frcnn_host.h"
 #include "nms_dev.h"
 #include "detect_dev.h"
 
@@ -34,19 +35,16 @@ static inline int64_t dm_stride(int64_t out_capacity) { return out_capacity < 1 
 // workspace: kept boxes [C-1][stride] float4 | kept scores [C-1][stride] f32 | counts [C-1] i32 | status [C-1] u32, each 256-byte aligned
 struct DmWs { float4 *box; float *score; int32_t *cnt; uint32_t *status; };
 
-static inline size_t dm_ws_layout(int64_t out_capacity, int64_t C, char *base, DmWs *w)
+// returns the bytes (sizeof(DmWs) is part of the layout stamp: the struct holds no total)
+static inline size_t dm_ws_layout(int64_t out_capacity, int64_t C, void *workspace, DmWs *w)
 {
     const size_t n = (size_t)(C - 1) * (size_t)dm_stride(out_capacity);
-    size_t off = 0;
-    if (w) w->box = (float4 *)(base + off);
-    off += align_up(n * sizeof(float4), 256);
-    if (w) w->score = (float *)(base + off);
-    off += align_up(n * sizeof(float), 256);
-    if (w) w->cnt = (int32_t *)(base + off);
-    off += align_up((size_t)(C - 1) * sizeof(int32_t), 256);
-    if (w) w->status = (uint32_t *)(base + off);
-    off += align_up((size_t)(C - 1) * sizeof(uint32_t), 256);
-    return off;
+    WsCarver c = WsCarver::any_base(workspace);
+    w->box = c.get<float4>(n);
+    w->score = c.get<float>(n);
+    w->cnt = c.get<int32_t>((size_t)(C - 1));
+    w->status = c.get<uint32_t>((size_t)(C - 1));
+    return c.bytes();
 }
 
 // detect_merge.hip: frcnn_detect_merge's argument checks under the caller's name `op` (FRCNN_OK, or the error already set), the rows packed

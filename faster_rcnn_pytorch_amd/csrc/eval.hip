@@ -34,27 +34,21 @@ FRCNN_LAYOUT_STAMP(eval);
 
 // workspace: ticket (64 bytes) | winner words [EVAL_MAX_T][G] u64 | match [D] i32 | reach [D] u32, each 256-byte aligned.  The ticket
 // and the winner words must be ZERO before the first call; the kernel leaves them zero.
-struct EvalWs { int32_t *ticket; u64 *win; int32_t *match; uint32_t *reach; };
+struct EvalWs { int32_t *ticket; u64 *win; int32_t *match; uint32_t *reach; size_t total; };
 
-static size_t eval_ws_layout(int64_t D, int64_t G, char *base, EvalWs *w)
+static EvalWs eval_ws_layout(int64_t D, int64_t G, void *workspace)
 {
-    size_t off = 0;
-    if (w) w->ticket = (int32_t *)(base + off);
-    off += 256;
-    if (w) w->win = (u64 *)(base + off);
-    off += align_up((size_t)EVAL_MAX_T * (size_t)G * sizeof(u64), 256);
-    if (w) w->match = (int32_t *)(base + off);
-    off += align_up((size_t)D * sizeof(int32_t), 256);
-    if (w) w->reach = (uint32_t *)(base + off);
-    off += align_up((size_t)D * sizeof(uint32_t), 256);
-    return off;
+    EvalWs w;
+    WsCarver c = WsCarver::any_base(workspace);
+    w.ticket = c.get<int32_t>(16);
+    w.win = c.get<u64>((size_t)EVAL_MAX_T * (size_t)G);
+    w.match = c.get<int32_t>((size_t)D);
+    w.reach = c.get<uint32_t>((size_t)D);
+    w.total = c.bytes();
+    return w;
 }
 
-size_t frcnn_ws_eval(int64_t D, int64_t G)
-{
-    if (!eval_supported(D, G)) return 0;
-    return 256 + eval_ws_layout(D, G, nullptr, nullptr);        // + the slack that aligns the caller's pointer
-}
+size_t frcnn_ws_eval(int64_t D, int64_t G) { return eval_supported(D, G) ? eval_ws_layout(D, G, nullptr).total : 0; }
 
 // Python's max(a, b) / min(a, b): the first argument unless the second is strictly beyond it (a NaN first argument stays)
 __device__ __forceinline__ double py_max(double a, double b) { return b > a ? b : a; }
@@ -249,10 +243,8 @@ FRCNN_EXPORT int frcnn_eval_update(const float *boxes, const int32_t *labels, co
                   "eval_update: NULL pointer");
     FRCNN_REQUIRE(record_capacity >= 1, "eval_update: record_capacity must be >= 1");
     FRCNN_REQUIRE(((uintptr_t)boxes & 15) == 0 && ((uintptr_t)gt_boxes & 15) == 0, "eval_update: boxes and gt_boxes must be 16-byte aligned");
-    const size_t need = frcnn_ws_eval(det_capacity, gt_capacity);
-    if (workspace_bytes < need) return frcnn_set_error(FRCNN_ERR_WORKSPACE, "eval_update: workspace %zu < %zu bytes", workspace_bytes, need);
-    EvalWs w;
-    eval_ws_layout(det_capacity, gt_capacity, eval_ws_base(workspace), &w);
+    const EvalWs w = eval_ws_layout(det_capacity, gt_capacity, workspace);
+    FRCNN_REQUIRE_WS("eval_update", workspace_bytes, w.total);
     int64_t nwg = (det_capacity + EVAL_THREADS - 1) / EVAL_THREADS;
     if (nwg > EVAL_MAX_WG) nwg = EVAL_MAX_WG;
     hipStream_t s = (hipStream_t)stream;
@@ -273,10 +265,9 @@ FRCNN_EXPORT int frcnn_eval_average_precision(const int32_t *labels_sorted, cons
                                EVAL_MAX_T);
     FRCNN_REQUIRE(labels_sorted && flags_sorted && n_dev && npos && ap && tp_total && fp_total && workspace, "eval_average_precision: NULL pointer");
     FRCNN_REQUIRE(capacity >= 1, "eval_average_precision: capacity must be >= 1");
-    const size_t need = 256 + (size_t)capacity * sizeof(double);
-    if (workspace_bytes < need)
-        return frcnn_set_error(FRCNN_ERR_WORKSPACE, "eval_average_precision: workspace %zu < %zu bytes", workspace_bytes, need);
-    double *pw = (double *)eval_ws_base(workspace);
+    WsCarver c = WsCarver::any_base(workspace);
+    double *pw = (double *)c.here();                            // one piece, sized to the byte (not rounded up to the carver's 256)
+    FRCNN_REQUIRE_WS("eval_average_precision", workspace_bytes, c.bytes() + (size_t)capacity * sizeof(double));
     hipStream_t s = (hipStream_t)stream;
     FRCNN_LAUNCH(eval_ap_kernel, dim3((unsigned)(C - 1)), dim3(EVAL_THREADS), 0, s, labels_sorted, flags_sorted, (const u64 *)n_dev,
                  (long long)capacity, (const u64 *)npos, T, ap, (long long *)tp_total, (long long *)fp_total, pw);

@@ -1,10 +1,11 @@
 // eval_dev.h -- what the evaluator translation units (eval.hip: the VOC protocol, coco_eval.hip and coco_eval_pooled.hip: the COCO protocol) share: the bits
-// of the device error word, the kernels' limits, the 256-byte aligned base of a caller's workspace, and on the device the order of fp32
+// of the device error word, the kernels' limits, and on the device the order of fp32
 // scores as unsigned integers, the error bits of a frame's counts, the bisection for a class's segment of the sorted records and the
 // block-wide scan of the packed (tp, fp) counts.  A change to the error word, the limits or the scan is made here, once.
 #pragma once
 #include "frcnn_common.h"
 #include "frcnn_dev.h"
+#include "frcnn_host.h"
 
 // device error word (evaluation.py reports them)
 #define EVAL_ERR_UPSTREAM_ABORT 1      // count < 0: an aborted proposal scan upstream
@@ -23,9 +24,6 @@
 typedef unsigned long long u64;
 
 static inline bool eval_supported(int64_t D, int64_t G) { return D >= 1 && D <= (int64_t)(EVAL_MAX_C - 1) * EVAL_MAX_P && G >= 1 && G <= EVAL_MAX_G; }
-
-// the first 256-byte aligned address of a caller's workspace (every frcnn_ws_* size holds 256 bytes of slack for it)
-static inline char *eval_ws_base(void *workspace) { return (char *)workspace + (align_up((uintptr_t)workspace, 256) - (uintptr_t)workspace); }
 
 #ifdef __HIPCC__
 // monotone in the float's value; -0 folded onto +0 (Python's sort sees them as equal)

@@ -73,32 +73,27 @@ static long long merge_table_slots(int64_t n2)
 }
 
 // n1 = W * SR, n2 = W * SI.  The block-count arrays are sized for the most workgroups W <= 64 shards can need: n / block + 64.
-static size_t merge_ws_layout(int64_t n1, int64_t n2, char *base, MergeWs *w)
+// Returns the bytes; MergeWs itself is a kernel argument and holds no host-side total.
+static size_t merge_ws_layout(int64_t n1, int64_t n2, void *workspace, MergeWs *w)
 {
-    const long long ts = merge_table_slots(n2);
     const long long nb1 = n1 / MERGE_SCAN_BLOCK + MERGE_MAX_W, nb2 = n2 / MERGE_ROW_BLOCK + MERGE_MAX_W;
-    size_t off = 0;
-    if (w) { w->table = (u64 *)(base + off); w->TS = ts; }
-    off += align_up((size_t)ts * sizeof(u64), 256);
-    if (w) w->keep_row = (uint8_t *)(base + off);
-    off += align_up((size_t)n2 + 1, 256);
-    if (w) w->keep_rec = (uint8_t *)(base + off);
-    off += align_up((size_t)n1 + 4, 256);
-    if (w) w->rb = (u64 *)(base + off);
-    off += align_up((size_t)nb1 * sizeof(u64), 256);
-    if (w) w->lb_cnt = (u64 *)(base + off);
-    off += align_up((size_t)nb2 * sizeof(u64), 256);
-    if (w) w->lb_len = (u64 *)(base + off);
-    off += align_up((size_t)nb2 * sizeof(u64), 256);
-    return off;
+    WsCarver c = WsCarver::any_base(workspace);
+    w->TS = merge_table_slots(n2);
+    w->table = c.get<u64>((size_t)w->TS);
+    w->keep_row = c.get<uint8_t>((size_t)n2 + 1);
+    w->keep_rec = c.get<uint8_t>((size_t)n1 + 4);
+    w->rb = c.get<u64>((size_t)nb1);
+    w->lb_cnt = c.get<u64>((size_t)nb2);
+    w->lb_len = c.get<u64>((size_t)nb2);
+    return c.bytes();
 }
 
 static bool merge_supported(int64_t n1, int64_t n2) { return n1 >= 0 && n2 >= 0 && n1 < ((int64_t)1 << 31) - 4096 && n2 < ((int64_t)1 << 30); }
 
 size_t frcnn_ws_eval_merge(int64_t n1, int64_t n2)
 {
-    if (!merge_supported(n1, n2)) return 0;
-    return 256 + merge_ws_layout(n1, n2, nullptr, nullptr);     // + the slack that aligns the caller's pointer
+    MergeWs w;
+    return merge_supported(n1, n2) ? merge_ws_layout(n1, n2, nullptr, &w) : 0;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -510,8 +505,8 @@ FRCNN_EXPORT int frcnn_eval_merge(int W, int64_t shard_record_capacity, int64_t 
     FRCNN_REQUIRE(((uintptr_t)sh_led_range & 7) == 0 && ((uintptr_t)led_range & 7) == 0 && ((uintptr_t)sh_n_records & 7) == 0 &&
                   ((uintptr_t)sh_n_images & 7) == 0 && ((uintptr_t)counter & 7) == 0 && ((uintptr_t)cursor & 7) == 0 && ((uintptr_t)led_count & 7) == 0 &&
                   ((uintptr_t)snap_cursor & 7) == 0 && ((uintptr_t)snap_counter & 7) == 0, "eval_merge: the 64-bit buffers must be 8-byte aligned");
-    const size_t need = frcnn_ws_eval_merge(n1, n2);
-    if (workspace_bytes < need) return frcnn_set_error(FRCNN_ERR_WORKSPACE, "eval_merge: workspace %zu < %zu bytes", workspace_bytes, need);
+    MergeWs ws;
+    FRCNN_REQUIRE_WS("eval_merge", workspace_bytes, merge_ws_layout(n1, n2, workspace, &ws));
     const MergeSpan wsp = {workspace, workspace_bytes};
     const int ns = (int)(sizeof(src) / sizeof(src[0])), nd = (int)(sizeof(dst) / sizeof(dst[0]));
     for (int i = 0; i < nd; ++i) {
@@ -521,8 +516,6 @@ FRCNN_EXPORT int frcnn_eval_merge(int W, int64_t shard_record_capacity, int64_t 
     }
     for (int j = 0; j < ns; ++j) FRCNN_REQUIRE(!merge_overlap(src[j], wsp), "eval_merge: a shard buffer overlaps the workspace");
 
-    MergeWs ws;
-    merge_ws_layout(n1, n2, eval_ws_base(workspace), &ws);
     const long long tps1 = (SR + MERGE_SCAN_BLOCK - 1) / MERGE_SCAN_BLOCK, tps2 = (SI + MERGE_ROW_BLOCK - 1) / MERGE_ROW_BLOCK;
     ws.NB1 = (long long)W * tps1;                               // <= n1 / MERGE_SCAN_BLOCK + W
     ws.NB2 = (long long)W * tps2;

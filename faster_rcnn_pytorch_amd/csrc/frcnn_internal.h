@@ -1,6 +1,7 @@
 // frcnn_internal.h -- structures and launchers shared between the .hip files.
 #pragma once
 #include "frcnn_common.h"
+#include "frcnn_host.h"
 
 #define FRCNN_MAX_LEVELS 8
 #define FRCNN_MAX_BASE 16
@@ -23,14 +24,12 @@ int frcnn_launch_prologue(const float *reg, const float *cls, const float *ancho
                           void *sample_ctl, int64_t pre_k, hipStream_t s);
 
 // top-K: count must be zero before topk_scatter runs; zero_count = true lets the rank kernel clear it.
-size_t frcnn_ws_topk(int64_t N);
 // sampled: the splitters are already in the workspace's control block (frcnn_topk_sample_ctl(ws, N); nullptr below the sample sort's size)
 void *frcnn_topk_sample_ctl(void *ws, int64_t N);
 int frcnn_launch_topk(const float *scores, const float *boxes_in, int64_t N, int64_t K, int proposal_mode,
                       int64_t *out_idx, float *out_scores, float *out_boxes, int32_t *out_count,
                       void *ws, size_t ws_bytes, bool sampled, hipStream_t s);
 
-size_t frcnn_ws_nms(int64_t K);
 // pre_zeroed: the caller has already cleared the region frcnn_nms_zero_region() describes (e.g. inside an earlier kernel of the
 // same stream); otherwise frcnn_launch_nms clears it with a memset node.
 int frcnn_launch_nms(const float *boxes, const int32_t *cls, const int32_t *n_boxes_dev, int64_t K, float thr, int64_t post_k,

@@ -1,8 +1,9 @@
 // input_dev.h -- what the transforms of the device input stage (preprocess.hip, mosaic.hip, photometric.hip, crop.hip) share, one copy each:
-// the host checks of a frame's sides and of two buffers' overlap, the workspace carver, the window table of one axis of one resize with
+// the host checks of a frame's sides and of two buffers' overlap, the window table of one axis of one resize with
 // its two device users (fill a row, produce one output pixel of a pass), the clip of a box to a region, and one step of the ordered
 // compaction of box rows.  The resampler's arithmetic itself stays in resample_dev.h.
 #pragma once
+#include "frcnn_host.h"
 #include "resample_dev.h"
 
 #define IN_SIDE_MAX 32767                 // a frame side: 32767^2 pixels < 2^30, and 3 * 32767^2 bytes index in 32 bits
@@ -16,25 +17,12 @@ static inline bool in_overlap(const void *a, size_t na, const void *b, size_t nb
     return a && b && pa < pb + nb && pb < pa + na;
 }
 
-// Carves a workspace into pieces that each start on a 256-byte boundary.  base == nullptr: nothing is addressed, only `o` (the bytes
-// needed so far) counts -- the *_workspace functions and the entry points run the same layout code.
-struct InCarver {
-    char *base;
-    size_t o;
-    template <class T> T *get(size_t count)
-    {
-        T *q = base ? (T *)(base + o) : nullptr;
-        o += align_up(count * sizeof(T), 256);
-        return q;
-    }
-};
-
 // The window table of one axis of one resize: row r holds one output index's window, b[2r] = its first source index, b[2r + 1] = its
 // number of taps (<= ks), k[r * ks .. r * ks + ks) = the weights (resample_dev.h).  Which output index a row belongs to is the owner's
 // business: preprocess.hip and mosaic.hip keep row i for index i, crop.hip keeps the region's indices only.
 struct RsAxis { int32_t *b, *k; int ks; };
 
-static inline RsAxis rs_axis_take(InCarver &c, int in_size, int out_size, int n_rows)
+static inline RsAxis rs_axis_take(WsCarver &c, int in_size, int out_size, int n_rows)
 {
     RsAxis a;
     a.ks = rs_ksize_host(in_size, out_size);

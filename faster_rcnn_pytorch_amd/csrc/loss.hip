@@ -143,7 +143,7 @@ FRCNN_EXPORT int frcnn_detection_loss(const float *rpn_cls, const float *rpn_reg
     const int nb_rpn = (int)((N + 255) / 256 < LOSS_MAX_BLOCKS ? (N + 255) / 256 : LOSS_MAX_BLOCKS);
     const int nb_head = (int)((R + 3) / 4 < LOSS_MAX_BLOCKS ? (R + 3) / 4 : LOSS_MAX_BLOCKS);
     const size_t need = 64 + (size_t)(nb_rpn + nb_head) * sizeof(LossAcc);
-    if (workspace_bytes < need) return frcnn_set_error(FRCNN_ERR_WORKSPACE, "detection_loss: workspace %zu < %zu bytes", workspace_bytes, need);
+    FRCNN_REQUIRE_WS("detection_loss", workspace_bytes, need);
     hipStream_t s = (hipStream_t)stream;
     int32_t *ticket = (int32_t *)workspace;                            // zero between calls (see the file header)
     LossAcc *slots = (LossAcc *)((char *)workspace + 64);

@@ -196,7 +196,7 @@ static bool mosaic_shapes_ok(const int32_t *src_hw, int size, int max_size, int 
 
 static size_t mosaic_ws_layout(void *base, const int32_t *src_hw, const int H1[4], const int W1[4], int size, MosaicDesc *d)
 {
-    InCarver c = {(char *)base, 0};
+    WsCarver c(base);
     d->size = size;
     d->regions = c.get<int32_t>(16);
     for (int t = 0; t < 4; ++t) {
@@ -207,7 +207,7 @@ static size_t mosaic_ws_layout(void *base, const int32_t *src_hw, const int H1[4
         T.tmp1 = c.get<uint8_t>((size_t)T.h * T.W1 * 3); T.img1 = c.get<uint8_t>((size_t)T.H1 * T.W1 * 3);
         T.tmp2 = c.get<uint8_t>((size_t)T.H1 * size * 3);
     }
-    return c.o;
+    return c.bytes();
 }
 
 FRCNN_EXPORT size_t frcnn_mosaic_workspace(const int32_t *src_hw, int size, int max_size)

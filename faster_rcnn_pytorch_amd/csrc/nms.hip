@@ -794,34 +794,33 @@ static bool nms_use_cascade(int64_t K)
 }
 static NmsWs carve_nms(void *ws, int64_t K)
 {
-    NmsWs w; char *p = (char *)ws; size_t o = 0;
-    auto take = [&](size_t b) { void *r = p ? p + o : nullptr; o += align_up(b, 256); return r; };
+    NmsWs w; WsCarver c(ws);
     const bool casc = nms_use_cascade(K);
     w.T = casc ? NMS_T_MAX : (int)K;
     const int64_t Kl[2] = {w.T, casc ? K - w.T : 0};
     for (int l = 0; l < 2; ++l) {
         w.L[l].nblk = (int)((Kl[l] + 63) / 64);
         w.L[l].nzw = (w.L[l].nblk + 63) / 64;
-        w.L[l].sup = Kl[l] ? (u64 *)take((size_t)Kl[l] * w.L[l].nblk * 8 + NMS_WS_PAD) : nullptr;
+        w.L[l].sup = Kl[l] ? (u64 *)c.take((size_t)Kl[l] * w.L[l].nblk * 8 + NMS_WS_PAD) : nullptr;
     }
-    w.cbox = casc ? (float4 *)take((size_t)Kl[1] * 16) : nullptr;
-    w.cidx = casc ? (int32_t *)take((size_t)Kl[1] * 4) : nullptr;
-    w.ccls = casc ? (int32_t *)take((size_t)Kl[1] * 4) : nullptr;
+    w.cbox = casc ? (float4 *)c.take((size_t)Kl[1] * 16) : nullptr;
+    w.cidx = casc ? (int32_t *)c.take((size_t)Kl[1] * 4) : nullptr;
+    w.ccls = casc ? (int32_t *)c.take((size_t)Kl[1] * 4) : nullptr;
     // ONE region to clear before the stage runs: the per-box bitmaps of non-zero words, the kept / removed bitmaps and the tile flags of
     // both levels, the look-back words, the control block (abort flag, ticket, survivor count)
-    const size_t z0 = o;
-    w.zero_begin = p ? p + o : nullptr;
+    const size_t z0 = c.bytes();
+    w.zero_begin = c.here();
     for (int l = 0; l < 2; ++l) {
         const size_t nb = (size_t)w.L[l].nblk;
-        w.L[l].nz = Kl[l] ? (u64 *)take((size_t)Kl[l] * w.L[l].nzw * 8) : nullptr;
-        w.L[l].kept = Kl[l] ? (u64 *)take((nb + 1) * 8) : nullptr;
-        w.L[l].rem = Kl[l] ? (u64 *)take((nb + 1) * 8) : nullptr;
-        w.L[l].done = Kl[l] ? (int32_t *)take((nb * (nb + 1) / 2 + 1) * 4) : nullptr;   // one flag per published tile (the resolver's start condition)
+        w.L[l].nz = Kl[l] ? (u64 *)c.take((size_t)Kl[l] * w.L[l].nzw * 8) : nullptr;
+        w.L[l].kept = Kl[l] ? (u64 *)c.take((nb + 1) * 8) : nullptr;
+        w.L[l].rem = Kl[l] ? (u64 *)c.take((nb + 1) * 8) : nullptr;
+        w.L[l].done = Kl[l] ? (int32_t *)c.take((nb * (nb + 1) / 2 + 1) * 4) : nullptr; // one flag per published tile (the resolver's start condition)
     }
-    w.look = casc ? (int32_t *)take(((size_t)w.L[1].nblk + 1) * 4) : nullptr;
-    w.ctl = (int32_t *)take(64);
-    w.zero_bytes = o - z0;
-    w.total = o;
+    w.look = casc ? (int32_t *)c.take(((size_t)w.L[1].nblk + 1) * 4) : nullptr;
+    w.ctl = (int32_t *)c.take(64);
+    w.zero_bytes = c.bytes() - z0;
+    w.total = c.bytes();
     return w;
 }
 size_t frcnn_ws_nms(int64_t K) { return carve_nms(nullptr, K).total; }
@@ -847,13 +846,9 @@ static int launch_level(const float4 *boxes, const int32_t *cls, const int32_t *
     // leave most of the chip's wave slots to the tile workgroups.  Above that the same kernel runs as two launches: tiles only, then
     // resolver only (all flags already up).  HIP does not promise in-order dispatch; if the assumption ever failed the resolver's
     // bounded wait runs out, the abort flag goes up, the count comes out as -1 and the step's loss is NaN (never a silent wrong result).
-    static const int fused_max_res = [] {
-        const char *e = getenv("FRCNN_NMS_FUSED_MAX_RES");
-        if (e) return atoi(e);
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        return cus * 4;
-    }();
+    static const char *const fused_env = getenv("FRCNN_NMS_FUSED_MAX_RES");       // read once
+    static const int fused_env_res = fused_env ? atoi(fused_env) : 0;
+    const int fused_max_res = fused_env ? fused_env_res : frcnn_cu_count_or(256) * 4;
     const bool dense = nms_use_dense(nblk);
 #define NMS_LAUNCH_ARGS boxes, cls, n_dev, Kl, thr, nblk, L.nzw, n_res_arg, L.sup, L.nz, L.kept, L.rem, L.done, abort_flag, ea
     auto launch = [&](unsigned grid, int n_res_arg) {
@@ -883,8 +878,7 @@ int frcnn_launch_nms(const float *boxes, const int32_t *cls, const int32_t *n_bo
                      int64_t *out_keep, float *out_rois, const int64_t *src_map, int64_t *out_src, int32_t *out_count,
                      void *ws, size_t ws_bytes, bool pre_zeroed, hipStream_t s)
 {
-    if (ws_bytes < frcnn_ws_nms(K))
-        return frcnn_set_error(FRCNN_ERR_WORKSPACE, "nms: workspace %zu < %zu bytes", ws_bytes, frcnn_ws_nms(K));
+    FRCNN_REQUIRE_WS("nms", ws_bytes, frcnn_ws_nms(K));
     if ((K + 63) / 64 > NMS_MAX_BLOCKS) return frcnn_set_error(FRCNN_ERR_UNSUPPORTED, "nms: K=%lld above limit %d", (long long)K, NMS_MAX_BLOCKS * 64);
     const NmsWs w = carve_nms(ws, K);
     if (!pre_zeroed && hipMemsetAsync(w.zero_begin, 0, w.zero_bytes, s) != hipSuccess) return frcnn_set_error(FRCNN_ERR_LAUNCH, "nms: memset failed");

@@ -195,16 +195,11 @@ __global__ __launch_bounds__(256) void zo_fill_kernel(const uint8_t *__restrict_
 // workgroups of 256 for `groups` four-pixel groups: at most 8 per CU of the current device, at most PM_MAX_BLOCKS, at least 1
 static int pm_grid(uint32_t groups, unsigned *grid)
 {
-    static int cus[64] = {0};
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return frcnn_set_error(FRCNN_ERR_LAUNCH, "photometric: no current HIP device");
-    if (cus[dev] == 0) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1)
-            return frcnn_set_error(FRCNN_ERR_LAUNCH, "photometric: cannot read the CU count of device %d", dev);
-        cus[dev] = n;
-    }
-    uint32_t need = (groups + 255u) / 256u, cap = 8u * (uint32_t)cus[dev];
+    const int cus = frcnn_cu_count();
+    if (cus < 1) return frcnn_set_error(FRCNN_ERR_LAUNCH, "photometric: cannot read the CU count of device %d", dev);
+    uint32_t need = (groups + 255u) / 256u, cap = 8u * (uint32_t)cus;
     if (cap > PM_MAX_BLOCKS) cap = PM_MAX_BLOCKS;
     if (need > cap) need = cap;
     *grid = need < 1u ? 1u : need;

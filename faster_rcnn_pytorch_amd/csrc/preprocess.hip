@@ -79,11 +79,11 @@ struct PreWs { RsAxis x, y; uint8_t *tmp; size_t total; };
 static PreWs pre_ws_layout(void *base, int h, int w, int oh, int ow)
 {
     PreWs p;
-    InCarver c = {(char *)base, 0};
+    WsCarver c(base);
     p.x = rs_axis_take(c, w, ow, ow);
     p.y = rs_axis_take(c, h, oh, oh);
     p.tmp = c.get<uint8_t>((size_t)h * ow * 3);
-    p.total = c.o;
+    p.total = c.bytes();
     return p;
 }
 

@@ -21,22 +21,20 @@ struct ProposalWs {
 static ProposalWs carve(void *ws, int64_t N, int64_t K, int64_t P)
 {
     ProposalWs w;
-    char *p = (char *)ws;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { void *r = p ? p + o : nullptr; o += align_up(bytes, 256); return r; };
-    w.boxes = (float *)take((size_t)N * 16);
-    w.scores = (float *)take((size_t)N * 4);
-    w.sidx = (int64_t *)take((size_t)K * 8);
-    w.sscores = (float *)take((size_t)K * 4);
-    w.sboxes = (float *)take((size_t)K * 16);
-    w.keep = (int64_t *)take((size_t)P * 8);
-    w.ctrl = (int32_t *)take(256);
-    w.lvl = (int32_t *)take((size_t)K * 4);
+    WsCarver c(ws);
+    w.boxes = (float *)c.take((size_t)N * 16);
+    w.scores = (float *)c.take((size_t)N * 4);
+    w.sidx = (int64_t *)c.take((size_t)K * 8);
+    w.sscores = (float *)c.take((size_t)K * 4);
+    w.sboxes = (float *)c.take((size_t)K * 16);
+    w.keep = (int64_t *)c.take((size_t)P * 8);
+    w.ctrl = (int32_t *)c.take(256);
+    w.lvl = (int32_t *)c.take((size_t)K * 4);
     w.topk_bytes = frcnn_ws_topk(N);
-    w.topk_ws = take(w.topk_bytes);
+    w.topk_ws = c.take(w.topk_bytes);
     w.nms_bytes = frcnn_ws_nms(K);
-    w.nms_ws = take(w.nms_bytes);
-    w.total = o;
+    w.nms_ws = c.take(w.nms_bytes);
+    w.total = c.bytes();
     return w;
 }
 
@@ -67,8 +65,7 @@ FRCNN_EXPORT int frcnn_region_proposal(const float *reg, const float *cls, const
     const int64_t K = pre_nms_top_k < N ? pre_nms_top_k : N;
     const int64_t P = post_nms_top_k;
     ProposalWs w = carve(workspace, N, K, K);
-    if (workspace_bytes < w.total)
-        return frcnn_set_error(FRCNN_ERR_WORKSPACE, "region_proposal: workspace %zu < %zu bytes", workspace_bytes, w.total);
+    FRCNN_REQUIRE_WS("region_proposal", workspace_bytes, w.total);
     hipStream_t s = (hipStream_t)stream;
     AnchorDesc d;
     if (!anchors) {

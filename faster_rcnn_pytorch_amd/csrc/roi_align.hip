@@ -993,21 +993,20 @@ FRCNN_EXPORT int frcnn_ms_roi_align_fwd(const float *const *feats, const int *H,
 struct RaBwdWs { int32_t *cnt, *tbase, *tnseg, *slot, *tix; int4 *items; RoiEnt *ent; float *pool, *part; int cap_items; size_t total; };
 static RaBwdWs carve_ra_bwd(void *ws, int64_t tiles, int64_t R, int n_cg)
 {
-    RaBwdWs w; char *p = (char *)ws; size_t o = 0;
-    auto take = [&](size_t b) { void *r = p ? p + o : nullptr; o += align_up(b, 256); return r; };
+    RaBwdWs w; WsCarver c(ws);
     // a RoI meets at most ~15 tiles of its level: at most tiles + 15 R / RS_SPLIT items; the plan kernel coarsens the split if not
     const int64_t cap_items = tiles + 15 * R / RS_SPLIT + 1;
     w.cap_items = (int)cap_items;
-    w.cnt = (int32_t *)take((size_t)(tiles + 1) * 4);
-    w.tbase = (int32_t *)take((size_t)(tiles + 1) * 4);
-    w.tnseg = (int32_t *)take((size_t)(tiles + 1) * 4);
-    w.tix = (int32_t *)take((size_t)(tiles + 1) * n_cg * 4);           // last-segment tickets, one per (tile, channel group): zeroed by the lists launch
-    w.items = (int4 *)take((size_t)(cap_items + RS_NSEG) * sizeof(int4));
-    w.slot = (int32_t *)take((size_t)(cap_items + RS_NSEG) * 4);
-    w.ent = (RoiEnt *)take((size_t)tiles * (size_t)(R > 0 ? R : 1) * sizeof(RoiEnt));
-    w.pool = (float *)take((size_t)(R > 0 ? R : 1) * RA_MAXT * RA_REC * sizeof(float));
-    w.part = (float *)take((size_t)cap_items * n_cg * (RT_CB * RT_TH * RT_TW) * sizeof(float));
-    w.total = o;
+    w.cnt = (int32_t *)c.take((size_t)(tiles + 1) * 4);
+    w.tbase = (int32_t *)c.take((size_t)(tiles + 1) * 4);
+    w.tnseg = (int32_t *)c.take((size_t)(tiles + 1) * 4);
+    w.tix = (int32_t *)c.take((size_t)(tiles + 1) * n_cg * 4);         // last-segment tickets, one per (tile, channel group): zeroed by the lists launch
+    w.items = (int4 *)c.take((size_t)(cap_items + RS_NSEG) * sizeof(int4));
+    w.slot = (int32_t *)c.take((size_t)(cap_items + RS_NSEG) * 4);
+    w.ent = (RoiEnt *)c.take((size_t)tiles * (size_t)(R > 0 ? R : 1) * sizeof(RoiEnt));
+    w.pool = (float *)c.take((size_t)(R > 0 ? R : 1) * RA_MAXT * RA_REC * sizeof(float));
+    w.part = (float *)c.take((size_t)cap_items * n_cg * (RT_CB * RT_TH * RT_TW) * sizeof(float));
+    w.total = c.bytes();
     return w;
 }
 static int64_t ra_bwd_tiles(const int *H, const int *W, int n_levels)
@@ -1046,7 +1045,7 @@ FRCNN_EXPORT int frcnn_ms_roi_align_bwd(const float *grad_out, float *const *gra
         const int n_cg = (C + RT_CB - 1) / RT_CB;
         const size_t need = frcnn_ms_roi_align_bwd_workspace(H, W, n_levels, C, R);
         FRCNN_REQUIRE(workspace != nullptr, "ms_roi_align_bwd: NULL workspace");
-        if (workspace_bytes < need) return frcnn_set_error(FRCNN_ERR_WORKSPACE, "ms_roi_align_bwd: workspace %zu < %zu bytes", workspace_bytes, need);
+        FRCNN_REQUIRE_WS("ms_roi_align_bwd", workspace_bytes, need);
         const RaBwdWs w = carve_ra_bwd(workspace, tiles, R, n_cg);
         const int cap = (int)(R > 0 ? R : 1);
         static const bool use_records = [] { const char *e = getenv("FRCNN_RA_RECORDS"); return !e || atoi(e) != 0; }();
@@ -1075,13 +1074,12 @@ FRCNN_EXPORT int frcnn_ms_roi_align_bwd(const float *grad_out, float *const *gra
         FLv.fill0[FRCNN_MAX_LEVELS] = (int)fills;
         const int64_t n_item_blocks = (int64_t)w.cap_items * n_cg;
         FRCNN_REQUIRE(n_item_blocks + fills < ((int64_t)1 << 31), "ms_roi_align_bwd: grid too large");
-        static const int resident = [] {                   // workgroups of the tile kernel the device holds at once
-            int dev = 0, cus = 256, per = 5;
-            hipDeviceProp_t pr;
-            if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) cus = pr.multiProcessorCount;
+        static const int per_cu = [] {                     // workgroups of the tile kernel a CU holds at once
+            int per = 5;
             if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, roi_align_bwd_tile_kernel<float, true>, 256, 0) != hipSuccess || per < 1) per = 5;
-            return cus * per;
+            return per;
         }();
+        const int resident = frcnn_cu_count_or(256) * per_cu;  // ... and the device
         const int n_first = (int)std::min<int64_t>(n_item_blocks, (int64_t)resident / n_cg * n_cg);
         if (C % RT_CB == 0 && ((size_t)grad_out & 15) == 0)
             FRCNN_LAUNCH((roi_align_bwd_tile_kernel<float, true>), dim3((unsigned)(n_item_blocks + fills)), dim3(256), 0, s, L, T, FLv, C, aligned,

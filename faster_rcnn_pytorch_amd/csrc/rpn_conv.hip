@@ -531,7 +531,19 @@ __global__ __launch_bounds__(256) void rpn_conv3x3_bwd_data_kernel(ConvLevels L,
     }
 }
 
-size_t frcnn_ws_rpn_conv(void) { return (size_t)(16 * 9 * 256 * 16 + 8 * 2 * 32 * 2 * 8) * 2; }
+// workspace of the forward and the backward-data launch: the packed 3x3 weights | the packed head weights (forward only), bf16
+#define RC3_W3P_ELEMS (16 * 9 * 256 * 16)
+struct RpnConvWs { unsigned short *w3p, *whp; size_t total; };
+static RpnConvWs rpn_conv_ws_layout(void *ws)
+{
+    RpnConvWs w;
+    WsCarver c(ws);
+    w.w3p = c.get<unsigned short>(RC3_W3P_ELEMS);
+    w.whp = c.get<unsigned short>(8 * 2 * 32 * 2 * 8);
+    w.total = c.bytes();
+    return w;
+}
+size_t frcnn_ws_rpn_conv(void) { return rpn_conv_ws_layout(nullptr).total; }
 
 // levels -> ConvLevels + launch geometry shared by the forward and the backward-data launch
 static int rpn_conv_levels(const char *who, const void *const *in_levels, void *const *out_levels, const int *H, const int *W, int n_levels,
@@ -558,27 +570,10 @@ static int rpn_conv_levels(const char *who, const void *const *in_levels, void *
     L.n_levels = n_levels;
     FRCNN_REQUIRE(tiles < ((int64_t)1 << 30), "%s: too many tiles", who);
     // tiles of the last, at most half-full round of CUs are split into halves (see the kernel)
-    int n_cu = 0;
-    {
-        int dev = -1;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0) n_cu = 256;
-    }
+    const int n_cu = frcnn_cu_count_or(256);
     const int64_t rem = tiles % n_cu;
     *first_split = (int)((rem > 0 && 2 * rem <= n_cu) ? tiles - rem : tiles);
     *grid = (unsigned)(*first_split + 2 * (tiles - *first_split));
-    return FRCNN_OK;
-}
-
-template <typename K>
-static int rpn_conv_reserve_lds(K kernel, const char *who, std::atomic<unsigned char> *done)
-{   // > 64 KB of dynamic LDS is an opt-in per (function, device)
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0) return frcnn_set_error(FRCNN_ERR_LAUNCH, "%s: no current device", who);
-    if (dev >= 64 || !done[dev].load(std::memory_order_acquire)) {
-        const hipError_t rc = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)RC3_LDS_BYTES);
-        if (rc != hipSuccess) return frcnn_set_error(FRCNN_ERR_LAUNCH, "%s: cannot reserve %zu bytes of LDS: %s", who, (size_t)RC3_LDS_BYTES, hipGetErrorString(rc));
-        if (dev < 64) done[dev].store(1, std::memory_order_release);
-    }
     return FRCNN_OK;
 }
 
@@ -588,18 +583,19 @@ FRCNN_EXPORT int frcnn_rpn_conv_bwd_data(const void *const *d_raw_levels_bf16, v
     FRCNN_REQUIRE(C == RC3_C, "rpn_conv_bwd_data: C=%d (this kernel is built for the FPN head: 256 channels)", C);
     FRCNN_REQUIRE(n_levels >= 1 && n_levels <= FRCNN_MAX_LEVELS && d_raw_levels_bf16 && d_feat_levels_bf16 && H && W, "rpn_conv_bwd_data: bad level table");
     FRCNN_REQUIRE(w3 && workspace, "rpn_conv_bwd_data: NULL pointer");
-    if (workspace_bytes < frcnn_ws_rpn_conv()) return frcnn_set_error(FRCNN_ERR_WORKSPACE, "rpn_conv_bwd_data: workspace %zu < %zu bytes", workspace_bytes, frcnn_ws_rpn_conv());
+    const RpnConvWs ws = rpn_conv_ws_layout(workspace);
+    FRCNN_REQUIRE_WS("rpn_conv_bwd_data", workspace_bytes, ws.total);
     ConvLevels L;
     int first_split = 0;
     unsigned grid = 0;
     int rc = rpn_conv_levels("rpn_conv_bwd_data", d_raw_levels_bf16, d_feat_levels_bf16, H, W, n_levels, &L, &first_split, &grid);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    unsigned short *w3p = (unsigned short *)workspace;
-    FRCNN_LAUNCH(rpn_conv_pack_bwd_kernel, dim3(16 * 9 * 256 * 16 / 256), dim3(256), 0, s, w3, w3p);
+    unsigned short *w3p = ws.w3p;
+    FRCNN_LAUNCH(rpn_conv_pack_bwd_kernel, dim3(RC3_W3P_ELEMS / 256), dim3(256), 0, s, w3, w3p);
     FRCNN_CHECK_LAUNCH("rpn_conv_pack_bwd_kernel");
     static std::atomic<unsigned char> done[64];
-    rc = rpn_conv_reserve_lds(rpn_conv3x3_bwd_data_kernel, "rpn_conv_bwd_data", done);
+    rc = frcnn_reserve_lds((const void *)rpn_conv3x3_bwd_data_kernel, RC3_LDS_BYTES, "rpn_conv_bwd_data", done);
     if (rc) return rc;
     FRCNN_LAUNCH(rpn_conv3x3_bwd_data_kernel, dim3(grid), dim3(256), RC3_LDS_BYTES, s, L, first_split, w3p);
     FRCNN_CHECK_LAUNCH("rpn_conv3x3_bwd_data_kernel");
@@ -615,52 +611,21 @@ FRCNN_EXPORT int frcnn_rpn_conv_head_fwd(const void *const *feat_levels_bf16, vo
     FRCNN_REQUIRE(n_levels >= 1 && n_levels <= FRCNN_MAX_LEVELS && feat_levels_bf16 && raw_levels_bf16 && H && W, "rpn_conv_head: bad level table");
     FRCNN_REQUIRE(n_cls > 0 && n_reg > 0 && n_cls + n_reg <= 32, "rpn_conv_head: n_cls + n_reg = %d must be in (0, 32]", n_cls + n_reg);
     FRCNN_REQUIRE(w3 && b3 && w_cls && b_cls && w_reg && b_reg && out_cls && out_reg && workspace, "rpn_conv_head: NULL pointer");
-    if (workspace_bytes < frcnn_ws_rpn_conv()) return frcnn_set_error(FRCNN_ERR_WORKSPACE, "rpn_conv_head: workspace %zu < %zu bytes", workspace_bytes, frcnn_ws_rpn_conv());
-    int64_t pos0[FRCNN_MAX_LEVELS + 1] = {0};
-    for (int k = 0; k < n_levels; ++k) {
-        FRCNN_REQUIRE(feat_levels_bf16[k] && raw_levels_bf16[k] && H[k] > 0 && W[k] > 0 && (int64_t)H[k] * W[k] * RC3_C < ((int64_t)1 << 31), "rpn_conv_head: bad level %d", k);
-        FRCNN_REQUIRE((((uintptr_t)feat_levels_bf16[k] | (uintptr_t)raw_levels_bf16[k]) & 3) == 0, "rpn_conv_head: level %d is not 4-byte aligned", k);
-        pos0[k + 1] = pos0[k] + (int64_t)H[k] * W[k];
-    }
-    FRCNN_REQUIRE(pos0[n_levels] < ((int64_t)1 << 31), "rpn_conv_head: too many positions");
-    hipStream_t s = (hipStream_t)stream;
-    unsigned short *w3p = (unsigned short *)workspace, *whp = w3p + 16 * 9 * 256 * 16;
-    FRCNN_LAUNCH(rpn_conv_pack_kernel, dim3(16 * 9 * 256 * 16 / 256), dim3(256), 0, s, w3, w_cls, n_cls, w_reg, n_reg, w3p, whp);
-    FRCNN_CHECK_LAUNCH("rpn_conv_pack_kernel");
-    const size_t lds = RC3_LDS_BYTES;
-    {   // > 64 KB of dynamic LDS is an opt-in per (function, device)
-        static std::atomic<unsigned char> done[64];
-        int dev = -1;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0) return frcnn_set_error(FRCNN_ERR_LAUNCH, "rpn_conv_head: no current device");
-        if (dev >= 64 || !done[dev].load(std::memory_order_acquire)) {
-            const hipError_t rc = hipFuncSetAttribute((const void *)rpn_conv3x3_head_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (rc != hipSuccess) return frcnn_set_error(FRCNN_ERR_LAUNCH, "rpn_conv_head: cannot reserve %zu bytes of LDS: %s", lds, hipGetErrorString(rc));
-            if (dev < 64) done[dev].store(1, std::memory_order_release);
-        }
-    }
+    const RpnConvWs ws = rpn_conv_ws_layout(workspace);
+    FRCNN_REQUIRE_WS("rpn_conv_head", workspace_bytes, ws.total);
     ConvLevels L;
-    int64_t tiles = 0;
-    for (int l = 0; l < FRCNN_MAX_LEVELS; ++l) {              // unused slots repeat level 0 and start past the last tile
-        const int k = l < n_levels ? l : 0;
-        L.x[l] = (const unsigned short *)feat_levels_bf16[k]; L.raw[l] = (unsigned short *)raw_levels_bf16[k];
-        L.H[l] = H[k]; L.W[l] = W[k];
-        L.tiles_x[l] = (W[k] + RC3_TW - 1) / RC3_TW;
-        L.tile0[l] = (int)tiles; L.pos0[l] = (int)pos0[k];
-        if (l < n_levels) tiles += (int64_t)L.tiles_x[l] * ((H[k] + RC3_TH - 1) / RC3_TH);
-    }
-    L.tile0[FRCNN_MAX_LEVELS] = (int)tiles;
-    L.n_levels = n_levels;
-    FRCNN_REQUIRE(tiles < ((int64_t)1 << 30), "rpn_conv_head: too many tiles");
-    // tiles of the last, at most half-full round of CUs are split into halves (see the kernel)
-    int n_cu = 0;
-    {
-        int dev = -1;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0) n_cu = 256;
-    }
-    const int64_t rem = tiles % n_cu;
-    const int first_split = (int)((rem > 0 && 2 * rem <= n_cu) ? tiles - rem : tiles);
-    const unsigned grid = (unsigned)(first_split + 2 * (tiles - first_split));
-    FRCNN_LAUNCH(rpn_conv3x3_head_kernel, dim3(grid), dim3(256), lds, s, L, first_split, w3p, b3, whp, b_cls, n_cls, b_reg, n_reg, out_cls, out_reg);
+    int first_split = 0;
+    unsigned grid = 0;
+    int rc = rpn_conv_levels("rpn_conv_head", feat_levels_bf16, raw_levels_bf16, H, W, n_levels, &L, &first_split, &grid);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    unsigned short *w3p = ws.w3p, *whp = ws.whp;
+    FRCNN_LAUNCH(rpn_conv_pack_kernel, dim3(RC3_W3P_ELEMS / 256), dim3(256), 0, s, w3, w_cls, n_cls, w_reg, n_reg, w3p, whp);
+    FRCNN_CHECK_LAUNCH("rpn_conv_pack_kernel");
+    static std::atomic<unsigned char> done[64];
+    rc = frcnn_reserve_lds((const void *)rpn_conv3x3_head_kernel, RC3_LDS_BYTES, "rpn_conv_head", done);
+    if (rc) return rc;
+    FRCNN_LAUNCH(rpn_conv3x3_head_kernel, dim3(grid), dim3(256), RC3_LDS_BYTES, s, L, first_split, w3p, b3, whp, b_cls, n_cls, b_reg, n_reg, out_cls, out_reg);
     FRCNN_CHECK_LAUNCH("rpn_conv3x3_head_kernel");
     return FRCNN_OK;
 }
@@ -984,7 +949,7 @@ FRCNN_EXPORT int frcnn_rpn_conv_wgrad(const void *const *feat_levels_bf16, const
 {
     FRCNN_REQUIRE(C == RC3_C, "rpn_conv_wgrad: C=%d (this kernel is built for the FPN head: 256 channels)", C);
     FRCNN_REQUIRE(n_levels >= 1 && n_levels <= FRCNN_MAX_LEVELS && feat_levels_bf16 && d_raw_levels_bf16 && H && W && dw3 && workspace, "rpn_conv_wgrad: bad argument");
-    if (workspace_bytes < frcnn_ws_rpn_conv_wgrad()) return frcnn_set_error(FRCNN_ERR_WORKSPACE, "rpn_conv_wgrad: workspace %zu < %zu bytes", workspace_bytes, frcnn_ws_rpn_conv_wgrad());
+    FRCNN_REQUIRE_WS("rpn_conv_wgrad", workspace_bytes, frcnn_ws_rpn_conv_wgrad());
     WgradLevels L;
     int64_t segs = 0, cost = 0;
     int lvl_cost[FRCNN_MAX_LEVELS] = {0};
@@ -1006,8 +971,7 @@ FRCNN_EXPORT int frcnn_rpn_conv_wgrad(const void *const *feat_levels_bf16, const
     L.n_levels = n_levels;
     FRCNN_REQUIRE(segs < ((int64_t)1 << 30), "rpn_conv_wgrad: too many positions");
     // K splits: 16 column groups (8 input-channel chunks x 2 output-channel halves) x splits workgroups = one round of the chip
-    int n_cu = 256;
-    { int dev = -1; if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0) n_cu = 256; }
+    const int n_cu = frcnn_cu_count_or(256);
     const int groups = (RC3_C / WG_CI) * (RC3_C / WG_CO);           // workgroups per split: input-channel chunks x output-channel parts
     int splits = n_cu / groups;
     if (splits < 1) splits = 1;
@@ -1027,15 +991,8 @@ FRCNN_EXPORT int frcnn_rpn_conv_wgrad(const void *const *feat_levels_bf16, const
     }
     hipStream_t s = (hipStream_t)stream;
     static std::atomic<unsigned char> done[64];
-    {
-        int dev = -1;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0) return frcnn_set_error(FRCNN_ERR_LAUNCH, "rpn_conv_wgrad: no current device");
-        if (dev >= 64 || !done[dev].load(std::memory_order_acquire)) {
-            const hipError_t rc = hipFuncSetAttribute((const void *)rpn_conv3x3_wgrad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WG_LDS_BYTES);
-            if (rc != hipSuccess) return frcnn_set_error(FRCNN_ERR_LAUNCH, "rpn_conv_wgrad: cannot reserve %d bytes of LDS: %s", (int)WG_LDS_BYTES, hipGetErrorString(rc));
-            if (dev < 64) done[dev].store(1, std::memory_order_release);
-        }
-    }
+    const int rc = frcnn_reserve_lds((const void *)rpn_conv3x3_wgrad_kernel, WG_LDS_BYTES, "rpn_conv_wgrad", done);
+    if (rc) return rc;
     FRCNN_LAUNCH(rpn_conv3x3_wgrad_kernel, dim3((unsigned)splits, (unsigned)groups), dim3(256), WG_LDS_BYTES, s, L, (float *)workspace);
     FRCNN_CHECK_LAUNCH("rpn_conv3x3_wgrad_kernel");
     FRCNN_LAUNCH(rpn_conv_wgrad_finalize_kernel, dim3(RC3_C * RC3_C * 9 / 256), dim3(256), 0, s, (const float *)workspace, splits, dw3);

@@ -1744,36 +1744,25 @@ __global__ __launch_bounds__(256, CW_WPS) void rpn_conv3x3_f32_wgrad_kernel(CwAr
 struct CfWs { int *cnt, *cnt2; float *wt, *part, *part2, *U, *V, *M; size_t total; };      // cnt2 / part2: the second product of a launch that holds two
 static int cf_ranges()
 {
-    static int per_dev[64];                                          // 0 = not asked yet; per device: one process may drive several
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    int g = __atomic_load_n(&per_dev[dev], __ATOMIC_RELAXED);
-    if (!g) {
-        int cus = 256;
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        g = CF_WPS * cus;                                            // CF_WPS workgroups of 51.7 KB LDS per CU
-        __atomic_store_n(&per_dev[dev], g, __ATOMIC_RELAXED);
-    }
-    return g;
+    return CF_WPS * frcnn_cu_count_or(256);                         // CF_WPS workgroups of 51.7 KB LDS per CU
 }
 static CfWs cf_carve(void *ws, int C, size_t u_floats = 0, size_t vm_floats = 0)
 {
     // C = max(Cin, Cout) rounded up to 128: the direct kernels' share (Cin = Cout there); u_floats / vm_floats != 0 add the Winograd stage's
     // operand buffers (transformed weights; transformed inputs and products, either of which may be the wider side)
-    CfWs w; char *p = (char *)ws; size_t o = 0;
-    auto take = [&](size_t b) { void *r = p ? p + o : nullptr; o += align_up(b, 256); return r; };
-    w.cnt = (int *)take(CF_MAX_TILES * sizeof(int));
-    w.cnt2 = (int *)take(CF_MAX_TILES * sizeof(int));              // (at a fixed offset like cnt: every layer's calls leave the same words zero)
-    w.wt = (float *)take((size_t)C * C * 9 * sizeof(float));
+    CfWs w; WsCarver c(ws);
+    w.cnt = (int *)c.take(CF_MAX_TILES * sizeof(int));
+    w.cnt2 = (int *)c.take(CF_MAX_TILES * sizeof(int));            // (at a fixed offset like cnt: every layer's calls leave the same words zero)
+    w.wt = (float *)c.take((size_t)C * C * 9 * sizeof(float));
     const size_t fwd = (size_t)cf_ranges() * 2 * CF_SLAB * sizeof(float);
     const size_t wg_tiles = (size_t)(C / 32) * (C / 32);           // weight gradient: tiles x workgroups per tile <= max(tiles, CUs) slabs of one tile
     const size_t wg = std::max<size_t>(wg_tiles, (size_t)cf_ranges() / CF_WPS * CW_WPS) * (32 * 32 * 9) * sizeof(float);
-    w.part = (float *)take(fwd > wg ? fwd : wg);
-    w.part2 = (float *)take(fwd / CF_WPS);                          // the k-contiguous product's ranges (wn_ranges_nt), two slabs each
-    w.U = u_floats ? (float *)take(u_floats * sizeof(float)) : nullptr;
-    w.V = vm_floats ? (float *)take(vm_floats * sizeof(float)) : nullptr;
-    w.M = vm_floats ? (float *)take(vm_floats * sizeof(float)) : nullptr;
-    w.total = o;
+    w.part = (float *)c.take(fwd > wg ? fwd : wg);
+    w.part2 = (float *)c.take(fwd / CF_WPS);                        // the k-contiguous product's ranges (wn_ranges_nt), two slabs each
+    w.U = u_floats ? (float *)c.take(u_floats * sizeof(float)) : nullptr;
+    w.V = vm_floats ? (float *)c.take(vm_floats * sizeof(float)) : nullptr;
+    w.M = vm_floats ? (float *)c.take(vm_floats * sizeof(float)) : nullptr;
+    w.total = c.bytes();
     return w;
 }
 size_t frcnn_ws_rpn_conv_f32(int64_t C) { return (C > 0 && C <= 4096) ? cf_carve(nullptr, (int)C).total : 0; }
@@ -2090,7 +2079,7 @@ static int cf_check(WnGeom *g, const CfCall &c)
         FRCNN_REQUIRE(l != g->large_level, "%s: level %d too large", what, l);
     }
     const size_t need = wn_workspace(*g);
-    if (c.ws_bytes < need) return frcnn_set_error(FRCNN_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", what, c.ws_bytes, need);
+    FRCNN_REQUIRE_WS(what, c.ws_bytes, need);
     return FRCNN_OK;
 }
 
@@ -2333,7 +2322,7 @@ FRCNN_EXPORT int frcnn_gemm_nt_f32(const float *A_dev, const float *B_dev, float
     if (M <= 0 || N <= 0 || K <= 0 || splits < 1 || M % 64 != 0 || N % 64 != 0 || K % (WN_KC * splits) != 0 || M > 4096 || N > 4096)
         return frcnn_set_error(FRCNN_ERR_UNSUPPORTED, "gemm_nt_f32: M = %d, N = %d must be multiples of 64 (<= 4096), K = %d of %d x splits (%d)", M, N, K, WN_KC, splits);
     const CfWs ws = cf_carve(workspace, CF_MT);
-    if (workspace_bytes < ws.total) return frcnn_set_error(FRCNN_ERR_WORKSPACE, "gemm_nt_f32: workspace %zu < %zu bytes", workspace_bytes, ws.total);
+    FRCNN_REQUIRE_WS("gemm_nt_f32", workspace_bytes, ws.total);
     const int MT = M % CF_MT == 0 ? CF_MT : 64, NW = N % CF_NT == 0 ? CF_NT : 64, mt = M / MT, nt = N / NW, Ks = K / splits;
     const long long n_tiles = (long long)splits * mt * nt, Kc = Ks / WN_KC, units = n_tiles * Kc;
     FRCNN_REQUIRE(n_tiles <= CF_MAX_TILES && units < (1ll << 31), "gemm_nt_f32: %lld tiles above the limit %d", n_tiles, CF_MAX_TILES);

@@ -487,8 +487,7 @@ FRCNN_EXPORT int frcnn_rpn_head_tail_ml_bwd(const void *const *conv_raw_levels, 
     FRCNN_REQUIRE(dtype == FRCNN_DTYPE_F32 || dtype == FRCNN_DTYPE_BF16, "rpn_head_tail_bwd: dtype %d (0 = f32, 1 = bf16)", dtype);
     FRCNN_REQUIRE(n_cls > 0 && n_reg > 0 && n_cls + n_reg <= 64, "rpn_head_tail_bwd: n_cls + n_reg = %d must be in (0, 64]", n_cls + n_reg);
     FRCNN_REQUIRE(b3 && w_cls && w_reg && g_cls && g_reg && dw_cls && db_cls && dw_reg && db_reg && db3 && workspace, "rpn_head_tail_bwd: NULL pointer");
-    if (workspace_bytes < frcnn_ws_head_bwd(C))
-        return frcnn_set_error(FRCNN_ERR_WORKSPACE, "rpn_head_tail_bwd: workspace %zu < %zu bytes", workspace_bytes, frcnn_ws_head_bwd(C));
+    FRCNN_REQUIRE_WS("rpn_head_tail_bwd", workspace_bytes, frcnn_ws_head_bwd(C));
     HeadBwdLevels L;
     L.n_levels = n_levels;
     int64_t tiles = 0, pos = 0;

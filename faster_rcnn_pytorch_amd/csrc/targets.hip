@@ -882,21 +882,20 @@ __global__ __launch_bounds__(1024) void head_targets_kernel(int variant, const f
 struct RpnWs { unsigned long long *colkey, *colkey2, *snap; RpnCtl *ctl; RpnSel2 *sel2; RpnBList *bl; int8_t *label8; int32_t *list; unsigned *keys; size_t total; };
 static RpnWs carve_rpn(void *ws, int64_t N, int64_t G)
 {
-    RpnWs w; char *p = (char *)ws; size_t o = 0;
-    auto take = [&](size_t b) { void *r = p ? p + o : nullptr; o += align_up(b, 256); return r; };
+    RpnWs w; WsCarver c(ws);
     // FIXED prefix (independent of N and G, so that a workspace reused at another size finds its control words where it left them,
     // zero): the control block, then one 64-byte line per GT box for the largest G the entry point accepts
-    w.ctl = (RpnCtl *)take(sizeof(RpnCtl));
-    w.snap = (unsigned long long *)take(16);
-    w.colkey = (unsigned long long *)take((size_t)RPN_MAX_G * 8 * 8);
-    w.sel2 = (RpnSel2 *)take(sizeof(RpnSel2));                      // the sampler's key histogram + list counters: zero between calls
-    w.bl = (RpnBList *)take(sizeof(RpnBList));
-    w.colkey2 = (unsigned long long *)take((size_t)G * 8 * 8);      // the staged paths' own maxima: cleared per call, so that
+    w.ctl = (RpnCtl *)c.take(sizeof(RpnCtl));
+    w.snap = (unsigned long long *)c.take(16);
+    w.colkey = (unsigned long long *)c.take((size_t)RPN_MAX_G * 8 * 8);
+    w.sel2 = (RpnSel2 *)c.take(sizeof(RpnSel2));                    // the sampler's key histogram + list counters: zero between calls
+    w.bl = (RpnBList *)c.take(sizeof(RpnBList));
+    w.colkey2 = (unsigned long long *)c.take((size_t)G * 8 * 8);    // the staged paths' own maxima: cleared per call, so that
                                                                     // the fused kernel's colkey keeps its "zero between calls" invariant
-    w.label8 = (int8_t *)take((size_t)N);
-    w.list = (int32_t *)take((size_t)N * 4);                        // parity mode: the candidates in anchor order
-    w.keys = (unsigned *)take((size_t)N * 4);                       // device-RNG mode: the Philox keys
-    w.total = o;
+    w.label8 = (int8_t *)c.take((size_t)N);
+    w.list = (int32_t *)c.take((size_t)N * 4);                      // parity mode: the candidates in anchor order
+    w.keys = (unsigned *)c.take((size_t)N * 4);                     // device-RNG mode: the Philox keys
+    w.total = c.bytes();
     return w;
 }
 size_t frcnn_ws_rpn_targets(int64_t N, int64_t G) { return carve_rpn(nullptr, N, G).total; }
@@ -916,13 +915,9 @@ FRCNN_EXPORT int frcnn_rpn_targets_n(int variant, const float *anchors, int64_t 
     FRCNN_REQUIRE(anchors && gt && out_cls && out_reg && out_counts && workspace, "rpn_targets: NULL pointer");
     FRCNN_REQUIRE(n_perm_pos >= 0 && n_perm_neg >= 0 && n_perm_pos < ((int64_t)1 << 31) && n_perm_neg < ((int64_t)1 << 31), "rpn_targets: bad perm length");
     RpnWs w = carve_rpn(workspace, N, G);
-    if (workspace_bytes < w.total) return frcnn_set_error(FRCNN_ERR_WORKSPACE, "rpn_targets: workspace %zu < %zu bytes", workspace_bytes, w.total);
+    FRCNN_REQUIRE_WS("rpn_targets", workspace_bytes, w.total);
     hipStream_t s = (hipStream_t)stream;
-    static const int n_cus = [] {
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        return cus;
-    }();
+    const int n_cus = frcnn_cu_count_or(256);
     static const bool no_fuse = [] { const char *e = getenv("FRCNN_RPN_FUSED"); return e && !strcmp(e, "0"); }();
     const bool device_rng = !perm_pos && !perm_neg;
     const int64_t nb1024 = (N + 1023) / 1024;

@@ -432,24 +432,35 @@ __global__ __launch_bounds__(256) void topk_bucket_kernel(const float *__restric
     }
 }
 
-size_t frcnn_ws_topk(int64_t N)
+// workspace: the sample sort's control block | N packed keys from SS_MIN_N on, the rank sort's partial ranks [nseg][N] below
+struct TopkWs { SsCtl *ctl; u64 *sorted; int32_t *partial; size_t total; };
+static TopkWs topk_ws_layout(void *ws, int64_t N)
 {
-    const int64_t nseg = (N + TOPK_SEG - 1) / TOPK_SEG;
-    if (N >= SS_MIN_N) return align_up(sizeof(SsCtl), 256) + align_up((size_t)N * 8, 256);
-    return align_up((size_t)(nseg > 0 ? nseg : 1) * (size_t)N * sizeof(int32_t), 256);
+    TopkWs w = {};
+    WsCarver c(ws);
+    if (N >= SS_MIN_N) {
+        w.ctl = c.get<SsCtl>(1);
+        w.sorted = c.get<u64>((size_t)N);
+    } else {
+        const int64_t nseg = (N + TOPK_SEG - 1) / TOPK_SEG;
+        w.partial = c.get<int32_t>((size_t)(nseg > 0 ? nseg : 1) * (size_t)N);
+    }
+    w.total = c.bytes();
+    return w;
 }
+size_t frcnn_ws_topk(int64_t N) { return topk_ws_layout(nullptr, N).total; }
 
-void *frcnn_topk_sample_ctl(void *ws, int64_t N) { return N >= SS_MIN_N ? ws : nullptr; }
+void *frcnn_topk_sample_ctl(void *ws, int64_t N) { return topk_ws_layout(ws, N).ctl; }
 
 int frcnn_launch_topk(const float *scores, const float *boxes_in, int64_t N, int64_t K, int proposal_mode,
                       int64_t *out_idx, float *out_scores, float *out_boxes, int32_t *out_count,
                       void *ws, size_t ws_bytes, bool sampled, hipStream_t s)
 {
-    if (ws_bytes < frcnn_ws_topk(N))
-        return frcnn_set_error(FRCNN_ERR_WORKSPACE, "topk: workspace %zu < %zu bytes", ws_bytes, frcnn_ws_topk(N));
+    const TopkWs w = topk_ws_layout(ws, N);
+    FRCNN_REQUIRE_WS("topk", ws_bytes, w.total);
     if (N >= SS_MIN_N) {
-        SsCtl *ctl = (SsCtl *)ws;
-        u64 *sorted = (u64 *)((char *)ws + align_up(sizeof(SsCtl), 256));
+        SsCtl *ctl = w.ctl;
+        u64 *sorted = w.sorted;
         const int gb = (int)((N + 256 * SS_PER_THREAD - 1) / (256 * SS_PER_THREAD));
         if (!sampled) {                                                         // (the proposal prologue has done it otherwise)
             int S, stride;
@@ -488,7 +499,7 @@ int frcnn_launch_topk(const float *scores, const float *boxes_in, int64_t N, int
     }
     const int nseg = (int)((N + TOPK_SEG - 1) / TOPK_SEG);
     const int nrow = (int)((N + TOPK_ROWS - 1) / TOPK_ROWS);
-    int32_t *partial = (int32_t *)ws;
+    int32_t *partial = w.partial;
     FRCNN_LAUNCH(topk_rank_kernel, dim3(nrow, nseg), dim3(TOPK_ROWS), 0, s, scores, (int)N, proposal_mode, partial, out_count);
     FRCNN_CHECK_LAUNCH("topk_rank_kernel");
     FRCNN_LAUNCH(topk_scatter_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, scores,
